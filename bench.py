@@ -9,6 +9,10 @@ q_xt → DiT forward → fused SUBS cross-entropy → weighted loss) followed by
 the bf16 gradient all-reduce overlapped with the backward.  The optimizer is excluded (BASELINE.json metric).  The fp32 →
 bf16 weight cast that autocast performs every forward in the reference is INSIDE the timed region.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps and prints the line.  ``--full`` adds what takes work of its own: the GEMM roofline
+(events around sampled launches inside the timed region), the per-entry-point ``roofline_table`` (extra untimed steps) and the CPU
+baseline.  ``--dump-outputs DIR`` writes what the last timed step handed its caller (bench.dump_outputs) as float32 ``.npy`` files.
 """
 from __future__ import annotations
 
@@ -358,6 +362,36 @@ def cpu_baseline_legs(seed):
     return legs
 
 
+GRAD_SAMPLE = 4096   # gradient elements dumped per parameter tensor (seeded pick); smaller tensors are dumped whole
+
+
+def dump_outputs(path, out, backbone):
+    """What a caller of the timed path receives after its last step, as float32 .npy files under `path` (about 4 MB for the 1.4 B model):
+    the Loss fields (loss, txt_loss, img_loss, per-token nlls, token_mask, modality_mask), every parameter gradient's norm in
+    named_parameters() order (grad_norms) and a fixed, seeded sample of GRAD_SAMPLE elements of each gradient, concatenated in that order
+    (grad_sample).  The same arguments give the same inputs, so two builds can be compared output for output."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for k in ("loss", "txt_loss", "img_loss", "nlls", "token_mask", "modality_mask"):
+        v = getattr(out, k)
+        if torch.is_tensor(v):
+            arrays[k] = v.detach().float()
+    g = torch.Generator().manual_seed(1234)
+    norms, sample = [], []
+    for _, p in backbone.named_parameters():
+        grad = p.grad.detach().reshape(-1).float() if p.grad is not None else torch.zeros(p.numel(), device=p.device)
+        norms.append(grad.norm())
+        if grad.numel() > GRAD_SAMPLE:
+            grad = grad[torch.randint(0, grad.numel(), (GRAD_SAMPLE,), generator=g).to(grad.device)]
+        sample.append(grad)
+    arrays["grad_norms"] = torch.stack(norms)
+    arrays["grad_sample"] = torch.cat(sample)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), v.cpu().numpy().astype(np.float32))
+
+
 def launcher_command(n_gpus, argv, port=None):
     """The command that runs this script on `n_gpus` ranks of one node (one process per GPU over RCCL): what `python bench.py --gpus N` starts
     by itself when it was not launched by torch.distributed.run (main.py:641-656 is the reference's accelerate launch of the same shape)."""
@@ -393,16 +427,21 @@ def main():
     ap.add_argument("--workload", default="unidisc-1.4b-l1280", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default: workload's)")
     ap.add_argument("--dropout", type=float, default=0.1, help="model.dropout (reference extra_large.yaml: 0.1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline-any-world", action="store_true", help="also time the CPU comparator on rank 0 of an N > 1 run (after every rank left the process group)")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--time-every", type=int, default=16, help="bracket 1 GEMM launch in this many with HIP events inside the timed region (1 = all: costs ~1.7 ms/step)")
+    ap.add_argument("--full", action="store_true", help="also measure the GEMM roofline, the roofline_table and the CPU baseline (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--cpu-baseline-any-world", action="store_true", help="with --full: also time the CPU comparator on rank 0 of an N > 1 run (after every rank left the process group)")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: leave out the roofline and the roofline_table")
+    ap.add_argument("--time-every", type=int, default=16, help="with --full: bracket 1 GEMM launch in this many with HIP events inside the timed region (1 = all: costs ~1.7 ms/step)")
     ap.add_argument("--hog-cus", type=int, default=0, help="diagnostics: hold this many CUs with a spinning kernel for the whole run (stand-in for RCCL's channel kernels; "
                     "combine with UDM_GEMM_CUS = 256 - n so the GEMMs plan for the remaining CUs)")
     ap.add_argument("--ddp-mode", default=None, choices=["auto", "overlap", "overlap_planned", "serialized"],
                     help="gradient all-reduce schedule for --gpus > 1 (default: UDM_DDP_MODE or auto = timed in warm-up on all ranks, fastest kept)")
-    ap.add_argument("--table-steps", type=int, default=2, help="extra untimed steps after the timed region with every launch event-timed (roofline_table); 0 = off")
+    ap.add_argument("--table-steps", type=int, default=2, help="with --full: extra untimed steps after the timed region with every launch event-timed (roofline_table); 0 = off")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    kernel_timing = args.full and not args.no_kernel_timing
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -450,7 +489,7 @@ def main():
         sync = ddp.wrap(diff.backbone, mode=args.ddp_mode)
     batch = {k: v.to(device) for k, v in synthetic_batch(args.workload, B, seed).items()}
     timer = KernelTimer(sample=args.time_every)
-    if not args.no_kernel_timing:
+    if kernel_timing:
         timer.install()
 
     def step(i):
@@ -506,6 +545,8 @@ def main():
     per_step_ms = sorted(a.elapsed_time(b) for a, b in zip(marks[:-1], marks[1:]))
     median_ms = per_step_ms[len(per_step_ms) // 2] if len(per_step_ms) % 2 else 0.5 * (per_step_ms[len(per_step_ms) // 2 - 1] + per_step_ms[len(per_step_ms) // 2])
     loss = float(out.loss.detach())
+    if args.dump_outputs and rank == 0:   # before the roofline_table's extra steps overwrite the gradients
+        dump_outputs(args.dump_outputs, out, diff.backbone)
     if world > 1:
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -554,7 +595,7 @@ def main():
         result["rccl_max_nchannels"] = rccl_channels              # NCCL_MAX_NCHANNELS in force (0 = RCCL's default)
         # time the compute stream spent waiting for the comm stream at the end of backward (events around BucketedGradSync.finish)
         result["exposed_comm_ms_per_step"] = sync.exposed_ms() / args.steps
-    if not args.no_kernel_timing and args.table_steps > 0:
+    if kernel_timing and args.table_steps > 0:
         # post-pass, OUTSIDE the timed region: the same step with EVERY launch bracketed by events -> one roofline row per C-ABI entry point
         timer.uninstall()
         full = KernelTimer(names=None)
@@ -593,7 +634,7 @@ def main():
         dist.barrier()
         torch.cuda.synchronize()
         dist.destroy_process_group()
-    want_cpu = not args.no_cpu_baseline and (world == 1 or args.cpu_baseline_any_world)
+    want_cpu = args.full and not args.no_cpu_baseline and (world == 1 or args.cpu_baseline_any_world)
     if rank == 0 and want_cpu:
         try:
             result["cpu_baseline"] = cpu_baseline(args.workload, cfg, diff, seed)
@@ -601,7 +642,7 @@ def main():
                 result["cpu_baseline"]["legs"] = cpu_baseline_legs(seed)
         except Exception as e:  # the GPU number stands on its own; say why the comparator is missing
             result["cpu_baseline"] = {"value": None, "unit": "tokens/s", "cores": os.cpu_count(), "kind": "port", "sample": f"failed: {type(e).__name__}: {e}"}
-    elif rank == 0 and world > 1:
+    elif rank == 0 and world > 1 and args.full:
         result["cpu_baseline"] = None      # measured by the N = 1 line of the same command (contract: rank 0 at N = 1 only)
     if rank == 0:
         print(json.dumps(result), flush=True)

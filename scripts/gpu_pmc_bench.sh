@@ -1,14 +1,14 @@
 #!/bin/bash
 # HBM traffic of the bench command from PMC counters (separate passes: FETCH_SIZE and WRITE_SIZE do not fit one pass).
-TAG=${1:-r01}; R=${GRAFT_REPO_ROOT:-$(pwd)}; mkdir -p $R/gpurun_out/pmcb; export TMPDIR=/tmp; cd /tmp
+TAG=${1:-r01}; R=$(pwd); OUT=${UDM_OUT:-$R/out}; mkdir -p $OUT/pmcb; export TMPDIR=/tmp; cd /tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 900 rocprofv3 --pmc $c --output-format csv -d $R/gpurun_out/pmcb/$c -o pmc -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-timing > $R/gpurun_out/pmcb/$c.log 2>&1
+  timeout 900 rocprofv3 --pmc $c --output-format csv -d $OUT/pmcb/$c -o pmc -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-timing > $OUT/pmcb/$c.log 2>&1
 done
 cd $R; python3 - <<PY
 import csv, glob, collections, json
 agg = collections.defaultdict(lambda: collections.defaultdict(float)); cnt = collections.defaultdict(int)
 for c in ("FETCH_SIZE", "WRITE_SIZE"):
-    for f in glob.glob(f"gpurun_out/pmcb/{c}/**/*counter_collection.csv", recursive=True):
+    for f in glob.glob(f"$OUT/pmcb/{c}/**/*counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(f)):
             kn = r["Kernel_Name"].replace("(anonymous namespace)::", "").replace("void ", "")
             kn = kn.split("(")[0]
@@ -21,7 +21,7 @@ for kn, d in agg.items():
     fetch_b = d.get("FETCH_SIZE", 0) / n * 1024 * 2
     write_b = d.get("WRITE_SIZE", 0) / max(cnt[(kn, "WRITE_SIZE")], 1) * 1024
     out[kn] = dict(launches=n, fetch_bytes_per_launch_corrected=fetch_b, write_bytes_per_launch=write_b, hbm_bytes_per_launch=fetch_b + write_b)
-json.dump(out, open("gpurun_out/pmc_traffic_$TAG.json", "w"), indent=1)
+json.dump(out, open("$OUT/pmc_traffic_$TAG.json", "w"), indent=1)
 for kn, v in sorted(out.items(), key=lambda kv: -kv[1]["hbm_bytes_per_launch"] * kv[1]["launches"])[:14]:
     print(f'{kn[:60]:60s} n={v["launches"]:4d} rd={v["fetch_bytes_per_launch_corrected"]/1e6:9.1f}MB wr={v["write_bytes_per_launch"]/1e6:9.1f}MB')
 PY

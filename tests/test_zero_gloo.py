@@ -71,6 +71,11 @@ def _worker(rank, world, port, min_bucket, q):
                 err = (a - b).abs().max().item()
                 worst = max(worst, err / (a.abs().max().item() + 1e-12))
                 ok = ok and err <= 1e-6 + 1e-5 * a.abs().max().item()
+            # keep the two models in lockstep (as in _worker_acc_ema): the two paths sum the clipping norm in different fp32 orders, and a last-bit difference
+            # flips bf16 roundings of the weight shadows in the NEXT forward, which Adam's normalised update turns into lr-sized differences where a gradient is
+            # near zero.  The replicated model follows the sharded one, so the sharded path still runs on the state its own step and broadcast left.
+            ref.backbone.load_state_dict(sh.backbone.state_dict())
+            ref.backbone.invalidate_shadows()
         flat = torch.cat([p.detach().flatten() for p in sh.backbone.parameters()])
         other = flat.clone()
         dist.broadcast(other, src=0)
@@ -102,7 +107,7 @@ def test_sharded_optimizer_world2(min_bucket):
         assert p.exitcode == 0
     owned_total = 0
     for rank, ok, worst, same, n_owned, n_all, owners, norm_same, rt, nb in res:
-        assert ok, (rank, worst)          # same parameters as the replicated path after three steps
+        assert ok, (rank, worst)          # same parameters as the replicated path after each of three steps
         assert same, rank                 # identical on every rank
         assert owners == [0, 1] and nb >= 2, (owners, nb)
         assert 0 < n_owned < n_all, (n_owned, n_all)     # moments for the owned parameters only
