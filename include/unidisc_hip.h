@@ -188,6 +188,11 @@ int udm_attention_bwd(const void* q, const void* k, const void* v, const void* o
  * L % 256 == 0, L >= 512, H >= 2, (B H) % 8 == 0 then runs the persistent 64-queries-per-wave kernel (csrc/attention_fwd64.hip), and the backward its two generated
  * counterparts (csrc/attention_dq64.hip: dQ + delta + the planes; csrc/attention_dkv64.hip: dK / dV; 16-byte aligned row strides). */
 #define UDM_ATTN_Q_PRESCALED 1
+/* UDM_ATTN_CAUSAL = causal mask (models/dit.py:768, :826, :843 with model.full_attention=false): query i sees keys j <= i.  Both entry points take it, alone or
+ * with UDM_ATTN_Q_PRESCALED; together with sample_ids / doc_ranges it is an argument error (the reference never combines them).  Causal calls always run the
+ * 8-wave kernels of csrc/attention.hip (triangular walks, heavy blocks first); the generated one-wave-per-SIMD programs and the wave-specialised dK / dV
+ * kernel decline them. */
+#define UDM_ATTN_CAUSAL 2
 
 /* ---- embeddings: EmbeddingLayer models/dit.py:1036-1043 (+modality embedding :1402-1411) ------------- */
 int udm_embedding_fwd(const int64_t* ids, const float* E, const int64_t* modality, const float* Em, float* x, int64_t M, int64_t d, int64_t V,

@@ -1,4 +1,4 @@
-// Bidirectional flash attention (forward, dQ, dK/dV) on gfx950 MFMA, bf16 in / fp32 accumulate.
+// Flash attention (forward, dQ, dK/dV) on gfx950 MFMA, bf16 in / fp32 accumulate: bidirectional, document-masked, or causal (CAUSAL).
 //
 // Replaces flash_attn_qkvpacked_func / SDPA / FlexAttention-with-document-mask in the reference
 // (models/dit.py:826-829, :843, :784-812; mask semantics model_utils.py:740-771).
@@ -77,7 +77,9 @@ __global__ __launch_bounds__(256) void attn_doc_ranges_kernel(const int64_t* __r
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
-template <int D, bool HAS_SID, bool USE_TR, int ABL = 0>   // ABL (timing-only ablations, wrong results): 1 = no softmax VALU, 2 = no MFMAs
+// CAUSAL (model.full_attention=false): query i sees keys j <= i.  A block walks only the key tiles below its diagonal (t * 64 < (tile_x + 1) * 128) and
+// the per-element test runs on the two tiles that cross it; blocks are dispatched late query tiles first (the longest walks start first).
+template <int D, bool HAS_SID, bool USE_TR, int ABL = 0, bool CAUSAL = false>   // ABL (timing-only ablations, wrong results): 1 = no softmax VALU, 2 = no MFMAs
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // K0 | K1 | V0 | V1 | sidk[2][64]   (one array: keeps LDS-DMA waits exact)
   constexpr int TB = BKV * D * 2;
@@ -89,6 +91,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
   // same XCD and shares its K/V (or Q/dO) through that L2 instead of re-fetching them over the fabric (B*H is a multiple of 8 in practice).
   int bh, tile_x;
   attn_block_to_work(blockIdx.x, a.B * a.H, bh, tile_x);
+  if (CAUSAL) tile_x = gridDim.x / (a.B * a.H) - 1 - tile_x;   // heavy (late) query blocks first
   const int b = bh / a.H, h = bh % a.H;
   const int qi = tile_x * BQ + wave * 32 + l31;
   const bool q_ok = qi < a.L;
@@ -124,6 +127,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
   bool doc_pure = false;   // the whole key span of this query block is the block's own document: no tile of the walk needs the element mask (nor its range entry)
   if (HAS_SID) { const DocSpan sp = doc_tile_span(a.doc_ranges, b, a.L, tile_x, nkv); t_begin = sp.t_begin; t_end = sp.t_end; blk_id = sp.blk_id;
                  doc_pure = sp.pure && sp.lo % BKV == 0 && (sp.hi % BKV == 0 || sp.hi == a.L); }   // (key tiles are walked from multiples of BKV: the span must start and end on one)
+  if (CAUSAL) t_end = min(t_end, (tile_x + 1) * (BQ / BKV));
   if (t_begin < t_end) {
     Stg::issue(kbase, a.k_stride, t_begin * BKV, a.L, smem + (t_begin & 1) * TB, wave, lane);
     Stg::issue(vbase, a.v_stride, t_begin * BKV, a.L, smem + (2 + (t_begin & 1)) * TB, wave, lane);
@@ -181,7 +185,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
         }
       }
     }
-    if (id_test || kv0 + BKV > a.L) {
+    const bool diag = CAUSAL && kv0 + BKV - 1 > tile_x * BQ;   // block-uniform: some key of the tile lies past some query of the block
+    if (id_test || kv0 + BKV > a.L || diag) {
       long sid_q = 0;
       if (IDS && id_test) sid_q = q_ok ? a.sample_ids[rowbase + qi] : -1;
 #pragma unroll
@@ -191,6 +196,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
           const int kl = f * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
           bool ok = kv0 + kl < a.L;
           if (IDS) ok = ok && (!id_test || attn_pair_ok(sid_q, sidk[kl]));
+          if (CAUSAL) ok = ok && kv0 + kl <= qi;   // (before the running maximum: a masked score contributes exp2(-inf) = 0 exactly)
           if (!ok) sT[f][r] = -INFINITY;
         }
     }
@@ -283,7 +289,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
 // ------------------------------------------------------------------------------------------------
 // backward, dQ: block owns 128 queries, walks key tiles.  dQ^T = K^T dS^T (lane owns a query column).
 // ------------------------------------------------------------------------------------------------
-template <int D, bool HAS_SID, bool USE_TR>
+template <int D, bool HAS_SID, bool USE_TR, bool CAUSAL = false>   // CAUSAL: the forward's walk (tiles below the diagonal, late query blocks first)
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // K0 | K1 | V0 | V1 | sidk[2][64]
   constexpr int TB = BKV * D * 2;
@@ -295,6 +301,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs a) {
   // same XCD and shares its K/V (or Q/dO) through that L2 instead of re-fetching them over the fabric (B*H is a multiple of 8 in practice).
   int bh, tile_x;
   attn_block_to_work(blockIdx.x, a.B * a.H, bh, tile_x);
+  if (CAUSAL) tile_x = gridDim.x / (a.B * a.H) - 1 - tile_x;
   const int b = bh / a.H, h = bh % a.H;
   const int qi = tile_x * BQ + wave * 32 + l31;
   const bool q_ok = qi < a.L;
@@ -350,6 +357,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs a) {
   bool doc_pure = false;   // (see the forward kernel)
   if (HAS_SID) { const DocSpan sp = doc_tile_span(a.doc_ranges, b, a.L, tile_x, nkv); t_begin = sp.t_begin; t_end = sp.t_end; blk_id = sp.blk_id;
                  doc_pure = sp.pure && sp.lo % BKV == 0 && (sp.hi % BKV == 0 || sp.hi == a.L); }
+  if (CAUSAL) t_end = min(t_end, (tile_x + 1) * (BQ / BKV));
   if (t_begin < t_end) {
     Stg::issue(kbase, a.k_stride, t_begin * BKV, a.L, smem + (t_begin & 1) * TB, wave, lane);
     Stg::issue(vbase, a.v_stride, t_begin * BKV, a.L, smem + (2 + (t_begin & 1)) * TB, wave, lane);
@@ -373,6 +381,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs a) {
       Stg::issue(kbase, a.k_stride, kv0 + BKV, a.L, smem + (st ^ 1) * TB, wave, lane);
       Stg::issue(vbase, a.v_stride, kv0 + BKV, a.L, smem + (2 + (st ^ 1)) * TB, wave, lane);
     }
+    const bool diag = CAUSAL && kv0 + BKV - 1 > tile_x * BQ;   // block-uniform (see the forward)
     float ds[2][16];
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
@@ -387,7 +396,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs a) {
       }
       // per-element masks only for document masks and the ragged last tile: full tiles have no out-of-range keys, and an out-of-range
       // QUERY has lse = +inf (p = 0) and zero operands
-      if (id_test || kv0 + BKV > a.L) {
+      if (id_test || kv0 + BKV > a.L || diag) {
         long sid_q = 0;
         if (HAS_SID && id_test) sid_q = q_ok ? a.sample_ids[rowbase + qi] : -1;
 #pragma unroll
@@ -395,6 +404,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs a) {
           const int kl = f * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
           bool ok = (kv0 + kl < a.L) && q_ok;
           if (HAS_SID) ok = ok && (!id_test || attn_pair_ok(sid_q, sidk[kl]));
+          if (CAUSAL) ok = ok && kv0 + kl <= qi;
           const float pv = ok ? __builtin_amdgcn_exp2f(sT[r] * c - lse_q) : 0.f;
           ds[f][r] = pv * (dpT[r] - delta_q);
         }
@@ -442,7 +452,9 @@ constexpr int BQT = 64;
 // MODE: 1 = dK only, 2 = dV only, 3 = both.  At D = 128 both accumulators (128 registers) plus K/V operands (64) do not fit two
 // waves per SIMD, so the backward launches the dK and dV halves separately (each recomputes S; 40 instead of 32 MFMAs per
 // 32-query step, but twice the occupancy).
-template <int D, bool HAS_SID, bool USE_TR, int MODE, int WAVES>
+// CAUSAL: a key block walks only the query tiles at or below its diagonal (from t = 2 tile_x: every query there sees some key of the block), with the
+// per-element test on the two tiles that cross it.  The early key blocks have the longest walks and are dispatched first anyway (tile-major order).
+template <int D, bool HAS_SID, bool USE_TR, int MODE, int WAVES, bool CAUSAL = false>
 __global__ __launch_bounds__(256, WAVES) void attn_bwd_dkv_kernel(AttnArgs a) {
   constexpr bool DO_DK = (MODE & 1) != 0, DO_DV = (MODE & 2) != 0;
   extern __shared__ __attribute__((aligned(16))) char smem[];  // Q0 | Q1 | dO0 | dO1 | lse[2][64] | delta[2][64] | sidq[2][64]
@@ -495,6 +507,7 @@ __global__ __launch_bounds__(256, WAVES) void attn_bwd_dkv_kernel(AttnArgs a) {
     if (sp.pure && a.doc_pure_split) return;   // block-uniform: this key block belongs to attn_bwd_dkv_ws_kernel (launched beside this one)
     t_begin = sp.t_begin; t_end = sp.t_end; blk_id = sp.blk_id;
   }
+  if (CAUSAL) t_begin = tile_x * (128 / BQT);
   if (t_begin < t_end) {
     Stg::issue(qbase, a.q_stride, t_begin * BQT, a.L, smem + (t_begin & 1) * TB, wave, lane);
     Stg::issue(dobase, a.do_stride, t_begin * BQT, a.L, smem + (2 + (t_begin & 1)) * TB, wave, lane);
@@ -537,7 +550,7 @@ __global__ __launch_bounds__(256, WAVES) void attn_bwd_dkv_kernel(AttnArgs a) {
       }
       __builtin_amdgcn_sched_barrier(0);
       float p[16], ds[16];
-      auto softmax_bwd = [&](auto IDT) {
+      auto softmax_bwd = [&](auto IDT, auto CDT) {
 #pragma unroll
         for (int rg = 0; rg < 4; ++rg) {
           const int ql0 = qs * 32 + 8 * rg + 4 * hi;
@@ -549,12 +562,15 @@ __global__ __launch_bounds__(256, WAVES) void attn_bwd_dkv_kernel(AttnArgs a) {
             const int r = rg * 4 + e;
             bool ok = k_ok && (q0 + ql0 + e < a.L);
             if (decltype(IDT)::value) ok = ok && attn_pair_ok(sidq[ql0 + e], sid_k);
+            if (decltype(CDT)::value) ok = ok && ki <= q0 + ql0 + e;
             p[r] = ok ? __builtin_amdgcn_exp2f(s[r] * c - lv[e]) : 0.f;
             ds[r] = p[r] * (dp[r] - dv[e]);
           }
         }
       };
-      if (HAS_SID && id_test) softmax_bwd(std::true_type{}); else softmax_bwd(std::false_type{});
+      if (HAS_SID && id_test) softmax_bwd(std::true_type{}, std::false_type{});
+      else if (CAUSAL && q0 < tile_x * 128 + 127) softmax_bwd(std::false_type{}, std::true_type{});   // block-uniform: the tile crosses the diagonal
+      else softmax_bwd(std::false_type{}, std::false_type{});
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int c2 = 0; c2 < 2; ++c2) {
@@ -594,16 +610,17 @@ template <typename KernT>
 void set_lds(KernT kern, size_t bytes) {
   (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
-template <int D, bool SID, bool TR>
+template <int D, bool SID, bool TR, bool CAUSAL = false>
 void launch_fwd(const AttnArgs& a, hipStream_t s) {
   dim3 grid(((a.L + BQ - 1) / BQ) * a.H * a.B);
   const size_t lds = 4 * BKV * D * 2 + 2 * BKV * sizeof(long);
-  auto kern = attn_fwd_kernel<D, SID, TR>;
+  auto kern = attn_fwd_kernel<D, SID, TR, 0, CAUSAL>;
   static bool once = false;
   if (!once) { set_lds(kern, lds); once = true; }
   // head dim 128, no mask, L % 256 == 0, q pre-scaled (the headline path): the one-wave-per-SIMD, 64-queries-per-wave kernel of attention_fwd64.hip
-  if (D == 128 && !SID && TR && a.q_prescaled && udm_launch_attn_fwd64(&a, s)) return;
-  if (D == 128 && !SID && TR) {   // UDM_ATTN_ABL=1|2: timing-only ablations of the forward kernel (scripts/bench_attn.py)
+  // (causal calls stay with this file's kernel: the generated program has no causal form)
+  if (D == 128 && !SID && TR && a.q_prescaled && !a.causal && udm_launch_attn_fwd64(&a, s)) return;
+  if (D == 128 && !SID && TR && !a.causal) {   // UDM_ATTN_ABL=1|2: timing-only ablations of the forward kernel (scripts/bench_attn.py)
     static const int abl = [] { const char* e = getenv("UDM_ATTN_ABL"); return e ? atoi(e) : 0; }();
     if (abl == 1) { auto k1 = attn_fwd_kernel<128, false, true, 1>; set_lds(k1, lds); hipLaunchKernelGGL(k1, grid, dim3(256), lds, s, a); return; }
     if (abl == 2) { auto k2 = attn_fwd_kernel<128, false, true, 2>; set_lds(k2, lds); hipLaunchKernelGGL(k2, grid, dim3(256), lds, s, a); return; }
@@ -612,23 +629,25 @@ void launch_fwd(const AttnArgs& a, hipStream_t s) {
   }
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
 }
-template <int D, bool SID, bool TR>
+template <int D, bool SID, bool TR, bool CAUSAL = false>
 void launch_bwd(const AttnArgs& a, hipStream_t s) {
   dim3 gq(((a.L + BQ - 1) / BQ) * a.H * a.B), gk(((a.L + 127) / 128) * a.H * a.B);
   const size_t lds_q = 4 * BKV * D * 2 + 2 * BKV * sizeof(long);
   const size_t lds_k = 4 * BQT * D * 2 + 4 * BQT * sizeof(float) + 2 * BQT * sizeof(long);
-  auto kq = attn_bwd_dq_kernel<D, SID, TR>;
+  auto kq = attn_bwd_dq_kernel<D, SID, TR, CAUSAL>;
   // D = 128: both accumulators (128 registers) plus K/V operands (64) only fit one wave per SIMD in the single-role kernel, which is then
   // bound by that one wave's instruction issue (0.39 ms at B8 H16 L1280).  Without a document mask the wave-specialised kernel of
-  // attention_dkv_ws.hip (two waves per SIMD with different roles, 0.27 ms) is used instead.
+  // attention_dkv_ws.hip (two waves per SIMD with different roles, 0.27 ms) is used instead.  Causal calls keep the single-role kernel (0.30 ms at that
+  // shape); dK and dV as two launches at two waves per SIMD measured the same (0.13 + 0.17 ms) and were not kept.
   constexpr int W = (D == 128) ? 1 : 2;
-  auto kk = attn_bwd_dkv_kernel<D, SID, TR, 3, W>;
+  auto kk = attn_bwd_dkv_kernel<D, SID, TR, 3, W, CAUSAL>;
   static bool once = false;
   if (!once) { set_lds(kq, lds_q); set_lds(kk, lds_k); once = true; }
   // D = 128, no mask, L % 256 == 0, q pre-scaled: both passes as generated one-wave-per-SIMD programs (round 6: attention_dq64.hip, attention_dkv64.hip)
-  if (!(D == 128 && !SID && TR && a.q_prescaled && udm_launch_attn_bwd_dq64(&a, s))) hipLaunchKernelGGL(kq, gq, dim3(256), lds_q, s, a);
-  if (D == 128 && !SID && TR && a.q_prescaled && udm_launch_attn_bwd_dkv64(&a, s)) return;   // the one-wave-per-SIMD, 64-keys-per-wave kernel (round 6)
-  if (D == 128 && !SID && TR && g_dkv_ws) udm_launch_attn_bwd_dkv_ws(&a, s);
+  // (causal calls take neither generated program nor the wave-specialised dK/dV kernel: none of them has a causal form)
+  if (!(D == 128 && !SID && TR && a.q_prescaled && !a.causal && udm_launch_attn_bwd_dq64(&a, s))) hipLaunchKernelGGL(kq, gq, dim3(256), lds_q, s, a);
+  if (D == 128 && !SID && TR && a.q_prescaled && !a.causal && udm_launch_attn_bwd_dkv64(&a, s)) return;   // the one-wave-per-SIMD, 64-keys-per-wave kernel (round 6)
+  if (D == 128 && !SID && TR && g_dkv_ws && !a.causal) udm_launch_attn_bwd_dkv_ws(&a, s);
   else if (D == 128 && SID && TR && g_dkv_ws && a.doc_ranges) {
     // packed documents: key blocks that lie inside one document and whose query span is exactly that document go to the wave-specialised
     // kernel (no id test needed anywhere); the blocks at document boundaries / with padding stay with the single-role kernel
@@ -644,6 +663,13 @@ void launch_bwd(const AttnArgs& a, hipStream_t s) {
     if (D == 128) { if (sid) { if (tr) FN<128, true, true>(a, s); else FN<128, true, false>(a, s); } else { if (tr) FN<128, false, true>(a, s); else FN<128, false, false>(a, s); } } \
     else if (D == 64) { if (sid) { if (tr) FN<64, true, true>(a, s); else FN<64, true, false>(a, s); } else { if (tr) FN<64, false, true>(a, s); else FN<64, false, false>(a, s); } } \
     else { if (sid) { if (tr) FN<32, true, true>(a, s); else FN<32, true, false>(a, s); } else { if (tr) FN<32, false, true>(a, s); else FN<32, false, false>(a, s); } } \
+  } while (0)
+// causal: never with sample ids (rejected at the entry points)
+#define ATTN_DISPATCH_CAUSAL(FN, a, D, tr, s)                                                     \
+  do {                                                                                            \
+    if (D == 128) { if (tr) FN<128, false, true, true>(a, s); else FN<128, false, false, true>(a, s); } \
+    else if (D == 64) { if (tr) FN<64, false, true, true>(a, s); else FN<64, false, false, true>(a, s); } \
+    else { if (tr) FN<32, false, true, true>(a, s); else FN<32, false, false, true>(a, s); }          \
   } while (0)
 
 int g_use_tr = 1;
@@ -673,7 +699,8 @@ extern "C" int udm_attention_doc_ranges(const int64_t* sample_ids, int64_t B, in
 extern "C" int udm_attention_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const int64_t* sample_ids, const int32_t* doc_ranges, int64_t B, int64_t H, int64_t L,
                                  int64_t D, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t flags, hipStream_t stream) {
   UDM_CHECK_ARG(q && k && v && o && lse, "udm_attention_fwd: null pointer");
-  UDM_CHECK_ARG((flags & ~(int64_t)UDM_ATTN_Q_PRESCALED) == 0, "udm_attention_fwd: unknown flags %ld", (long)flags);
+  UDM_CHECK_ARG((flags & ~(int64_t)(UDM_ATTN_Q_PRESCALED | UDM_ATTN_CAUSAL)) == 0, "udm_attention_fwd: unknown flags %ld", (long)flags);
+  UDM_CHECK_ARG(!(flags & UDM_ATTN_CAUSAL) || (!sample_ids && !doc_ranges), "udm_attention_fwd: UDM_ATTN_CAUSAL with sample_ids / doc_ranges");
   if (int rc = check_common("udm_attention_fwd", B, H, L, D, q_stride, k_stride, v_stride)) return rc;
   UDM_CHECK_ARG(o_stride % 4 == 0, "udm_attention_fwd: o_stride must be a multiple of 4");
   UDM_CHECK_ARG(sample_ids || !doc_ranges, "udm_attention_fwd: doc_ranges without sample_ids");
@@ -686,7 +713,9 @@ extern "C" int udm_attention_fwd(const void* q, const void* k, const void* v, vo
   a.scale = 1.0f / sqrtf((float)D);
   a.scale_log2 = a.scale * 1.4426950408889634f;
   if (flags & UDM_ATTN_Q_PRESCALED) { a.q_prescaled = 1; a.scale_log2 = 1.0f; }   // q already carries log2(e) / sqrt(D): the scores ARE the base-2 exponents
-  ATTN_DISPATCH(launch_fwd, a, D, sample_ids != nullptr, g_use_tr, stream);
+  a.causal = (flags & UDM_ATTN_CAUSAL) ? 1 : 0;
+  if (a.causal) ATTN_DISPATCH_CAUSAL(launch_fwd, a, D, g_use_tr, stream);
+  else ATTN_DISPATCH(launch_fwd, a, D, sample_ids != nullptr, g_use_tr, stream);
   UDM_CHECK_LAUNCH("udm_attention_fwd");
   return 0;
 }
@@ -696,7 +725,8 @@ extern "C" int udm_attention_bwd(const void* q, const void* k, const void* v, co
                                  int64_t v_stride, int64_t o_stride, int64_t do_stride, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride,
                                  int64_t flags, hipStream_t stream) {
   UDM_CHECK_ARG(q && k && v && o && dout && lse && delta && dq && dk && dv, "udm_attention_bwd: null pointer");
-  UDM_CHECK_ARG((flags & ~(int64_t)UDM_ATTN_Q_PRESCALED) == 0, "udm_attention_bwd: unknown flags %ld", (long)flags);
+  UDM_CHECK_ARG((flags & ~(int64_t)(UDM_ATTN_Q_PRESCALED | UDM_ATTN_CAUSAL)) == 0, "udm_attention_bwd: unknown flags %ld", (long)flags);
+  UDM_CHECK_ARG(!(flags & UDM_ATTN_CAUSAL) || (!sample_ids && !doc_ranges), "udm_attention_bwd: UDM_ATTN_CAUSAL with sample_ids / doc_ranges");
   if (int rc = check_common("udm_attention_bwd", B, H, L, D, q_stride, k_stride, v_stride)) return rc;
   UDM_CHECK_ARG(o_stride % 8 == 0 && do_stride % 8 == 0 && dq_stride % 4 == 0 && dk_stride % 4 == 0 && dv_stride % 4 == 0, "udm_attention_bwd: bad strides");
   UDM_CHECK_ARG(sample_ids || !doc_ranges, "udm_attention_bwd: doc_ranges without sample_ids");
@@ -715,8 +745,10 @@ extern "C" int udm_attention_bwd(const void* q, const void* k, const void* v, co
   if (flags & UDM_ATTN_Q_PRESCALED) { a.q_prescaled = 1; a.scale_log2 = 1.0f; a.scale = 0.6931471805599453f; }
   static const bool env_once = [] { if (const char* e = getenv("UDM_DKV_WS")) g_dkv_ws = atoi(e); return true; }();
   (void)env_once;
+  a.causal = (flags & UDM_ATTN_CAUSAL) ? 1 : 0;
   // (delta is computed and stored by the dQ kernel, which launch_bwd runs first)
-  ATTN_DISPATCH(launch_bwd, a, D, sample_ids != nullptr, g_use_tr, stream);
+  if (a.causal) ATTN_DISPATCH_CAUSAL(launch_bwd, a, D, g_use_tr, stream);
+  else ATTN_DISPATCH(launch_bwd, a, D, sample_ids != nullptr, g_use_tr, stream);
   UDM_CHECK_LAUNCH("udm_attention_bwd");
   return 0;
 }

@@ -74,10 +74,14 @@ struct AttnArgs {
   int B, H, L;
   float scale_log2;     // log2(e) / sqrt(D)
   float scale;          // 1 / sqrt(D)
+  int causal;           // UDM_ATTN_CAUSAL: query i sees keys j <= i (8-wave kernels only).  Sits in the alignment hole in front of `timeline`: no field
+                        // moves and the block keeps its size, so every kernarg layout - attn_fwd64_kernel's scalars behind it included - is unchanged
   unsigned long long* timeline;   // diagnostics (experiments library): cycle stamps of a few blocks, or null
   int exp;                        // experiment bits (udm_exp_flags), 0 in production
   int q_prescaled;                // UDM_ATTN_Q_PRESCALED: q carries log2(e) / sqrt(D) (scale_log2 = 1; the backward's `scale` = ln 2)
 };
+
+static_assert(sizeof(AttnArgs) == 208 && offsetof(AttnArgs, causal) == 188 && offsetof(AttnArgs, timeline) == 192, "AttnArgs layout (kernarg segments)");
 
 // Attention mask codes.  `sample_ids` holds one int64 per position:  bits 0-31 = sample id (signed; < 0 = padding), bits 32-39 = the KEY classes this
 // position belongs to, bits 40-47 = the key classes this position may see as a QUERY.  A query sees a key iff both sample ids are equal and >= 0 and

@@ -60,7 +60,7 @@ bool udm_launch_attn_bwd_dq64(const void* args, hipStream_t stream) {
   const AttnArgs& a = *reinterpret_cast<const AttnArgs*>(args);
   if (g_dq64 < 0) { const char* e = getenv("UDM_ATTN_DQ64"); g_dq64 = e ? atoi(e) : 1; }
   // whole 256-query blocks of at least two per (batch, head) (the magic divisions), the XCD-sequential block order (B H a multiple of 8), 16-byte row segments
-  if (!g_dq64 || !a.q_prescaled || a.H < 2 || a.L % 256 != 0 || a.L < 512 || (a.B * a.H) % 8 != 0) return false;
+  if (!g_dq64 || !a.q_prescaled || a.causal || a.H < 2 || a.L % 256 != 0 || a.L < 512 || (a.B * a.H) % 8 != 0) return false;
   if (a.out_stride % 8 != 0 || a.o_stride % 8 != 0 || a.q_stride % 8 != 0 || a.do_stride % 8 != 0) return false;
   const long lim = 1L << 31;     // 32-bit lane offsets: 64 rows of any operand, and the plane offset
   if (a.q_stride * 2 * 256 >= lim || a.do_stride * 2 * 256 >= lim || a.o_stride * 2 * 256 >= lim || a.k_stride * 2 * 64 >= lim || a.v_stride * 2 * 64 >= lim || a.out_stride * 2 * 256 >= lim) return false;

@@ -106,8 +106,10 @@ class Diffusion:
         else:
             self.text_vocab_size = self.vocab_size
         self.parameterization = cfg_get(config, "parameterization", "subs")
-        if self.parameterization != "subs":
-            raise NotImplementedError(f"unidisc_amd: parameterization={self.parameterization}; only SUBS is on the denoising hot path")
+        if self.parameterization not in ("subs", "ar"):
+            raise NotImplementedError(f"unidisc_amd: parameterization={self.parameterization}; SUBS and the AR baseline (ar) are implemented")
+        if self.parameterization == "ar":
+            self._check_ar(config, m, tr)
         if cfg_get(config, "backbone", "dit") != "dit":
             raise NotImplementedError("unidisc_amd: only backbone=dit is implemented")
         self.static_txt_sl = slice(None, cfg_get(m, "txt_length"))
@@ -123,6 +125,22 @@ class Diffusion:
         self.sampling_eps = cfg_get(tr, "sampling_eps", 1e-3)
         self.time_conditioning = cfg_get(config, "time_conditioning", False)
         self.neg_infinity = -1000000.0  # model_setup.py:269
+
+    @staticmethod
+    def _check_ar(config, m, tr):
+        """The AR baseline as configs/experiments/ar.yaml trains it (parameterization=ar, trainer.ar_shift, model.full_attention=false): next-token
+        cross-entropy, no time conditioning, x_t = x_0.  The AR variants of the trainer that change the batch or the objective are not built."""
+        if cfg_get(config, "time_conditioning", False) or cfg_get(m, "force_time_conditioning", False):
+            raise NotImplementedError("unidisc_amd: parameterization=ar with time_conditioning - the AR baseline has no sigma (model.py:840-918)")
+        if not cfg_get(tr, "ar_shift", False):
+            raise NotImplementedError("unidisc_amd: parameterization=ar without trainer.ar_shift (unshifted AR training) is not built")
+        for flag, why in (("rand_ar_modality_dropout", "masking a sample's first modality (model.py:906-913)"),
+                          ("ar_inpainting", "the doubled inpainting sequence (model.py:884-900)"),
+                          ("rand_flip_ar_prob", "flipping the modality order of a batch (model.py:357-380)"),
+                          ("ar_llm_loss", "the extra LLM loss term (model.py:1076-1136)"),
+                          ("use_orig_unidisc_dit", "the original UniDisc DiT head (model.py:757)")):
+            if cfg_get(tr, flag, None) not in (None, False):
+                raise NotImplementedError(f"unidisc_amd: parameterization=ar with trainer.{flag} - {why} - is not built")
 
     rng_device = None  # set to "cpu" to draw t / masks from the CPU generator (bit-reproducible across devices)
     _generic_qxt = False   # tests: route q_xt through the tensor statements even where the fused launch applies
@@ -491,8 +509,12 @@ class Diffusion:
 
     def forward(self, x, sigma, batch=None, forward_attention_mask=None, return_additional_loss=False, x_img_emb=None, disable_ar_shift=False,
                 continuous_mode=False, joint_ar_nar_mask=None, return_logits=False, block_mask=None, update_cache_slice=None, **kwargs):
-        """Returns log score (model.py:674-795): SUBS log-probs [B,L,V] (bf16), or raw logits when ``return_logits``."""
+        """Returns log score (model.py:674-795): SUBS log-probs [B,L,V] (bf16), or raw logits when ``return_logits``.  AR baseline: next-token log-probs
+        [B, L-1, V] (trainer.ar_shift), or [B, L, V] with ``disable_ar_shift``."""
         sigma = self._process_sigma(sigma)
+        if self.parameterization == "ar":
+            return self._ar_forward(x, batch, return_logits, disable_ar_shift, block_mask=block_mask, update_cache_slice=update_cache_slice,
+                                    continuous_mode=continuous_mode, x_img_emb=x_img_emb, **kwargs)
         logits = self.backbone(x, sigma, continuous_mode=continuous_mode, x_img_emb=x_img_emb, block_mask=block_mask,
                                update_cache_slice=update_cache_slice, **kwargs)
         if return_logits:
@@ -501,6 +523,31 @@ class Diffusion:
             raise RuntimeError("unidisc_amd.Diffusion.forward: full SUBS log-probs are an inference product (no autograd); "
                                "training uses compute_loss (fused path) — wrap sampler calls in torch.no_grad()")
         return self._subs_parameterization(logits, xt=x, batch=batch, **kwargs)
+
+    def _ar_forward(self, x, batch, return_logits, disable_ar_shift, **kwargs):
+        """model.py:717-781, AR branch: logits[:, :-1] (ar_shift), the [MASK] column excluded and - under force_argmax_valid_indices, when the modality map
+        is one longer than the shifted logits - the other modality's ids than the TARGET token's, then log-softmax.  Excluded ids read -1e6 (the SUBS
+        kernel's neg_infinity; the reference writes -1e6 / finfo.min before its log-softmax: their probability is 0 either way).  Inference product."""
+        logits = self.backbone(x, None, **kwargs)
+        shift = bool(cfg_get(cfg_get(self.config, "trainer"), "ar_shift", False)) and not disable_ar_shift
+        if shift:
+            logits = logits[:, :-1]
+        if return_logits:
+            return logits
+        if logits.requires_grad:
+            raise RuntimeError("unidisc_amd.Diffusion.forward: full AR log-probs are an inference product (no autograd); training uses compute_loss")
+        B, Lo, V = logits.shape
+        mod = kwargs.get("modality") if batch is None else batch.get("modality")
+        if self._restrict() and mod is None:
+            mod = torch.zeros((B, x.shape[1]), dtype=torch.int64, device=x.device)
+            mod[:, self.static_img_sl] = 1
+        mod = mod[:, 1:] if (self._restrict() and mod is not None and mod.shape[1] == Lo + 1) else None
+        xt = torch.full((B, Lo), self.mask_index, dtype=torch.int64, device=x.device)   # every row "masked": the SUBS log-prob of such a row is the AR one
+        flat = torch.zeros((B * Lo, (V + 7) // 8 * 8), dtype=torch.bfloat16, device=logits.device)
+        flat[:, :V] = logits.reshape(B * Lo, V)
+        out = K.subs_logprobs(flat, xt.reshape(-1), mod.reshape(-1).contiguous() if mod is not None else None, V, self.text_vocab_size, self.mask_index,
+                              mod is not None, out_dtype=torch.bfloat16)
+        return out.view(B, Lo, V)
 
     # ---- sampler inner loop (SURVEY §8f N1): the `ddpm_cache` predictor (config.sampling.predictor default) with classifier-free guidance
     # (config.eval.cfg, one pass over [x ; x_uncond] or two with config.eval.split_cfg_batches); no attention caching
@@ -767,6 +814,9 @@ class Diffusion:
         (x0 / x0_unmask conditioning kept fixed), timesteps = linspace(1, eps, steps + 1), one fused update per step with the logits
         cache reused while nothing changes, final arg-max of the log-probs (`noise_removal`).  Returns token ids [B, L]
         (and the number of backbone evaluations).  `noise`: optional list of uniforms [B, L, V] per step (replay of a recorded run)."""
+        if self.parameterization == "ar":
+            raise NotImplementedError("unidisc_amd.Diffusion.sample: the AR sampler (model_eval.py:2736, KV-cached next-token decoding) is not built - "
+                                      "parameterization=ar trains here (compute_loss) and gives log-probs (forward)")
         assert (x0 is None) == (x0_unmask is None)
         sampling = cfg_get(self.config, "sampling", None)
         if num_steps is None:
@@ -869,6 +919,8 @@ class Diffusion:
 
     # ---- model.py:797-1173, SUBS / continuous-time branch
     def compute_loss(self, batch, prefix, batch_idx=-1):
+        if self.parameterization == "ar":
+            return self._compute_loss_ar(batch, prefix)
         cfg, tr = self.config, cfg_get(self.config, "trainer")
         kwargs = self.get_cond_dict(batch)
         modality_mask = batch.get("modality_mask", None)
@@ -952,6 +1004,49 @@ class Diffusion:
         losses = Loss(loss=loss_dict["loss"], img_loss=loss_dict.get("img_loss", 0), txt_loss=loss_dict.get("txt_loss", 0), nlls=std_nlls,
                       txt_nlls=loss_dict.get("std_txt_loss", 0), img_nlls=loss_dict.get("std_img_loss", 0), token_mask=attention_mask,
                       modality_mask=modality_mask, extra_losses=loss_dict.get("extra_losses", None))
+        return self._finish_loss(losses, prefix)
+
+    def _compute_loss_ar(self, batch, prefix):
+        """model.py:840-1073 for parameterization=ar with trainer.ar_shift: x_t = x_0 (no t draw, no corruption), sigma = None, next-token log-probs from the
+        causal backbone's shifted head (DIT.forward_logp(ar_shift=True): the fused SUBS cross-entropy with every row "masked"), weight 1, and the reference's
+        reductions over the SHIFTED attention mask / modality mask (masked mean, or the text / image-weighted form) in one K.diffusion_loss launch."""
+        cfg, tr = self.config, cfg_get(self.config, "trainer")
+        kwargs = self.get_cond_dict(batch)
+        if "attention_mask" in kwargs:
+            raise NotImplementedError("unidisc_amd: parameterization=ar with model.use_attention_mask - an attention mask beside is_causal is an SDPA error in the reference")
+        x0, attention_mask, modality_mask = batch["input_ids"], batch.get("attention_mask", None), batch.get("modality_mask", None)
+        if x0.shape[1] > cfg_get(cfg_get(cfg, "model"), "length"):
+            raise NotImplementedError("unidisc_amd: sequence sub-sampling (text8-crop) is not on the denoising hot path")
+        log_p_full = self.backbone.forward_logp(x0, x0, self._process_sigma(None), modality=kwargs.get("modality"), restrict_modality=self._restrict(),
+                                                ar_shift=True)
+        self._flush_checks()
+        log_p_theta = log_p_full[:, :-1]   # (the last column has no target: 0, zero gradient)
+        attention_mask = attention_mask[:, 1:]
+        if modality_mask is not None:
+            modality_mask = modality_mask[:, 1:]
+        self._last = dict(t=None, sigma=None, dsigma=None, xt=x0, move_indices=None, log_p_theta=log_p_theta, modality=kwargs.get("modality"))
+        ones = torch.ones(x0.shape[0], dtype=torch.float32, device=x0.device)   # std_weighting = 1 (model.py:972-975), no soft-min SNR
+        weighted = cfg_get(tr, "text_loss_weight", None) is not None and cfg_get(tr, "img_loss_weight", None) is not None
+        use_mm = (cfg_get(tr, "multimodal_batches", False) or weighted) and modality_mask is not None
+        if weighted and modality_mask is None:
+            raise ValueError("unidisc_amd: trainer.text_loss_weight / img_loss_weight need batches with a modality map")
+        std_nlls, coef, sc = K.diffusion_loss(
+            log_p_theta.detach().float().contiguous(), ones, ones, attention_mask.contiguous(), modality_mask.contiguous() if use_mm else None, weighted=weighted,
+            full_mask=bool(cfg_get(tr, "force_full_attention_mask_loss_only", False)),
+            text_w=float(cfg_get(tr, "text_loss_weight", None)) if weighted else 1.0,
+            img_w=float(cfg_get(tr, "img_loss_weight", None)) if weighted else 1.0, ratio=cfg_get(tr, "set_max_txt_loss_ratio", None) if weighted else None)
+        loss = _LinearLoss.apply(log_p_theta, coef, sc[0])
+        extra = dict()
+        if use_mm:
+            extra["trainer/img_frac"], extra["trainer/txt_frac"], extra["trainer/attention_mask_valid_frac"] = sc[4], sc[3], sc[5]
+        sep = cfg_get(tr, "log_seperate_modal_losses", False)
+        losses = Loss(loss=loss, img_loss=sc[2] if weighted else 0, txt_loss=sc[1] if weighted else 0, nlls=std_nlls,
+                      txt_nlls=std_nlls * modality_mask[..., 0] if sep else 0, img_nlls=std_nlls * modality_mask[..., 1] if sep else 0,
+                      token_mask=attention_mask, modality_mask=modality_mask, extra_losses=extra)
+        return self._finish_loss(losses, prefix)
+
+    def _finish_loss(self, losses, prefix):
+        tr = cfg_get(self.config, "trainer")
         if cfg_get(tr, "disable_torchmetrics", False):
             raise NotImplementedError("Torchmetrics disabled")
         if prefix == "train":

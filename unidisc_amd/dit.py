@@ -146,6 +146,28 @@ class ModalityMask:
         self.txt_drop, self.img_drop, self.txt_length = txt_drop.reshape(-1).bool(), img_drop.reshape(-1).bool(), int(txt_length)
 
 
+def ar_head_operands(x0, modality, mask_index):
+    """The AR baseline's shifted head (model.py:717-781, :935-967 with trainer.ar_shift) as operands of the fused SUBS cross-entropy, per flat row:
+      - "xt": mask_index on every row that has a target - the SUBS log-prob of a [MASK] row IS the AR log-prob (log-softmax with the [MASK] column, and
+        under restrict_modality the other modality's ids, excluded) - and a non-mask id on the last position of each sequence, which has no target: its
+        log p is 0 with a zero gradient, and the compacted head leaves it out like any unmasked row;
+      - the target x0[:, r + 1] (on the last position: that same non-mask id, so that its one-hot log-prob is exactly 0);
+      - the TARGET's modality, modality[:, r + 1] (model.py:760-765 `(modality == k)[..., 1:]`): the per-modality head splits its rows by it, so the row
+        in front of the first image token (row txt_len - 1) goes to the image head.
+    x0, modality: int [B, L] (modality may be None).  Returns three flat int64 tensors [B L] (the third None without modality)."""
+    B, L = x0.shape
+    x0 = x0.to(torch.int64)
+    none = 1 if mask_index == 0 else 0
+    ce_ids = torch.full((B, L), mask_index, dtype=torch.int64, device=x0.device)
+    ce_ids[:, -1] = none
+    tgt = torch.cat([x0[:, 1:], torch.full((B, 1), none, dtype=torch.int64, device=x0.device)], 1)
+    mod = None
+    if modality is not None:
+        modality = modality.to(torch.int64)
+        mod = torch.cat([modality[:, 1:], modality[:, -1:]], 1).contiguous().view(-1)
+    return ce_ids.view(-1), tgt.contiguous().view(-1), mod
+
+
 class _Lin:
     """bf16 shadows of one nn.Linear weight: w16 [out(p), in] for forward, w16t [in, out(p)] for dgrad."""
 
@@ -214,8 +236,18 @@ class DIT(nn.Module, _HubMixin):
                           ("use_flex_attention_cache", "inference modality KV cache")):
             if cfg_get(m, flag, False):
                 raise NotImplementedError(f"unidisc_amd.DIT: model.{flag} ({why}) is outside the denoising hot path (SURVEY.md §8)")
-        if not cfg_get(m, "full_attention", True):
-            raise NotImplementedError("unidisc_amd.DIT: causal attention (model.full_attention=false) is not on the denoising hot path")
+        # model.full_attention=false (models/dit.py:1118, the AR baseline of configs/experiments/ar.yaml): every block attends causally (sdpa is_causal=True,
+        # :768 / :826 / :843) - the attention kernels' UDM_ATTN_CAUSAL form.  The reference never combines it with another mask: an attention_mask beside
+        # is_causal is an SDPA error, and the packed / flex-mask paths sit inside `parameterization != "ar"`.
+        self.causal = not cfg_get(m, "full_attention", True)
+        self._attn_mask_kw = dict(causal=True) if self.causal else {}   # (bidirectional blocks call the attention entry points exactly as before)
+        if self.causal:
+            if cfg_get(data, "require_sample_ids", False):
+                raise NotImplementedError("unidisc_amd.DIT: causal attention (model.full_attention=false) with data.require_sample_ids (packed documents) - "
+                                          "the reference has no causal document mask")
+            if cfg_get(m, "use_attention_mask", False):
+                raise NotImplementedError("unidisc_amd.DIT: causal attention (model.full_attention=false) with model.use_attention_mask - an attention mask "
+                                          "beside is_causal is an SDPA error in the reference")
         if cfg_get(tr, "image_mode", "discrete") == "continuous":
             raise NotImplementedError("unidisc_amd.DIT: continuous image mode is not on the denoising hot path")
         if cfg_get(m, "attn_dropout", None):
@@ -465,13 +497,15 @@ class DIT(nn.Module, _HubMixin):
                                       "transfusion path - are outside the denoising hot path)")
         return attention_mask
 
-    def forward_logp(self, xt, x0, sigma=None, modality=None, sample_ids=None, restrict_modality=False, block_mask=None, attention_mask=None):
+    def forward_logp(self, xt, x0, sigma=None, modality=None, sample_ids=None, restrict_modality=False, block_mask=None, attention_mask=None, ar_shift=False):
         """Fused training path: log p_theta(x0 | xt) per token [B, L] fp32 under the SUBS parameterisation
         (== gather(_subs_parameterization(logits, xt), x0), model.py:621-658 + :967) without materialising log-probs.
-        block_mask: a `ModalityMask` (modality attention dropout) or None.  attention_mask: the key-padding mask of `model.use_attention_mask` or None."""
+        block_mask: a `ModalityMask` (modality attention dropout) or None.  attention_mask: the key-padding mask of `model.use_attention_mask` or None.
+        ar_shift (the AR baseline, model.py:717-781 + :935-967; pass xt = x0): column r of the result is log p(x0[:, r+1] | x0[:, :r+1]) - the [MASK] id and,
+        with restrict_modality, the ids of the other modality than the TARGET's excluded - and the last column, which has no target, is 0 (zero gradient)."""
         params = self._ordered_params()
         inputs = dict(indices=xt, sigma=sigma, modality=modality, sample_ids=sample_ids, x0=x0, restrict=restrict_modality, save=self._needs_grad(params),
-                      block_mask=block_mask, key_mask=self._key_mask(attention_mask, xt))
+                      block_mask=block_mask, key_mask=self._key_mask(attention_mask, xt), ar_shift=bool(ar_shift))
         return _DitFn.apply(self, "logp", inputs, *params)
 
     @torch.no_grad()
@@ -618,8 +652,11 @@ class DIT(nn.Module, _HubMixin):
             del pos
         else:
             emb_mod = mod_flat
-        doc_ranges = K.attention_doc_ranges(sid) if sid is not None else None   # once per step, shared by every block's forward and backward
         bm = inp.get("block_mask")
+        if self.causal and (sid is not None or isinstance(bm, ModalityMask) or inp.get("key_mask") is not None):
+            raise NotImplementedError("unidisc_amd.DIT: causal attention (model.full_attention=false) with packed sample_ids, a ModalityMask or an attention mask - "
+                                      "the reference never combines is_causal with another mask")
+        doc_ranges = K.attention_doc_ranges(sid) if sid is not None else None   # once per step, shared by every block's forward and backward
         if isinstance(bm, ModalityMask) and sid is None:
             # modality attention dropout (model.py:863-878): an asymmetric per-sample mask, carried to the attention kernels as mask codes in
             # the sample-id slot (class bits: no tile skipping, every tile takes the per-element test)
@@ -645,9 +682,14 @@ class DIT(nn.Module, _HubMixin):
         # stream NOW and only read back right before the head, when the host has already queued every block of this forward -- the
         # device never waits for the host.
         plan_ids = inp.get("plan_ids")
+        ar = mode == "logp" and bool(inp.get("ar_shift", False))
+        if ar:   # the AR baseline's shifted head: row r predicts token r + 1 (ar_head_operands)
+            ar_mod = modality.reshape(B, L) if modality is not None else (self._static_modality(B, L, dev) if bool(inp.get("restrict", False)) else None)
+            ce_ids, ce_x0, ce_mod_ar = ar_head_operands(inp["x0"].reshape(B, L), ar_mod, self.mask_index)
         split_ok = (mode == "logp" and self.compact_head and self.split_head and bool(inp.get("restrict", False)) and mod_flat is not None and plan_ids is None
                     and 0 < self.text_vocab_size < self.vocab_size and self.head_chunk_rows <= 0)
-        head_plan = (self._plan_masked_rows(ids if plan_ids is None else plan_ids.reshape(ids.shape), mod_flat if split_ok else None)
+        plan_src, plan_mod = (ce_ids, ce_mod_ar) if ar else (ids if plan_ids is None else plan_ids.reshape(ids.shape), mod_flat)
+        head_plan = (self._plan_masked_rows(plan_src, plan_mod if split_ok else None)
                      if ((mode == "logp" and self.compact_head) or mode == "rows") else None)
 
         x = K.embedding_fwd(ids, self.vocab_embed.embedding.detach(), emb_mod if self.modality_embed is not None else None,
@@ -718,7 +760,7 @@ class DIT(nn.Module, _HubMixin):
             qn_kw = dict(gq=at.q_norm.weight.detach() if self.qk_norm else None, bq=at.q_norm.bias.detach() if self.qk_norm else None,
                          gk=at.k_norm.weight.detach() if self.qk_norm else None, bk=at.k_norm.bias.detach() if self.qk_norm else None)
             qkr, qstats = K.qknorm_rope_fwd(qkv, cos, sin, L, D, q_scale=self.attn_q_scale, **qn_kw)
-            o, lse = K.attention_fwd(qkr, qkv, B, L, H, D, sid, S["doc_ranges"], q_prescaled=True)
+            o, lse = K.attention_fwd(qkr, qkv, B, L, H, D, sid, S["doc_ranges"], q_prescaled=True, **self._attn_mask_kw)
             rows_c = last_rows
             if not recompute and i + 1 == self.n_blocks and head_plan is not None and mode == "logp" and self.compact_last_block and not tc:
                 head_rows_c = self._masked_rows(head_plan, M)   # (the count was queued at the top of this forward: the host does not wait for the device here)
@@ -796,15 +838,15 @@ class DIT(nn.Module, _HubMixin):
             if save:
                 S.update(x_final=x, hf=hf, rstdf=rstdf, meanf=meanf, fmod=fmod, logits=logits, head_rows=None)
             return logits[:, :V].view(B, L, V), S
-        x0 = inp["x0"].contiguous().view(-1).to(torch.int64)
+        x0 = (ce_x0 if ar else inp["x0"]).contiguous().view(-1).to(torch.int64)
         restrict = bool(inp.get("restrict", False))
-        if restrict and mod_flat is None:  # static slices (model.py:634-635)
-            cm = torch.zeros(L, dtype=torch.int64, device=dev)
-            cm[self.static_img_sl] = 1
-            ce_mod = cm[None].expand(B, L).contiguous().view(-1)
+        if ar:
+            ce_mod = ce_mod_ar
+        elif restrict and mod_flat is None:  # static slices (model.py:634-635)
+            ce_mod = self._static_modality(B, L, dev).view(-1)
         else:
             ce_mod = mod_flat
-        ids_h = ids
+        ids_h = ce_ids if ar else ids
         head_rows = self._masked_rows(head_plan, M) if head_plan is not None else None
         stream_compact = head_rows is not None and hf.shape[0] != M   # the last block already runs on the compacted rows (same list, same order)
         if head_rows is not None:  # compact operands: masked rows first, padded (with an unmasked row: zero loss, zero gradient) to a multiple of 64
@@ -812,7 +854,7 @@ class DIT(nn.Module, _HubMixin):
             # fixed-capacity buffers (views of M-row allocations): a different size every step would make the caching allocator go back
             # to hipMalloc until its pool covers every size seen (measured: occasional 120+ ms steps)
             hf_h = hf if stream_compact else torch.index_select(hf, 0, rows_p, out=torch.empty_like(hf)[: rows_p.numel()])
-            x0, ids_h = x0.index_select(0, rows_p), ids.index_select(0, rows_p)
+            x0, ids_h = x0.index_select(0, rows_p), ids_h.index_select(0, rows_p)
             ce_mod = ce_mod.index_select(0, rows_p) if ce_mod is not None else None
         else:
             hf_h = hf
@@ -856,6 +898,11 @@ class DIT(nn.Module, _HubMixin):
                      x0=x0, ce_mod=ce_mod, restrict=restrict, lse_ce=lse_ce, stream_compact=stream_compact, head_chunk=chunk,
                      head_groups=(head_plan.get("groups") if (head_plan is not None and head_rows is not None and restrict and not chunk) else None))
         return log_p.view(B, L), S
+
+    def _static_modality(self, B, L, dev):
+        cm = torch.zeros(L, dtype=torch.int64, device=dev)
+        cm[self.static_img_sl] = 1
+        return cm[None].expand(B, L).contiguous()
 
     def _plan_masked_rows(self, ids, mod=None):
         """Queue (without synchronising) a stable partition of the row indices with the [MASK] rows first and their count.  With `mod` (the rows' modality,
@@ -1203,7 +1250,7 @@ class DIT(nn.Module, _HubMixin):
                     self._wgrad(da, R["o"], lo, G)
             dqkr = torch.empty((M, 2 * d), dtype=BF16, device=dev)
             dqkv = torch.empty((M, 3 * d), dtype=BF16, device=dev)
-            K.attention_bwd(R["qkr"], R["qkv"], R["o"], do, R["lse"], dqkr, dqkv, B, L, H, D, S["sid"], S["doc_ranges"], q_prescaled=True)
+            K.attention_bwd(R["qkr"], R["qkv"], R["o"], do, R["lse"], dqkr, dqkv, B, L, H, D, S["sid"], S["doc_ranges"], q_prescaled=True, **self._attn_mask_kw)
             qn = self.qk_norm
             K.qknorm_rope_bwd(dqkr, R["qkv"], dqkv, S["cos"], S["sin"], L, D, gq=at.q_norm.weight.detach() if qn else None,
                               gk=at.k_norm.weight.detach() if qn else None, stats=R["qstats"], dgq=G[id(at.q_norm.weight)] if qn else None,

@@ -769,42 +769,51 @@ def attention_doc_ranges(sample_ids):
     return r
 
 
-def attention_fwd(qkr, qkv, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False):
-    """q, k from qkr [M,2d] (normalised+rotated), v from qkv [M,3d] columns [2d,3d).  q_prescaled: q holds q * attention_q_scale(D)."""
+ATTN_Q_PRESCALED, ATTN_CAUSAL = 1, 2   # flag bits of udm_attention_fwd / udm_attention_bwd (include/unidisc_hip.h)
+
+
+def _attn_flags(q_prescaled, causal):
+    return (ATTN_Q_PRESCALED if q_prescaled else 0) | (ATTN_CAUSAL if causal else 0)
+
+
+def attention_fwd(qkr, qkv, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False, causal=False):
+    """q, k from qkr [M,2d] (normalised+rotated), v from qkv [M,3d] columns [2d,3d).  q_prescaled: q holds q * attention_q_scale(D).
+    causal: query i sees keys j <= i (not combinable with sample_ids)."""
     d = H * D
     M = B * L
     o = torch.empty((M, d), dtype=BF16, device=qkr.device)
     lse = torch.empty((B, H, L), dtype=F32, device=qkr.device)
     q_ptr, k_ptr, v_ptr = qkr.data_ptr(), qkr.data_ptr() + 2 * d, qkv.data_ptr() + 4 * d
-    _lib.call("udm_attention_fwd", q_ptr, k_ptr, v_ptr, _p(o), _p(lse), _p(sample_ids), _p(doc_ranges), B, H, L, D, 2 * d, 2 * d, 3 * d, d, 1 if q_prescaled else 0, _s())
+    _lib.call("udm_attention_fwd", q_ptr, k_ptr, v_ptr, _p(o), _p(lse), _p(sample_ids), _p(doc_ranges), B, H, L, D, 2 * d, 2 * d, 3 * d, d,
+              _attn_flags(q_prescaled, causal), _s())
     return o, lse
 
 
-def attention_bwd(qkr, qkv, o, do, lse, dqkr, dqkv, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False):
+def attention_bwd(qkr, qkv, o, do, lse, dqkr, dqkv, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False, causal=False):
     """Writes dq|dk (wrt the stored rotated q, k) into dqkr [M,2d] and dv into dqkv[:, 2d:3d]."""
     d = H * D
     delta = torch.empty((3, B, H, L), dtype=F32, device=qkr.device)   # delta | -lse | -delta (include/unidisc_hip.h)
     q_ptr, k_ptr, v_ptr = qkr.data_ptr(), qkr.data_ptr() + 2 * d, qkv.data_ptr() + 4 * d
     dq_ptr, dk_ptr, dv_ptr = dqkr.data_ptr(), dqkr.data_ptr() + 2 * d, dqkv.data_ptr() + 4 * d
     _lib.call("udm_attention_bwd", q_ptr, k_ptr, v_ptr, _p(o), _p(do), _p(lse), _p(delta), dq_ptr, dk_ptr, dv_ptr, _p(sample_ids), _p(doc_ranges), B, H, L, D, 2 * d,
-              2 * d, 3 * d, d, do.stride(0), 2 * d, 2 * d, 3 * d, 1 if q_prescaled else 0, _s())
+              2 * d, 3 * d, d, do.stride(0), 2 * d, 2 * d, 3 * d, _attn_flags(q_prescaled, causal), _s())
 
 
-def attention_fwd_generic(q, k, v, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False):
+def attention_fwd_generic(q, k, v, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False, causal=False):
     """q, k, v: separate contiguous bf16 [B*L, H*D] (unit tests)."""
     d = H * D
     o = torch.empty((B * L, d), dtype=BF16, device=q.device)
     lse = torch.empty((B, H, L), dtype=F32, device=q.device)
-    _lib.call("udm_attention_fwd", _p(q), _p(k), _p(v), _p(o), _p(lse), _p(sample_ids), _p(doc_ranges), B, H, L, D, d, d, d, d, 1 if q_prescaled else 0, _s())
+    _lib.call("udm_attention_fwd", _p(q), _p(k), _p(v), _p(o), _p(lse), _p(sample_ids), _p(doc_ranges), B, H, L, D, d, d, d, d, _attn_flags(q_prescaled, causal), _s())
     return o, lse
 
 
-def attention_bwd_generic(q, k, v, o, do, lse, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False):
+def attention_bwd_generic(q, k, v, o, do, lse, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False, causal=False):
     d = H * D
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
     delta = torch.empty((3, B, H, L), dtype=F32, device=q.device)
     _lib.call("udm_attention_bwd", _p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), _p(sample_ids), _p(doc_ranges), B, H, L, D, d, d, d, d,
-              d, d, d, d, 1 if q_prescaled else 0, _s())
+              d, d, d, d, _attn_flags(q_prescaled, causal), _s())
     return dq, dk, dv
 
 
