@@ -304,6 +304,29 @@ int udm_adamw_step_shadow_ema(float* p, const float* g, float* m, float* v, int6
                               float weight_decay, int64_t step, const float* grad_norm_sq, float max_grad_norm, void* w16, int64_t ld16, void* w16t,
                               int64_t ldt, float* ema, float ema_decay, hipStream_t stream);
 
+/* ---- KV-cached AR decoding: `_ar_sampler` model_eval.py:2736-2822 with model.use_kv_cache (cache models/dit.py:588-607, 776-780, 1462-1473).
+ * udm_gemm_skinny_bf16: C[M, N] = A[M, K] W[N, K]^T for 1 <= M <= 64 (a decode step's rows against the bf16 weight shadows): each weight byte is read once,
+ *   by one workgroup; K is also split over workgroups (fp32 partial slabs in ws, a second launch sums them) where the column tiles alone leave CUs idle.
+ *   K % 32 == 0, lda / ldw multiples of 8; epilogue UDM_EPI_NONE, UDM_EPI_BIAS or UDM_EPI_BIAS_GELU (C = gelu_tanh(bf16(A W^T + bias)), no saved derivative);
+ *   out_f32: C is fp32.  ws (nullable: never split): fp32, slices * M * N elements are used, slices <= 32.
+ * udm_attention_decode: one new token per sequence, every row at position p.  Writes the new key row (k_new: after qk-norm + rope, as udm_qknorm_rope_fwd
+ *   leaves it) and value row (v_new) into slot p of k_cache / v_cache (bf16 [B, Lmax, H D]: element (b, l, h, :) at base + (b Lmax + l) H D + h D, the
+ *   udm_attention_fwd layout) and o[b, h] = softmax(q Kc[b, :p+1, h]^T) Vc[b, :p+1, h] with q pre-scaled (UDM_ATTN_Q_PRESCALED semantics: the scores are
+ *   base-2 exponents).  D = 32 / 64 / 128.  Keys are split over workgroups (fp32 partials in ws, (D + 2) floats per (b, h, split), at most 32 splits;
+ *   a second launch combines them); ws NULL or too small: fewer splits.  Every other cache slot is left as it is.
+ * udm_ar_sample_rows: the token of position pos for each of the R rows, one launch per step: z = logits (or (1 + *w) logits - *w logits_uncond) in fp32,
+ *   [MASK] excluded and, with restrict_modality, the ids of the other modality than modality[r, pos] (ids < Vt are text); y = argmax(z + g) (first index
+ *   on ties), g = the explicit Gumbel noise g[r * ldg + g_col0 + id] (replay of a recorded draw) or Philox Gumbel keyed by (seed, step, row, id).  Writes
+ *   x[r, pos] = x0_unmask[r, pos] ? x0[r, pos] : y (x, x0 int64, x0_unmask bool bytes, all [R, ldx]; modality int64 [R, ldm]) and, when next_ids is given,
+ *   next_ids[r] = that token and - with guidance - next_ids[R + r] = x0_unmask[r, pos] ? mask_id : that token (the unconditional half's next input). */
+int udm_gemm_skinny_bf16(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc, int out_f32,
+                         int epilogue, const float* bias, float* ws, int64_t ws_elems, hipStream_t stream);
+int udm_attention_decode(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, void* o, float* ws, int64_t ws_elems, int64_t B,
+                         int64_t H, int64_t D, int64_t Lmax, int64_t p, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, hipStream_t stream);
+int udm_ar_sample_rows(const void* logits, const void* logits_uncond, const float* w, int64_t ld, const int64_t* modality, int64_t ldm, const float* g,
+                       int64_t ldg, int64_t g_col0, uint64_t seed, int64_t step, int64_t* x, int64_t ldx, const int64_t* x0, const void* x0_unmask, int64_t pos,
+                       int64_t* next_ids, int64_t R, int64_t V, int64_t Vt, int64_t mask_id, int restrict_modality, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

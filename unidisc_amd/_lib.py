@@ -78,6 +78,9 @@ PROTOTYPES = {
     "udm_timestep_embedding": [_P, _P, _I64, _I64, _P],
     "udm_silu_fwd": [_P, _P, _I64, _P],
     "udm_silu_bwd": [_P, _P, _P, _I64, _P],
+    "udm_gemm_skinny_bf16": [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _P, _P, _I64, _P],
+    "udm_attention_decode": [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P],
+    "udm_ar_sample_rows": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _U64, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I, _P],
 }
 EXTRA_SYMBOLS = ["udm_last_error", "udm_abi_version"]
 ABI_VERSION = 3   # the UDM_ABI_VERSION of include/unidisc_hip.h that PROTOTYPES was written for (bumped whenever a signature changes)

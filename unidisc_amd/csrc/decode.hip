@@ -1,0 +1,445 @@
+// KV-cached next-token decoding of the AR baseline (`_ar_sampler`, model_eval.py:2736-2822, cache models/dit.py:588-607, 776-780, 1462-1473): the three
+// kernels a decode step needs that the training path has no form for.
+//
+//   udm_gemm_skinny_bf16   out[M, N] = A[M, K] W[N, K]^T for M <= 64 (the B rows of a decode step): weight streaming.  Every weight byte is read from HBM
+//                          by exactly one workgroup.  A wave owns 32 output columns over a K range and loads its operands straight to VGPRs (16 B per lane,
+//                          four 32-deep k-steps in flight) for 16x16x32 MFMAs; the four waves of a workgroup split the workgroup's K range and sum through
+//                          LDS.  Where the column tiles alone leave CUs idle (N = d out-projection, K = 4 d down-projection) K is also split over
+//                          workgroups: fp32 partial slabs in `ws` and a second launch that sums them and applies the epilogue.
+//   udm_attention_decode   one query row per (b, h) against the per-layer cache, all rows at the same position p (flash-decoding): the keys are split
+//                          over workgroups so that B H x splits covers the chip; each split keeps fp32 (m, l, acc) and a second launch combines them.  The
+//                          new key / value row is read from its producer for key p and written to cache slot p by the split that owns p - no other
+//                          workgroup of the launch reads slot p, so the append needs no ordering.
+//   udm_ar_sample_rows     the token choice: argmax(z + Gumbel) over one row per block, z = logits or (1 + w) l_c - w l_u in fp32 with [MASK] and (by next
+//                          modality) the other modality's ids excluded, and the chosen id written straight into x[b, pos] (x0 write-back applied) and into
+//                          the next step's input ids - the token loop never reads the device.
+#include "common.h"
+#include "../../include/unidisc_hip.h"
+
+namespace {
+
+using udm::bf2f;
+using udm::f2bf;
+
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;   // 16 bytes as a native vector (what __builtin_nontemporal_load takes)
+__device__ __forceinline__ bf16x8_t as_frag(u32x4_t v) { return __builtin_bit_cast(bf16x8_t, v); }
+
+// ------------------------------------------------------------------------------------------------ skinny GEMM
+struct SkArgs {
+  const bf16_t* A;
+  const bf16_t* W;
+  void* C;
+  float* ws;
+  const float* bias;
+  long lda, ldw, ldc;
+  int M, N, K, kslice, S, out_f32, epi;
+};
+
+constexpr int SK_U = 4;          // k-steps of 32 in flight per wave
+constexpr int SK_NB = 2;         // 16-column MFMA tiles per wave (32 columns)
+
+__device__ __forceinline__ float sk_epilogue(float v, int n, const SkArgs& a) {
+  if (a.epi == UDM_EPI_BIAS || a.epi == UDM_EPI_BIAS_GELU) v += a.bias[n];
+  if (a.epi == UDM_EPI_BIAS_GELU) v = udm::gelu_tanh(bf2f(f2bf(v)));   // u = bf16(A W^T + bias), C = gelu(u): the training epilogue's roundings
+  return v;
+}
+
+__device__ __forceinline__ void sk_store(const SkArgs& a, int m, int n, float v) {
+  if (a.out_f32) ((float*)a.C)[(long)m * a.ldc + n] = v;
+  else ((bf16_t*)a.C)[(long)m * a.ldc + n] = f2bf(v);
+}
+
+template <int MT>
+__global__ __launch_bounds__(256) void skinny_gemm_kernel(SkArgs a) {
+  __shared__ float red[4 * MT * SK_NB * 4 * 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n0 = blockIdx.x * 32;
+  const int s = blockIdx.y;
+  const int kbeg = s * a.kslice;
+  const int kend = min(a.K, kbeg + a.kslice);
+  const int kl = 8 * (lane >> 4);
+  // operand rows of this lane (rows past M / N are clamped to a valid row: their products land in outputs nobody stores)
+  const bf16_t* wrow[SK_NB];
+#pragma unroll
+  for (int nb = 0; nb < SK_NB; ++nb) wrow[nb] = a.W + (long)min(n0 + nb * 16 + (lane & 15), a.N - 1) * a.ldw + kl;
+  const bf16_t* arow[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) arow[mt] = a.A + (long)min(mt * 16 + (lane & 15), a.M - 1) * a.lda + kl;
+
+  f32x4_t acc[MT][SK_NB];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int nb = 0; nb < SK_NB; ++nb) acc[mt][nb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+  for (int k0 = kbeg + wave * 32 * SK_U; k0 < kend; k0 += 4 * 32 * SK_U) {
+    u32x4_t wf[SK_U][SK_NB], af[SK_U][MT];
+#pragma unroll
+    for (int u = 0; u < SK_U; ++u) {
+      const int k = k0 + 32 * u;
+      const bool ok = k < kend;   // (K % 32 == 0: a k-step is whole or absent)
+#pragma unroll
+      for (int nb = 0; nb < SK_NB; ++nb) wf[u][nb] = ok ? __builtin_nontemporal_load((const u32x4_t*)(wrow[nb] + k)) : u32x4_t{0, 0, 0, 0};
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) af[u][mt] = ok ? *(const u32x4_t*)(arow[mt] + k) : u32x4_t{0, 0, 0, 0};
+    }
+#pragma unroll
+    for (int u = 0; u < SK_U; ++u)
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nb = 0; nb < SK_NB; ++nb) acc[mt][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(af[u][mt]), as_frag(wf[u][nb]), acc[mt][nb], 0, 0, 0);
+  }
+  // the four waves' K ranges summed through LDS; element e = ((mt * NB + nb) * 4 + r) * 64 + lane
+  constexpr int E = MT * SK_NB * 4 * 64;
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int nb = 0; nb < SK_NB; ++nb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wave * E + ((mt * SK_NB + nb) * 4 + r) * 64 + lane] = acc[mt][nb][r];
+  __syncthreads();
+  for (int e = threadIdx.x; e < E; e += 256) {
+    const float v = red[e] + red[E + e] + red[2 * E + e] + red[3 * E + e];
+    const int ln = e & 63, r = (e >> 6) & 3, t = e >> 8;
+    const int nb = t % SK_NB, mt = t / SK_NB;
+    const int m = mt * 16 + (ln >> 4) * 4 + r, n = n0 + nb * 16 + (ln & 15);
+    if (m >= a.M || n >= a.N) continue;
+    if (a.S == 1) sk_store(a, m, n, sk_epilogue(v, n, a));
+    else a.ws[((long)s * a.M + m) * a.N + n] = v;
+  }
+}
+
+__global__ __launch_bounds__(256) void skinny_reduce_kernel(SkArgs a) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)a.M * a.N) return;
+  const int m = (int)(i / a.N), n = (int)(i % a.N);
+  float v = 0.f;
+  for (int s = 0; s < a.S; ++s) v += a.ws[(long)s * a.M * a.N + i];
+  sk_store(a, m, n, sk_epilogue(v, n, a));
+}
+
+// ------------------------------------------------------------------------------------------------ decode attention
+struct DecArgs {
+  const bf16_t* q;
+  const bf16_t* knew;
+  const bf16_t* vnew;
+  bf16_t* Kc;
+  bf16_t* Vc;
+  bf16_t* o;
+  float* ws;
+  long q_stride, k_stride, v_stride, o_stride;
+  int H, Lmax, p, S, chunk;
+};
+
+constexpr int DEC_U = 4;   // keys per lane group in flight
+
+template <int D>
+__global__ __launch_bounds__(256) void attn_decode_kernel(DecArgs a) {
+  constexpr int G = D / 8;          // lanes per key (16 B each)
+  constexpr int KPW = 64 / G;       // keys per wave per load round
+  constexpr int NG = 4 * KPW;       // lane groups per block
+  __shared__ float sm_acc[NG * D];
+  __shared__ float sm_m[NG], sm_l[NG];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane / G, c = lane % G;
+  const int grp = wave * KPW + g;
+  const int bh = blockIdx.x, s = blockIdx.y;
+  const int b = bh / a.H, h = bh % a.H;
+  const long d = (long)a.H * D;
+  const int lo = s * a.chunk, hi = min(a.p + 1, lo + a.chunk);
+  const long cache_row0 = (long)b * a.Lmax * d + h * D + c * 8;
+
+  const uint4 qv = *(const uint4*)(a.q + b * a.q_stride + h * D + c * 8);
+  const uint4 knv = *(const uint4*)(a.knew + b * a.k_stride + h * D + c * 8);
+  const uint4 vnv = *(const uint4*)(a.vnew + b * a.v_stride + h * D + c * 8);
+  if (s == a.S - 1 && threadIdx.x < G) {   // cache append: slot p of this (b, h), written by the one split that reads key p (from knew / vnew)
+    *(uint4*)(a.Kc + cache_row0 + (long)a.p * d) = knv;
+    *(uint4*)(a.Vc + cache_row0 + (long)a.p * d) = vnv;
+  }
+  float qf[8];
+  {
+    const bf16_t* qe = (const bf16_t*)&qv;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) qf[i] = bf2f(qe[i]);
+  }
+  float m = -INFINITY, l = 0.f, acc[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+
+  for (int base = lo; base < hi; base += NG * DEC_U) {
+    uint4 kk[DEC_U], vv[DEC_U];
+    int js[DEC_U];
+#pragma unroll
+    for (int u = 0; u < DEC_U; ++u) {
+      const int j = base + u * NG + grp;
+      js[u] = j;
+      const int jc = min(j, a.p - 1 < 0 ? 0 : a.p - 1);   // (clamped address for keys outside [lo, hi) and for key p; their values are not used)
+      const long off = cache_row0 + (long)jc * d;
+      kk[u] = (j < hi && j != a.p) ? *(const uint4*)(a.Kc + off) : knv;
+      vv[u] = (j < hi && j != a.p) ? *(const uint4*)(a.Vc + off) : vnv;
+    }
+    float sc[DEC_U];
+    float mx = m;
+#pragma unroll
+    for (int u = 0; u < DEC_U; ++u) {
+      const bf16_t* ke = (const bf16_t*)&kk[u];
+      float t = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) t += qf[i] * bf2f(ke[i]);
+#pragma unroll
+      for (int o = 1; o < G; o <<= 1) t += __shfl_xor(t, o, 64);
+      sc[u] = js[u] < hi ? t : -INFINITY;
+      mx = fmaxf(mx, sc[u]);
+    }
+    if (mx == -INFINITY) continue;
+    const float scale = __builtin_amdgcn_exp2f(m - mx);   // (m = -inf: 0)
+    l *= scale;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] *= scale;
+#pragma unroll
+    for (int u = 0; u < DEC_U; ++u) {
+      const float pu = __builtin_amdgcn_exp2f(sc[u] - mx);
+      l += pu;
+      const bf16_t* ve = (const bf16_t*)&vv[u];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc[i] += pu * bf2f(ve[i]);
+    }
+    m = mx;
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) sm_acc[grp * D + c * 8 + i] = acc[i];
+  if (c == 0) {
+    sm_m[grp] = m;
+    sm_l[grp] = l;
+  }
+  __syncthreads();
+  if (threadIdx.x < D) {
+    const int t = threadIdx.x;
+    float M = -INFINITY;
+    for (int gi = 0; gi < NG; ++gi) M = fmaxf(M, sm_m[gi]);
+    float L = 0.f, A = 0.f;
+    for (int gi = 0; gi < NG; ++gi) {
+      if (sm_m[gi] == -INFINITY) continue;
+      const float wgt = __builtin_amdgcn_exp2f(sm_m[gi] - M);
+      L += wgt * sm_l[gi];
+      A += wgt * sm_acc[gi * D + t];
+    }
+    if (a.S == 1) {
+      a.o[b * a.o_stride + h * D + t] = f2bf(A / L);
+    } else {
+      float* w = a.ws + ((long)bh * a.S + s) * (D + 2);
+      w[2 + t] = A;
+      if (t == 0) {
+        w[0] = M;
+        w[1] = L;
+      }
+    }
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(128) void attn_decode_combine_kernel(DecArgs a) {
+  const int bh = blockIdx.x, t = threadIdx.x;
+  if (t >= D) return;
+  const int b = bh / a.H, h = bh % a.H;
+  const float* w = a.ws + (long)bh * a.S * (D + 2);
+  float M = -INFINITY;
+  for (int s = 0; s < a.S; ++s) M = fmaxf(M, w[s * (D + 2)]);
+  float L = 0.f, A = 0.f;
+  for (int s = 0; s < a.S; ++s) {
+    const float wgt = __builtin_amdgcn_exp2f(w[s * (D + 2)] - M);
+    L += wgt * w[s * (D + 2) + 1];
+    A += wgt * w[s * (D + 2) + 2 + t];
+  }
+  a.o[b * a.o_stride + h * D + t] = f2bf(A / L);
+}
+
+// ------------------------------------------------------------------------------------------------ AR token choice
+struct ArArgs {
+  const bf16_t* logits;
+  const bf16_t* logits_u;
+  const float* w;
+  const int64_t* modality;
+  const float* g;
+  int64_t* x;
+  const int64_t* x0;
+  const uint8_t* unmask;
+  int64_t* next_ids;
+  long ld, ldg, g_col0, ldx, ldm, pos, step, V, Vt, mask_id;
+  uint64_t seed;
+  int R, restrict_modality;
+};
+
+__device__ __forceinline__ bool ar_better(float v, long i, float bv, long bi) { return v > bv || (v == bv && i < bi); }
+
+__device__ __forceinline__ float gumbel_of(uint32_t r) {
+  const float u = ((float)(r >> 8) + 0.5f) * (1.0f / 16777216.0f);   // (0, 1)
+  return -__logf(-__logf(u));
+}
+
+__global__ __launch_bounds__(512) void ar_sample_rows_kernel(ArArgs a) {
+  __shared__ float sv[8];
+  __shared__ long si[8];
+  const int b = blockIdx.x;
+  const int t = threadIdx.x;
+  const bf16_t* lr = a.logits + (long)b * a.ld;
+  const bf16_t* lu = a.logits_u ? a.logits_u + (long)b * a.ld : nullptr;
+  const float w = a.logits_u ? *a.w : 0.f;
+  const int img = a.restrict_modality ? (a.modality[(long)b * a.ldm + a.pos] == 1) : -1;
+  const uint64_t key = a.seed ^ ((uint64_t)(a.step + 1) * 0x9E3779B97F4A7C15ull);
+  float bv = -INFINITY;
+  long bi = 0x7fffffffffffffffL;
+  for (long v0 = (long)t * 8; v0 < a.V; v0 += 512 * 8) {
+    const uint4 raw = *(const uint4*)(lr + v0);
+    uint4 rawu = make_uint4(0, 0, 0, 0);
+    if (lu) rawu = *(const uint4*)(lu + v0);
+    uint32_t rnd[8];
+    if (!a.g) {
+      const uint4 r0 = udm::philox4x32(key, ((uint64_t)b << 40) | (uint64_t)(v0 >> 2));
+      const uint4 r1 = udm::philox4x32(key, ((uint64_t)b << 40) | (uint64_t)((v0 >> 2) + 1));
+      rnd[0] = r0.x, rnd[1] = r0.y, rnd[2] = r0.z, rnd[3] = r0.w, rnd[4] = r1.x, rnd[5] = r1.y, rnd[6] = r1.z, rnd[7] = r1.w;
+    }
+    const bf16_t* le = (const bf16_t*)&raw;
+    const bf16_t* ue = (const bf16_t*)&rawu;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const long v = v0 + i;
+      if (v >= a.V || v == a.mask_id) continue;
+      if (img >= 0 && (img ? v < a.Vt : v >= a.Vt)) continue;
+      float z = bf2f(le[i]);
+      if (lu) z = (1.f + w) * z - w * bf2f(ue[i]);
+      z += a.g ? a.g[(long)b * a.ldg + a.g_col0 + v] : gumbel_of(rnd[i]);
+      if (ar_better(z, v, bv, bi)) bv = z, bi = v;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const long oi = __shfl_xor(bi, o, 64);
+    if (ar_better(ov, oi, bv, bi)) bv = ov, bi = oi;
+  }
+  if ((t & 63) == 0) {
+    sv[t >> 6] = bv;
+    si[t >> 6] = bi;
+  }
+  __syncthreads();
+  if (t == 0) {
+    for (int i = 1; i < 8; ++i)
+      if (ar_better(sv[i], si[i], bv, bi)) bv = sv[i], bi = si[i];
+    if (bi == 0x7fffffffffffffffL) bi = 0;   // (no admissible id: cannot happen for V > 1 without NaN logits)
+    const long at = (long)b * a.ldx + a.pos;
+    const bool keep = a.unmask && a.unmask[at];
+    const int64_t val = keep ? a.x0[at] : (int64_t)bi;
+    a.x[at] = val;
+    if (a.next_ids) {
+      a.next_ids[b] = val;
+      if (a.logits_u) a.next_ids[a.R + b] = keep ? a.mask_id : val;   // the unconditional half: where(x0_unmask, mask, x)
+    }
+  }
+}
+
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" int udm_gemm_skinny_bf16(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc, int out_f32,
+                                    int epilogue, const float* bias, float* ws, int64_t ws_elems, hipStream_t stream) {
+  UDM_CHECK_ARG(A && W && C, "udm_gemm_skinny_bf16: null pointer");
+  UDM_CHECK_ARG(M >= 1 && M <= 64 && N >= 1 && K >= 32 && K % 32 == 0, "udm_gemm_skinny_bf16: bad shape M=%ld N=%ld K=%ld (1 <= M <= 64, K %% 32 == 0)",
+                (long)M, (long)N, (long)K);
+  UDM_CHECK_ARG(lda >= K && ldw >= K && ldc >= N && lda % 8 == 0 && ldw % 8 == 0, "udm_gemm_skinny_bf16: bad leading dimensions");
+  UDM_CHECK_ARG(al16(A) && al16(W) && al16(C) && (!ws || al16(ws)) && (!bias || al16(bias)), "udm_gemm_skinny_bf16: operands must be 16-byte aligned");
+  UDM_CHECK_ARG(epilogue == UDM_EPI_NONE || epilogue == UDM_EPI_BIAS || epilogue == UDM_EPI_BIAS_GELU, "udm_gemm_skinny_bf16: epilogue %d not supported", epilogue);
+  UDM_CHECK_ARG(epilogue == UDM_EPI_NONE || bias, "udm_gemm_skinny_bf16: the epilogue needs a bias");
+  UDM_CHECK_ARG(N < (1L << 30) && K < (1L << 30), "udm_gemm_skinny_bf16: shape too large");
+  const int nblk = (int)((N + 31) / 32);
+  // K split over workgroups until about two workgroups per CU stream (each slice >= 128 deep, the partial slabs must fit ws)
+  int S = 1;
+  if (ws && nblk < 512) {
+    S = (512 + nblk / 2) / nblk;
+    S = min(S, (int)(K / 128));
+    S = min(S, 32);
+    const int64_t cap = ws_elems / (M * N);
+    if (S > cap) S = (int)cap;
+    if (S < 1) S = 1;
+  }
+  int kslice = (int)(((K + S - 1) / S + 31) / 32 * 32);
+  S = (int)((K + kslice - 1) / kslice);
+  SkArgs a{(const bf16_t*)A, (const bf16_t*)W, C, ws, bias, (long)lda, (long)ldw, (long)ldc, (int)M, (int)N, (int)K, kslice, S, out_f32, epilogue};
+  const dim3 grid(nblk, S);
+  const int MT = (int)((M + 15) / 16);
+  switch (MT) {
+    case 1: hipLaunchKernelGGL(skinny_gemm_kernel<1>, grid, dim3(256), 0, stream, a); break;
+    case 2: hipLaunchKernelGGL(skinny_gemm_kernel<2>, grid, dim3(256), 0, stream, a); break;
+    case 3: hipLaunchKernelGGL(skinny_gemm_kernel<3>, grid, dim3(256), 0, stream, a); break;
+    default: hipLaunchKernelGGL(skinny_gemm_kernel<4>, grid, dim3(256), 0, stream, a); break;
+  }
+  UDM_CHECK_LAUNCH("udm_gemm_skinny_bf16");
+  if (S > 1) {
+    hipLaunchKernelGGL(skinny_reduce_kernel, dim3((unsigned)((M * N + 255) / 256)), dim3(256), 0, stream, a);
+    UDM_CHECK_LAUNCH("udm_gemm_skinny_bf16 (reduce)");
+  }
+  return 0;
+}
+
+extern "C" int udm_attention_decode(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, void* o, float* ws, int64_t ws_elems,
+                                    int64_t B, int64_t H, int64_t D, int64_t Lmax, int64_t p, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                                    int64_t o_stride, hipStream_t stream) {
+  UDM_CHECK_ARG(q && k_new && v_new && k_cache && v_cache && o, "udm_attention_decode: null pointer");
+  UDM_CHECK_ARG(D == 32 || D == 64 || D == 128, "udm_attention_decode: head dim %ld (32 / 64 / 128)", (long)D);
+  UDM_CHECK_ARG(B >= 1 && H >= 1 && Lmax >= 1 && p >= 0 && p < Lmax && Lmax < (1L << 30) && B * H < (1L << 30), "udm_attention_decode: bad shape B=%ld H=%ld Lmax=%ld p=%ld",
+                (long)B, (long)H, (long)Lmax, (long)p);
+  UDM_CHECK_ARG(q_stride % 8 == 0 && k_stride % 8 == 0 && v_stride % 8 == 0 && o_stride % 8 == 0 && q_stride >= H * D && k_stride >= H * D &&
+                    v_stride >= H * D && o_stride >= H * D, "udm_attention_decode: bad row strides");
+  UDM_CHECK_ARG(al16(q) && al16(k_new) && al16(v_new) && al16(k_cache) && al16(v_cache) && al16(o) && (!ws || al16(ws)),
+                "udm_attention_decode: operands must be 16-byte aligned");
+  const long n = p + 1, BH = B * H;
+  // splits: about two workgroups per CU over B H, at least 64 keys each, at most 32, bounded by ws
+  long S = (512 + BH - 1) / BH;
+  S = S < 32 ? S : 32;
+  S = S < (n + 63) / 64 ? S : (n + 63) / 64;
+  const long cap = ws ? ws_elems / (BH * (D + 2)) : 1;
+  if (S > cap) S = cap;
+  if (S < 1) S = 1;
+  long chunk = ((n + S - 1) / S + 63) / 64 * 64;
+  S = (n + chunk - 1) / chunk;
+  DecArgs a{(const bf16_t*)q, (const bf16_t*)k_new, (const bf16_t*)v_new, (bf16_t*)k_cache, (bf16_t*)v_cache, (bf16_t*)o, ws, (long)q_stride, (long)k_stride,
+            (long)v_stride, (long)o_stride, (int)H, (int)Lmax, (int)p, (int)S, (int)chunk};
+  const dim3 grid((unsigned)BH, (unsigned)S);
+  switch (D) {
+    case 32: hipLaunchKernelGGL(attn_decode_kernel<32>, grid, dim3(256), 0, stream, a); break;
+    case 64: hipLaunchKernelGGL(attn_decode_kernel<64>, grid, dim3(256), 0, stream, a); break;
+    default: hipLaunchKernelGGL(attn_decode_kernel<128>, grid, dim3(256), 0, stream, a); break;
+  }
+  UDM_CHECK_LAUNCH("udm_attention_decode");
+  if (S > 1) {
+    switch (D) {
+      case 32: hipLaunchKernelGGL(attn_decode_combine_kernel<32>, dim3((unsigned)BH), dim3(128), 0, stream, a); break;
+      case 64: hipLaunchKernelGGL(attn_decode_combine_kernel<64>, dim3((unsigned)BH), dim3(128), 0, stream, a); break;
+      default: hipLaunchKernelGGL(attn_decode_combine_kernel<128>, dim3((unsigned)BH), dim3(128), 0, stream, a); break;
+    }
+    UDM_CHECK_LAUNCH("udm_attention_decode (combine)");
+  }
+  return 0;
+}
+
+extern "C" int udm_ar_sample_rows(const void* logits, const void* logits_uncond, const float* w, int64_t ld, const int64_t* modality, int64_t ldm, const float* g,
+                                  int64_t ldg, int64_t g_col0, uint64_t seed, int64_t step, int64_t* x, int64_t ldx, const int64_t* x0, const void* x0_unmask,
+                                  int64_t pos, int64_t* next_ids, int64_t R, int64_t V, int64_t Vt, int64_t mask_id, int restrict_modality, hipStream_t stream) {
+  UDM_CHECK_ARG(logits && x, "udm_ar_sample_rows: null pointer");
+  UDM_CHECK_ARG(R >= 1 && V >= 1 && ld >= V && ld % 8 == 0 && pos >= 0 && pos < ldx, "udm_ar_sample_rows: bad shape R=%ld V=%ld ld=%ld pos=%ld", (long)R, (long)V,
+                (long)ld, (long)pos);
+  UDM_CHECK_ARG(!logits_uncond || w, "udm_ar_sample_rows: guidance needs the weight");
+  UDM_CHECK_ARG(!restrict_modality || (modality && ldm > pos && Vt > 0 && Vt < V), "udm_ar_sample_rows: the restriction needs the modality map and 0 < Vt < V");
+  UDM_CHECK_ARG(!x0_unmask || x0, "udm_ar_sample_rows: x0_unmask needs x0");
+  UDM_CHECK_ARG(!g || (ldg >= g_col0 + V && g_col0 >= 0), "udm_ar_sample_rows: bad noise layout");
+  UDM_CHECK_ARG(al16(logits) && (!logits_uncond || al16(logits_uncond)) && (!w || al16(w)) && (!modality || al16(modality)) && (!g || al16(g)) && al16(x) &&
+                    (!x0 || al16(x0)) && (!x0_unmask || al16(x0_unmask)) && (!next_ids || al16(next_ids)),
+                "udm_ar_sample_rows: operands must be 16-byte aligned");
+  ArArgs a{(const bf16_t*)logits, (const bf16_t*)logits_uncond, w, modality, g, x, x0, (const uint8_t*)x0_unmask, next_ids, (long)ld, (long)ldg, (long)g_col0,
+           (long)ldx, (long)ldm, (long)pos, (long)step, (long)V, (long)Vt, (long)mask_id, seed, (int)R, restrict_modality};
+  hipLaunchKernelGGL(ar_sample_rows_kernel, dim3((unsigned)R), dim3(512), 0, stream, a);
+  UDM_CHECK_LAUNCH("udm_ar_sample_rows");
+  return 0;
+}

@@ -807,6 +807,134 @@ class Diffusion:
         pred_full.view(-1).index_copy_(0, rows_n, tok)
         return torch.where(result, pred_full, x), 1
 
+    # ---- AR baseline sampler: `_ar_sampler` model_eval.py:2736-2822 on the backbone's KV cache (reset_kv_cache / forward(start_pos=...))
+    def _ar_bos_id(self, bos_token_id=None):
+        """tokenizer.bos_token_id (model_eval.py:2742), else the `bos_token_id=` extension, else an error"""
+        bos = getattr(self.tokenizer, "bos_token_id", None) if self.tokenizer is not None else None
+        if bos is None:
+            bos = bos_token_id
+        if bos is None:
+            raise ValueError("unidisc_amd.Diffusion._ar_sampler: no BOS id - the tokenizer has no bos_token_id and no bos_token_id= was given")
+        return int(bos)
+
+    @staticmethod
+    def _ar_fixed_prefix(x0_unmask, L):
+        """Length n0 >= 1 of the prefix that is final in every row before decoding starts: position 0 (BOS or x0) plus the common leading run of x0_unmask
+        from position 1.  Those tokens are never redrawn, so prefilling them is exact; capped at L - 1 (the positions the sampler feeds)."""
+        n0 = 1
+        if x0_unmask is not None:
+            run = x0_unmask[:, 1:].all(0).to(torch.int64).cpu()
+            n0 += int(run.cumprod(0).sum())
+        return min(n0, L - 1)
+
+    @staticmethod
+    def _ar_nucleus(z, top_p, temperature, generator=None):
+        """`nucleus_sampling` (model_eval.py:2691-2734), not the p / T quirk of nucleus_sampling_batch: softmax(z / T), sort, keep cumsum <= top_p plus the top
+        id, renormalise, multinomial.  z fp32 [R, V] with excluded ids at -inf (softmax is shift-invariant: raw logits give the log-probs' distribution)."""
+        probs = torch.softmax(z / temperature, dim=-1)
+        sp, si = torch.sort(probs, descending=True, dim=-1)
+        keep = sp.cumsum(-1) <= top_p
+        keep[..., 0] = True
+        fp = sp * keep.float()
+        fp = fp / fp.sum(-1, keepdim=True)
+        return si.gather(-1, torch.multinomial(fp, 1, generator=generator)).squeeze(-1)
+
+    def _ar_excluded(self, next_modality):
+        """bool [R, V]: the [MASK] id and, with force_argmax_valid_indices, the other modality's ids than next_modality [R]"""
+        V, Vt = self.vocab_size, self.text_vocab_size
+        ids = torch.arange(V, device=next_modality.device if next_modality is not None else self.device)
+        bad = (ids == self.mask_index)[None]
+        if next_modality is not None:
+            img = (next_modality == 1)[:, None]
+            bad = bad | torch.where(img, ids[None] < Vt, ids[None] >= Vt)
+        return bad
+
+    @torch.no_grad()
+    def _ar_sampler(self, B, x0=None, x0_unmask=None, modality=None, noise=None, seed=None, bos_token_id=None, **kwargs):
+        """Next-token sampling of the AR baseline, KV-cached: x[:, 0] = BOS, x0 / x0_unmask conditioning, the fixed prefix prefilled in one causal forward,
+        then one decode step per token; token = argmax(next + Gumbel) (noise [B, L-1, V] replays a recorded draw, otherwise Philox Gumbel from `seed`), or
+        the reference's nucleus_sampling with eval.top_p.  CFG (eval.cfg with x0, eval.force_cfg_value) runs [x ; where(x0_unmask, [MASK], x)] as one
+        batch on one cache.  Returns (x [B, L], nfe) - nfe counts the argmax steps (0 with top_p, the reference's quirk)."""
+        if self.device.type != "cuda":
+            raise NotImplementedError("unidisc_amd.Diffusion: the AR sampler runs on the GPU only (KV-cached decoding in HIP kernels; there is no CPU path)")
+        assert B > 0
+        assert (x0 is None) == (x0_unmask is None)
+        m, ev = cfg_get(self.config, "model"), cfg_get(self.config, "eval", None)
+        cfg_w = cfg_get(ev, "cfg", None)
+        guided = cfg_w is not None and x0 is not None
+        if guided and not cfg_get(ev, "force_cfg_value", False):
+            raise NotImplementedError("unidisc_amd.Diffusion._ar_sampler: eval.cfg without eval.force_cfg_value - the reference's get_cfg_weight indexes a "
+                                      "Python float there, so AR guidance exists only with a constant weight (eval.force_cfg_value=true)")
+        for key in ("cfg_min_timestep", "cfg_max_timestep"):
+            if guided and cfg_get(ev, key, None) is not None:
+                raise NotImplementedError(f"unidisc_amd.Diffusion._ar_sampler: eval.{key} with AR guidance is not built")
+        top_p = cfg_get(ev, "top_p", None)
+        temperature = float(cfg_get(ev, "temperature", 1.0) or 1.0)
+        bos = self._ar_bos_id(bos_token_id)
+        L = int(cfg_get(m, "length"))
+        n_pred = L - 1
+        dev = self.device
+        V, Vt = self.vocab_size, self.text_vocab_size
+        x = torch.zeros((B, L), dtype=torch.int64, device=dev)
+        x[:, 0] = bos
+        if x0 is not None:
+            x0 = x0.to(dev).to(torch.int64).contiguous()
+            x0_unmask = x0_unmask.to(dev).bool().contiguous()
+            x = torch.where(x0_unmask, x0, x)
+        restrict = self._restrict()
+        if modality is None and (restrict or self.backbone.modality_embed is not None or self.backbone.rope_2d):
+            modality = torch.zeros((B, L), dtype=torch.int64, device=dev)
+            modality[:, self.static_img_sl] = 1
+        if modality is not None:
+            modality = modality.to(dev).to(torch.int64).contiguous()
+        if noise is not None:
+            noise = noise.to(dev).to(torch.float32).contiguous()
+            if tuple(noise.shape) != (B, n_pred, V):
+                raise ValueError(f"unidisc_amd.Diffusion._ar_sampler: noise must be [{B}, {n_pred}, {V}], got {tuple(noise.shape)}")
+        R = 2 * B if guided else B
+        bb = self.backbone
+        bb.reset_kv_cache(batch_size=R, seq_len=n_pred, dtype=self.dtype, device=dev,
+                          modality=torch.cat([modality, modality], 0) if (guided and modality is not None) else modality)
+        kv = bb._kv
+        w = torch.full((4,), float(cfg_w) if guided else 0.0, dtype=torch.float32, device=dev)
+        base_seed = int(seed if seed is not None else torch.initial_seed()) & ((1 << 63) - 1)
+        gen = torch.Generator(device=dev).manual_seed(base_seed + 3) if top_p is not None else None
+        logits = kv.logits
+
+        def choose(i):   # token of position i + 1 from kv.logits (the next-token logits of position i); writes x and kv.ids
+            if top_p is None:
+                K.ar_sample_rows(logits, x, i + 1, V, Vt, self.mask_index, step=i, modality=modality, restrict=restrict, g=noise,
+                                 g_col0=i * V, seed=base_seed, x0=x0, x0_unmask=x0_unmask, next_ids=kv.ids,
+                                 logits_u=logits[B:] if guided else None, w=w if guided else None, rows=B)
+                return
+            z = logits[:B, :V].float()
+            if guided:
+                z = (1 + float(cfg_w)) * z - float(cfg_w) * logits[B:2 * B, :V].float()
+            z = z.masked_fill(self._ar_excluded(modality[:, i + 1] if restrict else None), float("-inf"))
+            y = self._ar_nucleus(z, float(top_p), temperature, gen)
+            col = y if x0 is None else torch.where(x0_unmask[:, i + 1], x0[:, i + 1], y)
+            x[:, i + 1] = col
+            kv.ids[:B] = col
+            if guided:
+                kv.ids[B:2 * B] = torch.where(x0_unmask[:, i + 1], torch.full_like(col, self.mask_index), col)
+
+        n0 = self._ar_fixed_prefix(x0_unmask, L)
+        ids0 = x[:, :n0]
+        if guided:
+            ids0 = torch.cat([ids0, torch.where(x0_unmask, self.mask_index, x)[:, :n0]], 0)
+        mod0 = None
+        if modality is not None:
+            mod0 = modality[:, :n0]
+            if guided:
+                mod0 = torch.cat([mod0, mod0], 0)
+        bb._prefill(ids0, mod0, last_only=True)
+        choose(n0 - 1)
+        for i in range(n0, n_pred):
+            bb._decode_step(i)
+            choose(i)
+        bb.reset_kv_cache(batch_size=R, seq_len=n_pred, dtype=self.dtype, device=dev, set_to_none=True)
+        return x, (n_pred if top_p is None else 0)
+
     @torch.no_grad()
     def sample(self, num_steps=None, eps=1e-5, x0=None, x0_unmask=None, batch_size=None, modality=None, sample_ids=None, seed=None, noise=None,
                noise_removal=True, return_nfe=False, predictor=None, replay=None):
@@ -814,9 +942,18 @@ class Diffusion:
         (x0 / x0_unmask conditioning kept fixed), timesteps = linspace(1, eps, steps + 1), one fused update per step with the logits
         cache reused while nothing changes, final arg-max of the log-probs (`noise_removal`).  Returns token ids [B, L]
         (and the number of backbone evaluations).  `noise`: optional list of uniforms [B, L, V] per step (replay of a recorded run)."""
-        if self.parameterization == "ar":
-            raise NotImplementedError("unidisc_amd.Diffusion.sample: the AR sampler (model_eval.py:2736, KV-cached next-token decoding) is not built - "
-                                      "parameterization=ar trains here (compute_loss) and gives log-probs (forward)")
+        if self.parameterization == "ar":   # model_eval.py:2736-2822: one step per token
+            if self.device.type != "cuda":
+                raise NotImplementedError("unidisc_amd.Diffusion: the AR sampler runs on the GPU only (KV-cached decoding in HIP kernels; there is no CPU path)")
+            L_ar = int(cfg_get(cfg_get(self.config, "model"), "length"))
+            for name, v, ok in (("sample_ids", sample_ids, sample_ids is None), ("replay", replay, replay is None),
+                                ("predictor", predictor, predictor in (None, "ar")), ("num_steps", num_steps, num_steps in (None, L_ar - 1))):
+                if not ok:
+                    raise NotImplementedError(f"unidisc_amd.Diffusion.sample: `{name}`={v!r} with parameterization=ar - the AR sampler takes one step per token "
+                                              f"(num_steps = model.length - 1 = {L_ar - 1}), no predictor choice, no replay list and no packed sample ids")
+            B = x0.shape[0] if x0 is not None else int(batch_size)
+            x, nfe = self._ar_sampler(B, x0=x0, x0_unmask=x0_unmask, modality=modality, noise=noise, seed=seed)
+            return (x, nfe) if return_nfe else x
         assert (x0 is None) == (x0_unmask is None)
         sampling = cfg_get(self.config, "sampling", None)
         if num_steps is None:

@@ -17,6 +17,7 @@ Only bf16 compute is implemented (``trainer.precision=bf16``, the reference's tr
 from __future__ import annotations
 
 import math
+import types
 import os
 from typing import Dict, List, Optional
 
@@ -232,10 +233,16 @@ class DIT(nn.Module, _HubMixin):
         self.sandwich_normalization = cfg_get(m, "sandwich_normalization", False)
         self.static_img_sl, self.static_txt_sl = static_img_sl, static_txt_sl
         for flag, why in (("img_cond", "cross-attention image conditioning"), ("cond_label", "class-label conditioning"),
-                          ("use_pretrained_img_emb", "pretrained VQ embedding table"), ("use_kv_cache", "inference KV cache"),
-                          ("use_flex_attention_cache", "inference modality KV cache")):
+                          ("use_pretrained_img_emb", "pretrained VQ embedding table"), ("use_flex_attention_cache", "inference modality KV cache")):
             if cfg_get(m, flag, False):
                 raise NotImplementedError(f"unidisc_amd.DIT: model.{flag} ({why}) is outside the denoising hot path (SURVEY.md §8)")
+        # model.use_kv_cache (models/dit.py:588-607, 776-780, 1462-1473): the AR sampler's per-block K / V cache and its one-token decode step
+        # (reset_kv_cache / forward(start_pos=...)) - a causal cache, so only for causal backbones
+        self.use_kv_cache = bool(cfg_get(m, "use_kv_cache", False))
+        if self.use_kv_cache and cfg_get(m, "full_attention", True):
+            raise NotImplementedError("unidisc_amd.DIT: model.use_kv_cache (inference KV cache) needs a causal backbone (model.full_attention=false, the AR "
+                                      "baseline): a bidirectional block's keys change with every new token")
+        self._kv = None
         # model.full_attention=false (models/dit.py:1118, the AR baseline of configs/experiments/ar.yaml): every block attends causally (sdpa is_causal=True,
         # :768 / :826 / :843) - the attention kernels' UDM_ATTN_CAUSAL form.  The reference never combines it with another mask: an attention_mask beside
         # is_causal is an SDPA error, and the packed / flex-mask paths sit inside `parameterization != "ar"`.
@@ -344,8 +351,144 @@ class DIT(nn.Module, _HubMixin):
     # K / V buffer here and WRITES it in the cache-building / text-only steps (models/dit.py:797-803), but no forward ever reads it back (:812 attends
     # to the keys of the current input only) - so the sampler's three kinds of step need no state in the backbone: `Diffusion.sample` passes the
     # image-queries-see-image-keys mask / the text slice itself.  The two calls are accepted and remembered for callers that probe them.
-    def reset_kv_cache(self, *a, **k):
+    #
+    # With arguments (`_ar_sampler`, model_eval.py:2736-2822) it is the AR baseline's KV cache: per block bf16 K / V [rows, seq_len, d] (rows padded to a
+    # multiple of 8), the decode step's buffers and its rotary rows, allocated once here.  `modality` (extension, full length [batch_size, model.length]):
+    # the decode step at position p then takes its modality-embedding ids and - with 2-D rope - its rotary rows from row p of the FULL-length tables
+    # (the ones training used), so decode step p equals row p of the causal forward.  set_to_none=True frees everything.
+    def reset_kv_cache(self, batch_size=None, seq_len=None, dtype=None, device=None, set_to_none=False, modality=None):
         self.use_flex_attention_cache = False
+        if set_to_none:
+            self._kv = None
+            return
+        if batch_size is None:
+            return
+        if not self.causal:
+            raise NotImplementedError("unidisc_amd.DIT.reset_kv_cache: model.use_kv_cache needs a causal backbone (model.full_attention=false)")
+        if self.time_conditioning:
+            raise NotImplementedError("unidisc_amd.DIT.reset_kv_cache: the decode step has no adaLN (time_conditioning); the AR baseline has no sigma")
+        dev = torch.device(device) if device is not None else self.vocab_embed.embedding.device
+        B, Lmax = int(batch_size), int(seq_len)
+        Bp = _ceil(B, 8)
+        if Bp > K.SKINNY_MAX_ROWS:
+            raise NotImplementedError(f"unidisc_amd.DIT.reset_kv_cache: {B} rows (padded {Bp}); the decode step serves at most {K.SKINNY_MAX_ROWS}")
+        if not 1 <= Lmax <= self.total_length:
+            raise ValueError(f"unidisc_amd.DIT.reset_kv_cache: seq_len {Lmax} outside [1, model.length = {self.total_length}]")
+        self._kv = None
+        self._refresh_shadows_now()
+        d, H, D = self.hidden_size, self.n_heads, self.head_dim
+        Lt = self.total_length
+        kv = types.SimpleNamespace(B=B, Bp=Bp, Lmax=Lmax, pos=0)
+        kv.K = [torch.zeros((Bp, Lmax, d), dtype=BF16, device=dev) for _ in self.blocks]
+        kv.V = [torch.zeros((Bp, Lmax, d), dtype=BF16, device=dev) for _ in self.blocks]
+        kv.ids = torch.zeros(Bp, dtype=torch.int64, device=dev)
+        # the step's buffers: residual stream ping-pong (x -> x_mid -> x), one bf16 norm output, row statistics nobody reads back
+        kv.x = [torch.empty((Bp, d), dtype=F32, device=dev) for _ in range(2)]
+        kv.h = torch.empty((Bp, d), dtype=BF16, device=dev)
+        kv.stat = [torch.empty(Bp, dtype=F32, device=dev) for _ in range(4)]
+        kv.qkr = torch.empty((Bp, 2 * d), dtype=BF16, device=dev)
+        kv.qstats = torch.empty((Bp, 4), dtype=F32, device=dev)
+        kv.qkv = torch.empty((Bp, 3 * d), dtype=BF16, device=dev)
+        kv.o = torch.empty((Bp, d), dtype=BF16, device=dev)
+        kv.a_out = torch.empty((Bp, d), dtype=BF16, device=dev)
+        kv.g = torch.empty((Bp, 4 * d), dtype=BF16, device=dev)
+        kv.u2 = torch.empty((Bp, d), dtype=BF16, device=dev)
+        kv.logits = torch.empty((Bp, self._lins["head"].outp), dtype=BF16, device=dev)
+        need = max(K.skinny_ws_elems(Bp, N, Kd) for N, Kd in ((3 * d, d), (d, d), (4 * d, d), (d, 4 * d), (self.vocab_size, d)))
+        kv.gws = torch.empty(max(need, 4), dtype=F32, device=dev)   # the K splits of the step's five GEMM shapes
+        kv.aws = K.attention_decode_ws(Bp, H, D, dev)
+        mod_full = None
+        if modality is not None:
+            modality = modality.to(dev).to(torch.int64)
+            if tuple(modality.shape) != (B, Lt):
+                raise ValueError(f"unidisc_amd.DIT.reset_kv_cache: modality must be the full-length map [{B}, {Lt}], got {tuple(modality.shape)}")
+            mod_full = torch.cat([modality, modality[:1].expand(Bp - B, Lt)], 0) if Bp > B else modality
+        elif self.modality_embed is not None or self.rope_2d:
+            if self.multimodal_batches:
+                raise ValueError("unidisc_amd.DIT.reset_kv_cache: modality_embed / rope_2d with multimodal_batches need the full-length `modality`")
+            mod_full = self._static_modality(Bp, Lt, dev)
+        kv.mod_full = mod_full
+        kv.mod_cols = mod_full.t().contiguous() if mod_full is not None else None     # [L, Bp]: the embedding's modality ids of position p, contiguous
+        if self.rope_2d:
+            cos, sin = self._rotary(mod_full, Lt)                                        # [Bp, L, D/2], the training tables
+            kv.cos, kv.sin = cos.transpose(0, 1).contiguous(), sin.transpose(0, 1).contiguous()
+        else:
+            kv.cos = kv.sin = None
+        self._kv = kv
+
+    def _refresh_shadows_now(self):
+        """refresh_weight_shadows() for the cached paths, which then read every shadow at once: a recast it queued on the side stream (UDM_OVERLAP_CAST)
+        is awaited here, before any decode or prefill launch."""
+        self.refresh_weight_shadows()
+        for key in list(getattr(self, "_cast_events", {})):
+            self._await_cast(key)
+
+    def _rope_rows(self, p):
+        """rotary rows of decode position p: (cos, sin) with the qk-norm + rope kernel's table form (a one-row table, or [1, Bp, D/2] per row)"""
+        kv = self._kv
+        if kv.cos is None:
+            return self.rotary_cos_emb[p:p + 1], self.rotary_sin_emb[p:p + 1]
+        return kv.cos[p][None], kv.sin[p][None]
+
+    @torch.no_grad()
+    def _decode_step(self, p):
+        """One token per cached row at position p (the ids in self._kv.ids) -> logits [Bp, Vp] bf16 (self._kv.logits).  Engine path without autograd or host
+        synchronisation: norm, skinny qkv, qk-norm + rope (row p of the full-length tables), decode attention (appends k / v at slot p), skinny out-proj,
+        residual + norm, skinny up + GELU, skinny down, residual (+ the next block's norm), head."""
+        kv, lin = self._kv, self._lins
+        d, H, D = self.hidden_size, self.n_heads, self.head_dim
+        nt = K.norm_id(self.norm_type)
+        sw = self.sandwich_normalization
+        emb_mod = kv.mod_cols[p] if (self.modality_embed is not None) else None
+        xa, xb = kv.x
+        st = kv.stat
+        K.embedding_fwd(kv.ids, self.vocab_embed.embedding.detach(), emb_mod, self.modality_embed.embedding.detach() if self.modality_embed is not None else None,
+                        out=xa)
+        cos, sin = self._rope_rows(p)
+        res_out = (None, st[0], st[1], kv.h, st[2], st[3])
+        for i, blk in enumerate(self.blocks):
+            if i == 0:
+                K.norm_fwd(xa, blk.norm1.weight.detach(), nt, 1, out=(kv.h, st[2], st[3]))
+            qkv = K.gemm_skinny(kv.h, lin[f"{i}.qkv"].w16, out=kv.qkv, N=3 * d, ws=kv.gws)
+            at = blk.attention
+            qn_kw = dict(gq=at.q_norm.weight.detach(), bq=at.q_norm.bias.detach(), gk=at.k_norm.weight.detach(), bk=at.k_norm.bias.detach()) if self.qk_norm else {}
+            qkr, _ = K.qknorm_rope_fwd(qkv, cos, sin, 1, D, q_scale=self.attn_q_scale, out=(kv.qkr, kv.qstats), **qn_kw)
+            o = K.attention_decode(qkr[:, :d], qkr[:, d:], qkv[:, 2 * d:], kv.K[i], kv.V[i], p, H, D, out=kv.o, ws=kv.aws)
+            a_out = K.gemm_skinny(o, lin[f"{i}.out"].w16, out=kv.a_out, N=d, ws=kv.gws)
+            K.residual_fwd(xa, a_out, 1, w_b=blk.pre_residual_norm.weight.detach() if sw else None, norm_type=nt, next_w=blk.norm2.weight.detach(),
+                           out=(xb,) + res_out[1:])
+            f1, f2 = lin[f"{i}.fc1"], lin[f"{i}.fc2"]
+            g = K.gemm_skinny(kv.h, f1.w16, out=kv.g, N=4 * d, epilogue=K.EPI_BIAS_GELU, bias=f1.bias.detach(), ws=kv.gws)
+            u2 = K.gemm_skinny(g, f2.w16, out=kv.u2, N=d, epilogue=K.EPI_BIAS, bias=f2.bias.detach(), ws=kv.gws)
+            nxt_w = (self.blocks[i + 1].norm1.weight if i + 1 < self.n_blocks else self.output_layer.norm_final.weight).detach()
+            K.residual_fwd(xb, u2, 1, w_b=blk.post_ff_norm.weight.detach() if sw else None, norm_type=nt, next_w=nxt_w, out=(xa,) + res_out[1:])
+        head = lin["head"]
+        K.gemm_skinny(kv.h, head.w16, out=kv.logits, N=self.vocab_size, epilogue=K.EPI_BIAS, bias=head.bias.detach(), ws=kv.gws)
+        kv.pos = p + 1
+        return kv.logits
+
+    @torch.no_grad()
+    def _prefill(self, ids, modality=None, last_only=False):
+        """start_pos = 0 over n >= 1 tokens of every cached row: the causal forward (rotary rows 0..n-1 of the full-length tables) that leaves each block's
+        post-rope k and v in cache slots [0, n).  ids / modality [B, n] with B <= the cached rows (padded with row 0).  Returns logits [B, n, V], or with
+        last_only the logits of position n - 1 in self._kv.logits [Bp, Vp]."""
+        kv = self._kv
+        B, n = ids.shape
+        if n > kv.Lmax:
+            raise ValueError(f"unidisc_amd.DIT: prefill of {n} tokens into a cache of {kv.Lmax}")
+        Bp = kv.Bp
+        pad = lambda t: torch.cat([t, t[:1].expand(Bp - B, *t.shape[1:])], 0) if (t is not None and Bp > B) else t   # noqa: E731
+        idsp = pad(ids.to(torch.int64)).contiguous()
+        mod = modality.to(torch.int64) if modality is not None else (kv.mod_full[:B, :n] if kv.mod_full is not None else None)
+        modp = pad(mod).contiguous() if mod is not None else None
+        rope = None
+        if kv.cos is not None:
+            rope = (kv.cos[:n].transpose(0, 1).contiguous(), kv.sin[:n].transpose(0, 1).contiguous())
+        inputs = dict(indices=idsp, sigma=None, modality=modp, sample_ids=None, x0=None, save=False, block_mask=None, key_mask=None,
+                      kv_sink=list(zip(kv.K, kv.V)), rope=rope, head_out=kv.logits if last_only else None)
+        out, _ = self._engine_forward(inputs, "logits", save=False)
+        kv.pos = n
+        return out if last_only else out[:B]
 
     def set_flex_attention_cache(self, batch_size=None, seq_len=None, device=None, dtype=None):
         self.use_flex_attention_cache = True
@@ -479,11 +622,41 @@ class DIT(nn.Module, _HubMixin):
     def forward(self, indices, sigma=None, label=None, x_cond=None, attention_mask=None, continuous_mode=False, x_img_emb=None, modality=None,
                 start_pos=None, block_mask=None, update_cache_slice=None, sample_ids=None):
         """→ logits [B, L, V] (bf16).  Signature of the reference's DIT.forward (models/dit.py:1324-1338)."""
-        self._check_unsupported(label, x_cond, None, continuous_mode, x_img_emb, start_pos, block_mask, update_cache_slice, sample_ids)
+        self._check_unsupported(label, x_cond, None, continuous_mode, x_img_emb, None, block_mask, update_cache_slice, sample_ids)
+        if start_pos is not None:
+            return self._forward_cached(indices, modality, int(start_pos), attention_mask, block_mask)
         params = self._ordered_params()
         inputs = dict(indices=indices, sigma=sigma, modality=modality, sample_ids=sample_ids, x0=None, save=self._needs_grad(params),
                       block_mask=block_mask if isinstance(block_mask, ModalityMask) else None, key_mask=self._key_mask(attention_mask, indices))
         return _DitFn.apply(self, "logits", inputs, *params)
+
+    @torch.no_grad()
+    def _forward_cached(self, indices, modality, start_pos, attention_mask, block_mask):
+        """forward(start_pos=p) on the KV cache (reset_kv_cache first): one token per row at p (decode step, logits [B, 1, V]) or n >= 1 tokens at p = 0
+        (prefill, logits [B, n, V]).  Anything else - several tokens at p > 0 (chunked prefill) - is not built."""
+        if self._kv is None:
+            raise RuntimeError("unidisc_amd.DIT.forward(start_pos=...): no KV cache - call reset_kv_cache(batch_size, seq_len, ...) first")
+        if attention_mask is not None or (block_mask is not None and block_mask is not True):
+            raise NotImplementedError("unidisc_amd.DIT.forward(start_pos=...): the KV-cached forward takes no attention_mask / block_mask")
+        kv = self._kv
+        B, n = indices.shape
+        if B > kv.B:
+            raise ValueError(f"unidisc_amd.DIT.forward(start_pos=...): {B} rows, the cache holds {kv.B}")
+        if start_pos == 0:
+            K.require_gpu(indices)
+            return self._prefill(indices, modality)
+        if n != 1:
+            raise NotImplementedError(f"unidisc_amd.DIT.forward: start_pos={start_pos} with {n} tokens (multi-token decode / chunked prefill) is not built - "
+                                      "start_pos=0 prefills, start_pos=p > 0 takes one token per row")
+        if not 0 < start_pos < kv.Lmax:
+            raise ValueError(f"unidisc_amd.DIT.forward: start_pos={start_pos} outside the cache [0, {kv.Lmax})")
+        K.require_gpu(indices)
+        self._refresh_shadows_now()
+        kv.ids[:B].copy_(indices[:, 0])
+        if modality is not None and kv.mod_cols is not None:   # (the step's own modality column, when given, for the embedding)
+            kv.mod_cols[start_pos, :B].copy_(modality[:, 0])
+        logits = self._decode_step(start_pos)
+        return logits[:B, :self.vocab_size].view(B, 1, self.vocab_size)
 
     @staticmethod
     def _key_mask(attention_mask, indices):
@@ -705,9 +878,12 @@ class DIT(nn.Module, _HubMixin):
             tab = torch.cat([self.img_count_embedding.detach().to(x.dtype), torch.zeros((1, x.shape[1]), dtype=x.dtype, device=x.device)], 0)
             x.add_(tab.index_select(0, cnt_j))
             S["cnt_j"] = cnt_j
+        elif inp.get("rope") is not None:   # (KV-cache prefill: rows of the full-length tables)
+            cos, sin = inp["rope"]
         else:
             cos, sin = self._rotary(modality, L)
         S["cos"], S["sin"] = cos, sin
+        kv_sink = inp.get("kv_sink")
 
         any_img = None
         if tc:
@@ -760,6 +936,9 @@ class DIT(nn.Module, _HubMixin):
             qn_kw = dict(gq=at.q_norm.weight.detach() if self.qk_norm else None, bq=at.q_norm.bias.detach() if self.qk_norm else None,
                          gk=at.k_norm.weight.detach() if self.qk_norm else None, bk=at.k_norm.bias.detach() if self.qk_norm else None)
             qkr, qstats = K.qknorm_rope_fwd(qkv, cos, sin, L, D, q_scale=self.attn_q_scale, **qn_kw)
+            if kv_sink is not None:   # KV-cache prefill: the post-rope k and the v of every position into cache slots [0, L)
+                kv_sink[i][0][:, :L].copy_(qkr.view(B, L, 2 * d)[:, :, d:])
+                kv_sink[i][1][:, :L].copy_(qkv.view(B, L, 3 * d)[:, :, 2 * d:])
             o, lse = K.attention_fwd(qkr, qkv, B, L, H, D, sid, S["doc_ranges"], q_prescaled=True, **self._attn_mask_kw)
             rows_c = last_rows
             if not recompute and i + 1 == self.n_blocks and head_plan is not None and mode == "logp" and self.compact_last_block and not tc:
@@ -832,6 +1011,10 @@ class DIT(nn.Module, _HubMixin):
             logits = torch.empty((hf_h.shape[0], Vp), dtype=BF16, device=dev)
             K.gemm_nt(hf_h, head.w16, out=logits, N=V, epilogue=K.EPI_BIAS, bias=head.bias.detach())
             return (logits, rows_p, n_masked), S
+        if mode == "logits" and inp.get("head_out") is not None:   # (KV-cache prefill: the head on each row's last position only)
+            last = torch.arange(B, device=dev) * L + (L - 1)
+            K.gemm_nt(hf.index_select(0, last), head.w16, out=inp["head_out"], N=V, epilogue=K.EPI_BIAS, bias=head.bias.detach())
+            return inp["head_out"], S
         if mode == "logits":
             logits = torch.empty((M, Vp), dtype=BF16, device=dev)
             K.gemm_nt(hf, head.w16, out=logits, N=V, epilogue=K.EPI_BIAS, bias=head.bias.detach())

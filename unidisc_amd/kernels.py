@@ -602,12 +602,15 @@ def _mod_ptrs(mod, idx, d):
     return [mod.data_ptr() + es * k * d for k in idx], mod.stride(0)
 
 
-def norm_fwd(x, w, norm_type, L, *, mod=None, mod_idx=(0, 1), modality=None, any_img=None):
-    """y = modulate(norm(x) * w) -> bf16.  mod_idx = (shift chunk, scale chunk) of the adaLN output."""
+def norm_fwd(x, w, norm_type, L, *, mod=None, mod_idx=(0, 1), modality=None, any_img=None, out=None):
+    """y = modulate(norm(x) * w) -> bf16.  mod_idx = (shift chunk, scale chunk) of the adaLN output.  out: caller's (y, rstd, mean) buffers."""
     M, d = x.shape
-    y = torch.empty((M, d), dtype=BF16, device=x.device)
-    rstd = torch.empty(M, dtype=F32, device=x.device)
-    mean = torch.empty(M, dtype=F32, device=x.device) if norm_type == NORM_LN else None
+    if out is not None:
+        y, rstd, mean = out
+    else:
+        y = torch.empty((M, d), dtype=BF16, device=x.device)
+        rstd = torch.empty(M, dtype=F32, device=x.device)
+        mean = torch.empty(M, dtype=F32, device=x.device) if norm_type == NORM_LN else None
     (shift, scale), ms = _mod_ptrs(mod, mod_idx, d)
     _lib.call("udm_norm_fwd", _p(x), _p(y), _p(rstd), _p(mean), _p(w), shift, scale, ms, _p(modality) if mod is not None else None,
               _p(any_img) if mod is not None else None, M, d, L, norm_type, 1e-6 if norm_type == NORM_RMS else 1e-5, _s())
@@ -626,23 +629,33 @@ def norm_bwd(dy, x, rstd, mean, w, norm_type, L, dx, dw, *, accumulate=True, mod
 
 
 def residual_fwd(x_in, branch, L, *, w_b=None, norm_type=NORM_RMS, mod=None, gate_idx=None, modality=None, p_drop=0.0, seed=0, next_w=None, next_mod=None,
-                 next_mod_idx=(0, 1), next_modality=None, next_any_img=None):
+                 next_mod_idx=(0, 1), next_modality=None, next_any_img=None, out=None):
     """x_out = x_in + gate * dropout(sandwich_norm(branch)).  gate = chunk gate_idx of `mod` (None: no gate).
     next_w: weight of the norm that consumes x_out next -- fused; returns (x_out, rstd, mean, (h, rstd_n, mean_n)).  next_mod: that norm is modulated by chunks
-    next_mod_idx = (shift, scale) of this adaLN tensor (image rows only under next_modality / next_any_img, as norm_fwd)."""
+    next_mod_idx = (shift, scale) of this adaLN tensor (image rows only under next_modality / next_any_img, as norm_fwd).
+    out: caller's buffers (x_out, rstd, mean, h, rstd_n, mean_n) - the unneeded ones may be None."""
     M, d = x_in.shape
-    x_out = torch.empty_like(x_in)
-    rstd = torch.empty(M, dtype=F32, device=x_in.device) if w_b is not None else None
-    mean = torch.empty(M, dtype=F32, device=x_in.device) if (w_b is not None and norm_type == NORM_LN) else None
+    if out is not None:
+        x_out, rstd, mean = out[:3]
+        rstd = rstd if w_b is not None else None
+        mean = mean if (w_b is not None and norm_type == NORM_LN) else None
+    else:
+        x_out = torch.empty_like(x_in)
+        rstd = torch.empty(M, dtype=F32, device=x_in.device) if w_b is not None else None
+        mean = torch.empty(M, dtype=F32, device=x_in.device) if (w_b is not None and norm_type == NORM_LN) else None
     (gate,), ms = _mod_ptrs(mod if gate_idx is not None else None, (gate_idx,), d)
     eps = 1e-6 if norm_type == NORM_RMS else 1e-5
     if next_w is None:
         _lib.call("udm_residual_fwd", _p(x_in), _p(branch), _p(x_out), _p(w_b), _p(rstd), _p(mean), gate, ms, _p(modality), M, d, L, norm_type,
                   eps, float(p_drop), int(seed), _s())
         return x_out, rstd, mean
-    h = torch.empty((M, d), dtype=BF16, device=x_in.device)
-    rstd_n = torch.empty(M, dtype=F32, device=x_in.device)
-    mean_n = torch.empty(M, dtype=F32, device=x_in.device) if norm_type == NORM_LN else None
+    if out is not None:
+        h, rstd_n, mean_n = out[3:]
+        mean_n = mean_n if norm_type == NORM_LN else None
+    else:
+        h = torch.empty((M, d), dtype=BF16, device=x_in.device)
+        rstd_n = torch.empty(M, dtype=F32, device=x_in.device)
+        mean_n = torch.empty(M, dtype=F32, device=x_in.device) if norm_type == NORM_LN else None
     if next_mod is not None:
         (n_shift, n_scale), n_ms = _mod_ptrs(next_mod, next_mod_idx, d)
         _lib.call("udm_residual_norm_fwd_ada", _p(x_in), _p(branch), _p(x_out), _p(w_b), _p(rstd), _p(mean), gate, ms, _p(modality), M, d, L, norm_type,
@@ -724,12 +737,16 @@ def attention_q_scale(D):
     return 1.4426950408889634 / math.sqrt(D)
 
 
-def qknorm_rope_fwd(qkv, cos, sin, L, D, *, gq=None, bq=None, gk=None, bk=None, q_scale=1.0):
-    """qkv bf16 [M, 3d] -> qkr bf16 [M, 2d] (normalised + rotated q | k), LayerNorm statistics.  q_scale != 1: the q half holds bf16(q * q_scale) (one rounding)."""
+def qknorm_rope_fwd(qkv, cos, sin, L, D, *, gq=None, bq=None, gk=None, bk=None, q_scale=1.0, out=None):
+    """qkv bf16 [M, 3d] -> qkr bf16 [M, 2d] (normalised + rotated q | k), LayerNorm statistics.  q_scale != 1: the q half holds bf16(q * q_scale) (one rounding).
+    out: caller's (qkr, stats) buffers."""
     M, d3 = qkv.shape
     d = d3 // 3
-    qkr = torch.empty((M, 2 * d), dtype=BF16, device=qkv.device)
-    stats = torch.empty((M, 4), dtype=F32, device=qkv.device) if gq is not None else None
+    if out is not None:
+        qkr, stats = out[0], (out[1] if gq is not None else None)
+    else:
+        qkr = torch.empty((M, 2 * d), dtype=BF16, device=qkv.device)
+        stats = torch.empty((M, 4), dtype=F32, device=qkv.device) if gq is not None else None
     per_sample = 1 if cos.dim() == 3 else 0
     _lib.call("udm_qknorm_rope_fwd", _p(qkv), _p(qkr), _p(gq), _p(bq), _p(gk), _p(bk), _p(stats), _p(cos), _p(sin), per_sample, M, d, L, D, 1e-5, float(q_scale), _s())
     return qkr, stats
@@ -840,10 +857,10 @@ def set_attention_dkv64(enable):
 
 
 # ------------------------------------------------------------------------------------------------ embedding / CE / adaLN helpers
-def embedding_fwd(ids, E, modality=None, Em=None):
+def embedding_fwd(ids, E, modality=None, Em=None, out=None):
     M = ids.numel()
     V, d = E.shape
-    x = torch.empty((M, d), dtype=F32, device=E.device)
+    x = torch.empty((M, d), dtype=F32, device=E.device) if out is None else out
     _lib.call("udm_embedding_fwd", _p(ids), _p(E), _p(modality), _p(Em), _p(x), M, d, V, _s())
     return x
 
@@ -910,3 +927,70 @@ def silu_bwd(x, dy):
     dx = torch.empty_like(x)
     _lib.call("udm_silu_bwd", _p(x), _p(dy), _p(dx), x.numel(), _s())
     return dx
+
+
+# ------------------------------------------------------------------------------------------------ KV-cached AR decoding (csrc/decode.hip)
+SKINNY_MAX_ROWS = 64
+
+
+def gemm_skinny(a, w, out=None, *, N=None, epilogue=EPI_NONE, bias=None, out_dtype=BF16, ws=None):
+    """out[M, N] = a[M, K] @ w[N, K]^T (+ bias, + GELU) for M <= 64 rows: the weight-streaming GEMM of a decode step.  `w` is a bf16 weight shadow
+    (its padded rows past N are never read); ws: fp32 scratch for the K split (None: the per-device scratch, grown to what this shape's split needs)."""
+    _chk(a, BF16, "gemm_skinny a"), _chk(w, BF16, "gemm_skinny w")
+    M, K = a.shape
+    N = w.shape[0] if N is None else N
+    if out is None:
+        out = torch.empty((M, N), dtype=out_dtype, device=a.device)
+    if ws is None:
+        need = skinny_ws_elems(M, N, K)
+        ws = _scratch(need, a.device) if need else None
+    _lib.call("udm_gemm_skinny_bf16", _p(a), _p(w), _p(out), M, N, K, a.stride(0), w.stride(0), out.stride(0), 1 if out.dtype == F32 else 0, epilogue, _p(bias),
+              _p(ws), ws.numel() if ws is not None else 0, _s())
+    return out
+
+
+def skinny_ws_elems(M, N, K):
+    """fp32 elements udm_gemm_skinny_bf16 uses for its K split of this shape (its split plan: about two workgroups of 32 columns per CU, slices of at least 128
+    deep, at most 32), 0 when it does not split."""
+    nblk = -(-N // 32)
+    if nblk >= 512:
+        return 0
+    S = min(max((512 + nblk // 2) // nblk, 1), K // 128, 32)
+    return S * M * N if S > 1 else 0   # (the slices it then plans never exceed S)
+
+
+def attention_decode_ws(B, H, D, device):
+    """fp32 split scratch of udm_attention_decode: (D + 2) floats per (row, head, split), 32 splits."""
+    return torch.empty(B * H * 32 * (D + 2), dtype=F32, device=device)
+
+
+def attention_decode(q, k_new, v_new, k_cache, v_cache, p, H, D, out=None, ws=None):
+    """o [B, H D] bf16 of one new token per row at position p against the caches [B, Lmax, H D] (q pre-scaled by attention_q_scale(D)); writes k_new / v_new
+    into cache slot p.  q / k_new / v_new / out: 2-D row views (any 16-byte aligned row stride)."""
+    B, Lmax, d = k_cache.shape
+    if out is None:
+        out = torch.empty((B, d), dtype=BF16, device=q.device)
+    _lib.call("udm_attention_decode", _p(q), _p(k_new), _p(v_new), _p(k_cache), _p(v_cache), _p(out), _p(ws), ws.numel() if ws is not None else 0, B, H, D, Lmax,
+              int(p), q.stride(0), k_new.stride(0), v_new.stride(0), out.stride(0), _s())
+    return out
+
+
+def ar_sample_rows(logits, x, pos, V, Vt, mask_id, *, step=0, modality=None, restrict=False, g=None, g_col0=0, seed=0, x0=None, x0_unmask=None,
+                   next_ids=None, logits_u=None, w=None, rows=None):
+    """x[r, pos] = argmax(z + Gumbel) for r < rows (default: every row of x), z = logits[r] (or (1 + w) logits[r] - w logits_u[r]) with [MASK] and, with
+    restrict, the other modality than modality[r, pos] excluded; the x0 write-back applied.  g: explicit noise [rows, ldg] fp32 read at column g_col0 + id."""
+    _chk(logits, BF16, "ar_sample_rows logits")
+    R = x.shape[0] if rows is None else rows
+    if (logits_u is None) != (w is None):
+        raise ValueError("ar_sample_rows: guidance needs both logits_u and w")
+    if logits_u is not None and logits_u.stride(0) != logits.stride(0):
+        raise ValueError("ar_sample_rows: logits_u must have the row stride of logits")
+    for t, name in ((x, "x"), (x0, "x0"), (modality, "modality")):
+        if t is not None and (t.dtype != torch.int64 or t.stride(-1) != 1):
+            raise TypeError(f"ar_sample_rows: {name} must be int64 with contiguous rows")
+    if x0_unmask is not None and (x0_unmask.dtype != torch.bool or x0_unmask.stride(0) != x.stride(0) or x0.stride(0) != x.stride(0)):
+        raise TypeError("ar_sample_rows: x0 / x0_unmask must be laid out like x (bool mask)")
+    _lib.call("udm_ar_sample_rows", _p(logits), _p(logits_u), _p(w), logits.stride(0), _p(modality), modality.stride(0) if modality is not None else 0, _p(g),
+              g.stride(0) if g is not None else 0, int(g_col0), int(seed), int(step), _p(x), x.stride(0), _p(x0), _p(x0_unmask), int(pos), _p(next_ids), R, V, Vt,
+              mask_id, 1 if restrict else 0, _s())
+    return x
