@@ -28,7 +28,7 @@ extern "C" {
 typedef struct ihipStream_t* hipStream_t;
 #endif
 
-#define UDM_ABI_VERSION 3
+#define UDM_ABI_VERSION 4
 
 /* GEMM epilogues */
 #define UDM_EPI_NONE 0      /* C = A·Bᵀ                                                   */
@@ -279,28 +279,29 @@ int udm_sample_t_noise(const float* u, int64_t n, int antithetic, float sampling
  * fp32 masters and moments; `step` is the 1-based update count (bias corrections are computed from it); `grad_norm_sq` (nullable) is a DEVICE
  * scalar holding the sum of squares of ALL gradients (udm_sumsq_f32 over the engine's flat gradient buffer): g is scaled by
  * min(1, max_grad_norm / (sqrt(*grad_norm_sq) + 1e-6)) without a host round trip.  The _shadow form updates a row-major [R, C] GEMM weight and
- * writes its bf16 copy [R, ld16] and transposed bf16 copy [C, ldt] in the same pass (replaces the per-forward autocast weight cast). */
+ * writes its bf16 copy [R, ld16] and transposed bf16 copy [C, ldt] in the same pass (replaces the per-forward autocast weight cast).
+ * The betas are doubles (ABI 4), as in torch: 1 - beta and the bias corrections are formed in double and rounded once (1 - (float)0.999 is 1.3e-5 off 0.001). */
 int udm_sumsq_f32(const float* x, int64_t n, float* out, float* ws, int64_t ws_elems, hipStream_t stream); /* ws: >= 1024 floats */
-int udm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+int udm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps, float weight_decay,
                    int64_t step, const float* grad_norm_sq, float max_grad_norm, hipStream_t stream);
-int udm_adamw_step_shadow(float* p, const float* g, float* m, float* v, int64_t R, int64_t C, float lr, float beta1, float beta2, float eps,
+int udm_adamw_step_shadow(float* p, const float* g, float* m, float* v, int64_t R, int64_t C, float lr, double beta1, double beta2, float eps,
                           float weight_decay, int64_t step, const float* grad_norm_sq, float max_grad_norm, void* w16, int64_t ld16, void* w16t,
                           int64_t ldt, hipStream_t stream);
 /* The same updates with the parameter EMA of models/ema.py:44-53 (`ExponentialMovingAverage.update`, called after optimizer.step at model.py:1541-1545)
  * folded into the pass: ema <- ema - (1 - ema_decay) (ema - p_new).  `ema_decay` is the decay OF THIS UPDATE (the caller applies the reference's
  * warm-up min(decay, (1 + n) / (10 + n))).  ema NULL: identical to the plain forms. */
-int udm_adamw_step_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+int udm_adamw_step_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps, float weight_decay,
                        int64_t step, const float* grad_norm_sq, float max_grad_norm, float* ema, float ema_decay, hipStream_t stream);
 /* the same update for MANY flat tensors in one launch: `jobs` = device array of njobs records {float* p; const float* g; float* m; float* v; float* ema (nullable);
  * int64 n; int64 chunk0} with chunk0 = sum over the earlier jobs of ceil(n / 1024) and nchunks the total; every pointer 16-byte aligned. */
-int udm_adamw_step_multi(const void* jobs, int64_t njobs, int64_t nchunks, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
+int udm_adamw_step_multi(const void* jobs, int64_t njobs, int64_t nchunks, float lr, double beta1, double beta2, float eps, float weight_decay, int64_t step,
                          const float* grad_norm_sq, float max_grad_norm, float ema_decay, hipStream_t stream);
 /* ... and for MANY 2-D GEMM weights with their bf16 shadows: `jobs` = device array of records {float* p; const float* g; float* m; float* v; float* ema (nullable);
  * bf16* w16 (nullable); bf16* w16t (nullable); int64 ld16; int64 ldt; int32 R; int32 C; int32 tile0; int32 tiles_c} with tiles_c = ceil(C / 64) and tile0 = sum over
  * the earlier jobs of ceil(R / 64) * tiles_c; ntiles the total. */
-int udm_adamw_step_shadow_multi(const void* jobs, int64_t njobs, int64_t ntiles, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
+int udm_adamw_step_shadow_multi(const void* jobs, int64_t njobs, int64_t ntiles, float lr, double beta1, double beta2, float eps, float weight_decay, int64_t step,
                                 const float* grad_norm_sq, float max_grad_norm, float ema_decay, hipStream_t stream);
-int udm_adamw_step_shadow_ema(float* p, const float* g, float* m, float* v, int64_t R, int64_t C, float lr, float beta1, float beta2, float eps,
+int udm_adamw_step_shadow_ema(float* p, const float* g, float* m, float* v, int64_t R, int64_t C, float lr, double beta1, double beta2, float eps,
                               float weight_decay, int64_t step, const float* grad_norm_sq, float max_grad_norm, void* w16, int64_t ld16, void* w16t,
                               int64_t ldt, float* ema, float ema_decay, hipStream_t stream);
 

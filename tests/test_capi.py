@@ -33,7 +33,7 @@ def test_header_symbols_exported(lib):
     nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = {ln.split()[-1] for ln in nm.splitlines() if " T " in ln and ln.split()[-1].startswith("udm_")}
     assert exported == declared, (sorted(exported - declared), sorted(declared - exported))
-    assert lib.udm_abi_version() == _lib.ABI_VERSION == 3
+    assert lib.udm_abi_version() == _lib.ABI_VERSION == 4
 
 
 def test_prototype_arity_matches_header(lib):
@@ -46,6 +46,23 @@ def test_prototype_arity_matches_header(lib):
         assert m, name
         n = len([a for a in m.group(1).split(",") if a.strip() and a.strip() != "void"])
         assert n == len(args), (name, n, len(args))
+
+
+def test_prototype_doubles_match_header(lib):
+    """a float bound where the header says double (or the reverse) shifts no argument but passes garbage: the AdamW betas are doubles since ABI 4"""
+    import ctypes
+
+    from unidisc_amd import _lib
+
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "unidisc_hip.h")).read(), flags=re.S)
+    seen = 0
+    for name, args in _lib.PROTOTYPES.items():
+        params = [a.strip() for a in re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", header, flags=re.S).group(1).split(",")]
+        for decl, ct in zip(params, args):
+            assert (decl.startswith("double ")) == (ct is ctypes.c_double), (name, decl, ct)
+            assert (decl.startswith("float ")) == (ct is ctypes.c_float), (name, decl, ct)
+            seen += decl.startswith("double ")
+    assert seen == 12      # beta1, beta2 of the six udm_adamw_step* entry points
 
 
 def test_no_cpu_fallback():

@@ -10,13 +10,13 @@ from __future__ import annotations
 import ctypes
 import os
 import subprocess
-from ctypes import c_float, c_int, c_int64, c_uint64, c_void_p
+from ctypes import c_double, c_float, c_int, c_int64, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libunidisc_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 
-_P, _I64, _I, _F, _U64 = c_void_p, c_int64, c_int, c_float, c_uint64
+_P, _I64, _I, _F, _U64, _D = c_void_p, c_int64, c_int, c_float, c_uint64, c_double
 
 # name -> argument ctypes (the trailing hipStream_t is a pointer); must mirror include/unidisc_hip.h exactly
 PROTOTYPES = {
@@ -63,12 +63,12 @@ PROTOTYPES = {
     "udm_ddpm_sample_rows_cfg": [_P, _P, _P, _I64, _P, _P, _P, _P, _I64, _U64, _P, _I64, _I64, _I64, _I64, _I, _I, _P],
     "udm_ddpm_sample_rows": [_P, _I64, _P, _P, _P, _P, _I64, _U64, _P, _I64, _I64, _I64, _I64, _I, _I, _P],
     "udm_sumsq_f32": [_P, _I64, _P, _P, _I64, _P],
-    "udm_adamw_step_ema": [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _I64, _P, _F, _P, _F, _P],
-    "udm_adamw_step_shadow_ema": [_P, _P, _P, _P, _I64, _I64, _F, _F, _F, _F, _F, _I64, _P, _F, _P, _I64, _P, _I64, _P, _F, _P],
-    "udm_adamw_step_shadow_multi": [_P, _I64, _I64, _F, _F, _F, _F, _F, _I64, _P, _F, _F, _P],
-    "udm_adamw_step_multi": [_P, _I64, _I64, _F, _F, _F, _F, _F, _I64, _P, _F, _F, _P],
-    "udm_adamw_step": [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _I64, _P, _F, _P],
-    "udm_adamw_step_shadow": [_P, _P, _P, _P, _I64, _I64, _F, _F, _F, _F, _F, _I64, _P, _F, _P, _I64, _P, _I64, _P],
+    "udm_adamw_step_ema": [_P, _P, _P, _P, _I64, _F, _D, _D, _F, _F, _I64, _P, _F, _P, _F, _P],
+    "udm_adamw_step_shadow_ema": [_P, _P, _P, _P, _I64, _I64, _F, _D, _D, _F, _F, _I64, _P, _F, _P, _I64, _P, _I64, _P, _F, _P],
+    "udm_adamw_step_shadow_multi": [_P, _I64, _I64, _F, _D, _D, _F, _F, _I64, _P, _F, _F, _P],
+    "udm_adamw_step_multi": [_P, _I64, _I64, _F, _D, _D, _F, _F, _I64, _P, _F, _F, _P],
+    "udm_adamw_step": [_P, _P, _P, _P, _I64, _F, _D, _D, _F, _F, _I64, _P, _F, _P],
+    "udm_adamw_step_shadow": [_P, _P, _P, _P, _I64, _I64, _F, _D, _D, _F, _F, _I64, _P, _F, _P, _I64, _P, _I64, _P],
     "udm_embedding_fwd": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P],
     "udm_embedding_bwd": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
     "udm_subs_ce_fwd": [_P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P],
@@ -83,7 +83,7 @@ PROTOTYPES = {
     "udm_ar_sample_rows": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _U64, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I, _P],
 }
 EXTRA_SYMBOLS = ["udm_last_error", "udm_abi_version"]
-ABI_VERSION = 3   # the UDM_ABI_VERSION of include/unidisc_hip.h that PROTOTYPES was written for (bumped whenever a signature changes)
+ABI_VERSION = 4   # the UDM_ABI_VERSION of include/unidisc_hip.h that PROTOTYPES was written for (bumped whenever a signature changes)
 
 _lib = None
 

@@ -15,13 +15,15 @@
 #include "../../include/unidisc_hip.h"
 
 #include <math.h>
+#include <stddef.h>
 
 namespace {
 using namespace udm;
 
 struct AdamArgs {
   float* p; const float* g; float* m; float* v;
-  float lr, b1, b2, eps, decay, bc1, rsqrt_bc2;   // decay = 1 - lr * wd; bc1 = 1 - b1^t; rsqrt_bc2 = 1 / sqrt(1 - b2^t)
+  float lr, omb1, b2, omb2, eps, decay, bc1, rsqrt_bc2;   // omb = 1 - beta (*); decay = 1 - lr * wd; bc1 = 1 - b1^t (*); rsqrt_bc2 = 1 / sqrt(1 - b2^t) (*)
+                                                          // (*) computed on the host in double from the double betas: 1.f - 0.999f is 1.3e-5 away from 1 - 0.999
   const float* gnorm_sq;                          // nullable: sum of squares of ALL gradients (device scalar)
   float max_norm;
   float* ema;                                     // nullable: exponential moving average of p (models/ema.py:44-53), updated in the same pass
@@ -40,8 +42,8 @@ __device__ __forceinline__ float clip_coef(const AdamArgs& a) {
 }
 __device__ __forceinline__ float adam_update(const AdamArgs& a, float p, float g, float& m, float& v) {
   p *= a.decay;
-  m = m + (1.f - a.b1) * (g - m);
-  v = a.b2 * v + (1.f - a.b2) * g * g;
+  m = m + a.omb1 * (g - m);
+  v = a.b2 * v + a.omb2 * g * g;
   const float denom = sqrtf(v) * a.rsqrt_bc2 + a.eps;
   return p - (a.lr / a.bc1) * (m / denom);
 }
@@ -73,6 +75,10 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a, long n) {
 // every flat parameter of a model in ONE launch (a 1.4 B DiT has ~250 norm / bias / embedding tensors: one launch each is ~250 x (launch + a wave of idle CUs)):
 // device job table, chunk c of 1024 elements belongs to the job with chunk0 <= c < next chunk0 (bisection)
 struct AdamJob { float* p; const float* g; float* m; float* v; float* ema; long n; long chunk0; };
+// the host packs these records with struct.pack("<QQQQQqq") (kernels.py::adamw_jobs): pin the layout the pack string assumes
+static_assert(sizeof(AdamJob) == 56, "AdamJob: 7 x 8 bytes");
+static_assert(offsetof(AdamJob, p) == 0 && offsetof(AdamJob, g) == 8 && offsetof(AdamJob, m) == 16 && offsetof(AdamJob, v) == 24 && offsetof(AdamJob, ema) == 32 &&
+              offsetof(AdamJob, n) == 40 && offsetof(AdamJob, chunk0) == 48, "AdamJob: field offsets must match the host's pack string");
 constexpr int ADAM_CHUNK = 1024;   // elements per block iteration (256 threads x float4)
 __global__ __launch_bounds__(256) void adamw_multi_kernel(AdamArgs a, const AdamJob* __restrict__ jobs, int njobs, long nchunks) {
   const float clip = clip_coef(a);
@@ -174,6 +180,12 @@ __global__ __launch_bounds__(256) void adamw_shadow_kernel(AdamArgs a, int R, in
 }
 // every GEMM weight of a model in ONE launch (97 at 1.4 B: a launch each ramps up and drains the chip 97 times): device job table, block -> job by bisection on tile0
 struct AdamShadowJob { float* p; const float* g; float* m; float* v; float* ema; bf16_t* w16; bf16_t* w16t; long ld16, ldt; int R, C, tile0, tiles_c; };
+// packed with struct.pack("<QQQQQQQqqiiii") (kernels.py::adamw_shadow_jobs)
+static_assert(sizeof(AdamShadowJob) == 88, "AdamShadowJob: 9 x 8 + 4 x 4 bytes");
+static_assert(offsetof(AdamShadowJob, p) == 0 && offsetof(AdamShadowJob, g) == 8 && offsetof(AdamShadowJob, m) == 16 && offsetof(AdamShadowJob, v) == 24 &&
+              offsetof(AdamShadowJob, ema) == 32 && offsetof(AdamShadowJob, w16) == 40 && offsetof(AdamShadowJob, w16t) == 48 && offsetof(AdamShadowJob, ld16) == 56 &&
+              offsetof(AdamShadowJob, ldt) == 64 && offsetof(AdamShadowJob, R) == 72 && offsetof(AdamShadowJob, C) == 76 && offsetof(AdamShadowJob, tile0) == 80 &&
+              offsetof(AdamShadowJob, tiles_c) == 84, "AdamShadowJob: field offsets must match the host's pack string");
 __global__ __launch_bounds__(256) void adamw_shadow_multi_kernel(AdamArgs a0, const AdamShadowJob* __restrict__ jobs, int njobs) {
   __shared__ __attribute__((aligned(16))) bf16_t tile[TT][TT + TPAD];
   int lo = 0, hi = njobs - 1;
@@ -214,16 +226,16 @@ __global__ __launch_bounds__(256) void sumsq_final_kernel(const float* __restric
   if (threadIdx.x == 0) out[0] = red[0] + red[1] + red[2] + red[3];
 }
 
-int fill_args(AdamArgs& a, const char* name, float* p, const float* g, float* m, float* v, float lr, float beta1, float beta2, float eps, float weight_decay,
+int fill_args(AdamArgs& a, const char* name, float* p, const float* g, float* m, float* v, float lr, double beta1, double beta2, float eps, float weight_decay,
               int64_t step, const float* grad_norm_sq, float max_grad_norm) {
   UDM_CHECK_ARG(p && g && m && v, "%s: null pointer", name);
-  UDM_CHECK_ARG(step >= 1 && beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps > 0.f, "%s: bad hyper-parameters (step %ld)", name, (long)step);
+  UDM_CHECK_ARG(step >= 1 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps > 0.f, "%s: bad hyper-parameters (step %ld)", name, (long)step);
   UDM_CHECK_ARG(!grad_norm_sq || max_grad_norm > 0.f, "%s: clipping needs max_grad_norm > 0", name);
   a.p = p; a.g = g; a.m = m; a.v = v;
-  a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps;
+  a.lr = lr; a.omb1 = (float)(1.0 - beta1); a.b2 = (float)beta2; a.omb2 = (float)(1.0 - beta2); a.eps = eps;
   a.decay = 1.f - lr * weight_decay;
-  a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-  a.rsqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)step)));
+  a.bc1 = (float)(1.0 - pow(beta1, (double)step));
+  a.rsqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow(beta2, (double)step)));
   a.gnorm_sq = grad_norm_sq; a.max_norm = max_grad_norm;
   a.ema = nullptr; a.ema_omd = 0.f;
   return 0;
@@ -250,7 +262,7 @@ extern "C" int udm_sumsq_f32(const float* x, int64_t n, float* out, float* ws, i
   return 0;
 }
 
-extern "C" int udm_adamw_step_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+extern "C" int udm_adamw_step_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps, float weight_decay,
                                   int64_t step, const float* grad_norm_sq, float max_grad_norm, float* ema, float ema_decay, hipStream_t stream) {
   AdamArgs a;
   if (int rc = fill_args(a, "udm_adamw_step", p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_norm_sq, max_grad_norm)) return rc;
@@ -266,7 +278,7 @@ extern "C" int udm_adamw_step_ema(float* p, const float* g, float* m, float* v, 
 }
 
 // jobs: device array of njobs records {p, g, m, v, ema (nullable), n, chunk0} (7 x 8 bytes; chunk0 = sum over the jobs before of ceil(n / 1024)), nchunks = the total
-extern "C" int udm_adamw_step_multi(const void* jobs, int64_t njobs, int64_t nchunks, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
+extern "C" int udm_adamw_step_multi(const void* jobs, int64_t njobs, int64_t nchunks, float lr, double beta1, double beta2, float eps, float weight_decay, int64_t step,
                                     const float* grad_norm_sq, float max_grad_norm, float ema_decay, hipStream_t stream) {
   UDM_CHECK_ARG(jobs && njobs > 0 && nchunks > 0, "udm_adamw_step_multi: empty job table");
   AdamArgs a;
@@ -282,7 +294,7 @@ extern "C" int udm_adamw_step_multi(const void* jobs, int64_t njobs, int64_t nch
 }
 
 // jobs: device array of records {p, g, m, v, ema (nullable), w16 (nullable), w16t (nullable), ld16, ldt, R, C, tile0, tiles_c} (see AdamShadowJob), ntiles = total 64 x 64 tiles
-extern "C" int udm_adamw_step_shadow_multi(const void* jobs, int64_t njobs, int64_t ntiles, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
+extern "C" int udm_adamw_step_shadow_multi(const void* jobs, int64_t njobs, int64_t ntiles, float lr, double beta1, double beta2, float eps, float weight_decay, int64_t step,
                                            const float* grad_norm_sq, float max_grad_norm, float ema_decay, hipStream_t stream) {
   UDM_CHECK_ARG(jobs && njobs > 0 && ntiles > 0 && ntiles < (1ll << 31), "udm_adamw_step_shadow_multi: empty / oversized job table");
   AdamArgs a;
@@ -296,12 +308,12 @@ extern "C" int udm_adamw_step_shadow_multi(const void* jobs, int64_t njobs, int6
   return 0;
 }
 
-extern "C" int udm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+extern "C" int udm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps, float weight_decay,
                               int64_t step, const float* grad_norm_sq, float max_grad_norm, hipStream_t stream) {
   return udm_adamw_step_ema(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_norm_sq, max_grad_norm, nullptr, 0.f, stream);
 }
 
-extern "C" int udm_adamw_step_shadow_ema(float* p, const float* g, float* m, float* v, int64_t R, int64_t C, float lr, float beta1, float beta2, float eps,
+extern "C" int udm_adamw_step_shadow_ema(float* p, const float* g, float* m, float* v, int64_t R, int64_t C, float lr, double beta1, double beta2, float eps,
                                          float weight_decay, int64_t step, const float* grad_norm_sq, float max_grad_norm, void* w16, int64_t ld16, void* w16t,
                                          int64_t ldt, float* ema, float ema_decay, hipStream_t stream) {
   AdamArgs a;
@@ -316,7 +328,7 @@ extern "C" int udm_adamw_step_shadow_ema(float* p, const float* g, float* m, flo
   return 0;
 }
 
-extern "C" int udm_adamw_step_shadow(float* p, const float* g, float* m, float* v, int64_t R, int64_t C, float lr, float beta1, float beta2, float eps,
+extern "C" int udm_adamw_step_shadow(float* p, const float* g, float* m, float* v, int64_t R, int64_t C, float lr, double beta1, double beta2, float eps,
                                      float weight_decay, int64_t step, const float* grad_norm_sq, float max_grad_norm, void* w16, int64_t ld16, void* w16t,
                                      int64_t ldt, hipStream_t stream) {
   return udm_adamw_step_shadow_ema(p, g, m, v, R, C, lr, beta1, beta2, eps, weight_decay, step, grad_norm_sq, max_grad_norm, w16, ld16, w16t, ldt, nullptr, 0.f,
