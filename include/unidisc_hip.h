@@ -193,6 +193,27 @@ int udm_attention_bwd(const void* q, const void* k, const void* v, const void* o
  * 8-wave kernels of csrc/attention.hip (triangular walks, heavy blocks first); the generated one-wave-per-SIMD programs and the wave-specialised dK / dV
  * kernel decline them. */
 #define UDM_ATTN_CAUSAL 2
+/* ---- attention-probability dropout: model.attn_dropout, sdpa(dropout_p = attn_dropout if training else 0) models/dit.py:825-829 (bidirectional and causal)
+ * The argument lists of udm_attention_fwd / _bwd plus (p_drop, seed) in front of the stream; 0 <= p_drop < 1.  The forward and the backward of one attention
+ * take the same pair: the probabilities never exist in memory, so the forward, the dQ and the dK / dV kernel each regenerate the keep mask Z.
+ *   thr = (uint32)(p_drop * 65536 + 0.5) (fp32), s = 1 / (1 - p_drop) (nominal p, as the residual dropout of udm_residual_fwd and as torch).
+ *   thr == 0: the call IS udm_attention_fwd / _bwd - the same dispatch (generated programs included), bit-identical results.
+ *   thr > 0: always the 8-wave kernels of csrc/attention.hip in their dropout form (head dim 32 / 64 / 128, with or without UDM_ATTN_CAUSAL and
+ *   UDM_ATTN_Q_PRESCALED); sample_ids / doc_ranges are an argument error (the reference's FlexAttention path, models/dit.py:784-812, has no dropout), and so
+ *   is the "attention_tr_read" = 0 debug switch.
+ * Mask: one Philox4x32-10 call (the generator of the residual dropout: key = seed, 64-bit counter, words x y z w) per patch of 2 queries x 4 keys,
+ *     ctr   = ((b * H + h) * ceil(L / 2) + (i >> 1)) * ceil(L / 4) + (j >> 2)
+ *     field = 16-bit lane number (i & 1) * 4 + (j & 3) of philox4x32(seed, ctr), the lanes in the order x.lo x.hi y.lo y.hi z.lo z.hi w.lo w.hi
+ *     Z[b, h, i, j] = field >= thr
+ *   - a function of (seed, b, h, i, j) and of the shape (H, L) only: not of the tiling, the head dim, strides, flags or the kernel that asks.
+ * Arithmetic: running maximum, row sum l and lse from the UNDROPPED probabilities P = softmax(S) (masked elements as without dropout, the keep mask applied
+ * after them); O = (s Z o P) V; delta = rowsum(dO o O) as before (it equals sum_j s Z P dP); dS = P o (s Z o dP - delta) for dQ and dK; dV = (s Z o P)^T dO. */
+int udm_attention_fwd_dropout(const void* q, const void* k, const void* v, void* o, float* lse, const int64_t* sample_ids, const int32_t* doc_ranges, int64_t B, int64_t H, int64_t L,
+                              int64_t D, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t flags, float p_drop, uint64_t seed, hipStream_t stream);
+int udm_attention_bwd_dropout(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, float* delta, void* dq, void* dk,
+                              void* dv, const int64_t* sample_ids, const int32_t* doc_ranges, int64_t B, int64_t H, int64_t L, int64_t D, int64_t q_stride, int64_t k_stride,
+                              int64_t v_stride, int64_t o_stride, int64_t do_stride, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t flags, float p_drop,
+                              uint64_t seed, hipStream_t stream);
 
 /* ---- embeddings: EmbeddingLayer models/dit.py:1036-1043 (+modality embedding :1402-1411) ------------- */
 int udm_embedding_fwd(const int64_t* ids, const float* E, const int64_t* modality, const float* Em, float* x, int64_t M, int64_t d, int64_t V,

@@ -53,6 +53,9 @@ PROTOTYPES = {
     "udm_attention_doc_ranges": [_P, _I64, _I64, _P, _P],
     "udm_attention_fwd": [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P],
     "udm_attention_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P],
+    "udm_attention_fwd_dropout": [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _F, _U64, _P],
+    "udm_attention_bwd_dropout": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _F, _U64,
+                                  _P],
     "udm_assemble_joint_tokens": [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P],
     "udm_interleaved_rope": [_P, _P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P],
     "udm_interleaved_block_lottery": [_P, _P, _P, _I64, _F, _I64, _I64, _P, _P, _P, _P, _P, _P],

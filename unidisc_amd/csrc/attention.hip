@@ -75,12 +75,73 @@ __global__ __launch_bounds__(256) void attn_doc_ranges_kernel(const int64_t* __r
 }
 
 // ------------------------------------------------------------------------------------------------
+// attention-probability dropout (model.attn_dropout; the reference's sdpa(dropout_p=...), models/dit.py:825-829)
+// ------------------------------------------------------------------------------------------------
+// The probabilities never exist in memory, so the forward, the dQ and the dK/dV kernel each regenerate the keep mask Z from a counter RNG.  The mask is
+// defined on patches of 2 queries x 4 keys, one Philox call per patch (include/unidisc_hip.h states it for restating):
+//     ctr   = ((b H + h) ceil(L / 2) + (i >> 1)) ceil(L / 4) + (j >> 2)
+//     field = 16-bit lane (i & 1) 4 + (j & 3) of philox4x32(seed, ctr), lanes in the order x.lo x.hi y.lo y.hi z.lo z.hi w.lo w.hi
+//     Z[b, h, i, j] = field >= thr,  thr = (uint32)(p 65536 + 0.5)
+// A lane never compares more fields than it draws: it turns each patch it draws into 8 keep BITS (bit = the field's lane number), packs the 4 patches
+// of a tile into one 32-bit word, and the lanes that share patches swap whole words with one DPP move each.
+//   forward, dQ (lane = one query, runs of 4 keys): the lane pair (i, i ^ 1) shares its 8 runs of a 64-key tile; the even lane draws runs 0, 2, 4, 6, the
+//     odd lane 1, 3, 5, 7: 4 Philox calls per lane and key tile, 1 DPP move.
+//   dK/dV (lane = one key, runs of 4 queries = 2 patches): the 4 lanes of a key group (j >> 2) share the 16 query pairs of a 64-query tile; lane
+//     (j & 3) draws pairs 4 m + (j & 3), m = 0..3: 4 Philox calls per lane and query tile, 4 DPP moves (quad broadcasts).
+// The element's decision is then one v_bfe_i32 (bit -> 0 / ~0) and one v_and on the fp32 value.
+struct AttnDrop {
+  uint64_t seed;
+  uint32_t thr;       // keep iff 16-bit field >= thr
+  float keep_scale;   // 1 / (1 - p)
+};
+__device__ __forceinline__ AttnDrop drop_of() { return AttnDrop{}; }
+__device__ __forceinline__ AttnDrop drop_of(const AttnDrop& d) { return d; }
+__device__ __forceinline__ uint32_t drop_patch_bits(uint64_t seed, uint64_t ctr, uint32_t thr) {
+  const uint4 r = philox4x32(seed, ctr);
+  const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+  uint32_t bits = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    bits |= ((w[k] & 0xffffu) >= thr ? 1u : 0u) << (2 * k);
+    bits |= ((w[k] >> 16) >= thr ? 1u : 0u) << (2 * k + 1);
+  }
+  return bits;
+}
+template <int CTRL>
+__device__ __forceinline__ uint32_t drop_quad_perm(uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, false); }
+// x if bit `BIT` of w is set, else +0
+template <int BIT>
+__device__ __forceinline__ float drop_keep(float x, uint32_t w) {
+  return __builtin_bit_cast(float, __builtin_bit_cast(int, x) & ((int)(w << (31 - BIT)) >> 31));
+}
+// the 4 values of one run: bits 8 g + 0..3 of w (g is a constant after unrolling)
+__device__ __forceinline__ void drop_apply4(float* x, uint32_t w, int g) {
+  const uint32_t v = w >> (8 * g);
+  x[0] = drop_keep<0>(x[0], v); x[1] = drop_keep<1>(x[1], v); x[2] = drop_keep<2>(x[2], v); x[3] = drop_keep<3>(x[3], v);
+}
+// forward / dQ: keep-bit words of this lane's query for the 64-key tile at kv0.  Run n = 4 f + rg (keys kv0 + 8 n + 4 hi + 0..3) has its 4 bits at
+// 8 (n >> 1) + 0..3 of w[n & 1].  row_ctr = ((b H + h) ceil(L/2) + (qi >> 1)) ceil(L/4), par = qi & 1 (= lane & 1: query blocks start on even rows).
+__device__ __forceinline__ void drop_words_q(const AttnDrop& dr, uint64_t row_ctr, int kv0, int par, int hi, uint32_t (&w)[2]) {
+  uint32_t mine = 0;
+#pragma unroll
+  for (int m = 0; m < 4; ++m) mine |= drop_patch_bits(dr.seed, row_ctr + (uint32_t)((kv0 >> 2) + 4 * m + 2 * par + hi), dr.thr) << (8 * m);
+  const uint32_t theirs = drop_quad_perm<0xB1>(mine);   // lane ^ 1
+  w[0] = (par ? theirs : mine) >> (4 * par);
+  w[1] = (par ? mine : theirs) >> (4 * par);
+}
+
+// ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
 // CAUSAL (model.full_attention=false): query i sees keys j <= i.  A block walks only the key tiles below its diagonal (t * 64 < (tile_x + 1) * 128) and
 // the per-element test runs on the two tiles that cross it; blocks are dispatched late query tiles first (the longest walks start first).
-template <int D, bool HAS_SID, bool USE_TR, int ABL = 0, bool CAUSAL = false>   // ABL (timing-only ablations, wrong results): 1 = no softmax VALU, 2 = no MFMAs
-__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
+// DROP: attention-probability dropout.  Running maximum, row sum and lse come from the undropped probabilities; only the P operand of O^T += V^T P^T is
+// Z o P, and 1 / (1 - p) goes onto 1 / l in the epilogue.
+// DR: empty, or AttnDrop - the dropout form takes its parameters as a second by-value argument (AttnArgs is full and its layout is shared with the generated kernels)
+template <int D, bool HAS_SID, bool USE_TR, int ABL = 0, bool CAUSAL = false, typename... DR>   // ABL (timing-only ablations, wrong results): 1 = no softmax VALU, 2 = no MFMAs
+__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a, DR... drop_arg) {
+  constexpr bool DROP = sizeof...(DR) != 0;
+  [[maybe_unused]] const AttnDrop dr = drop_of(drop_arg...);
   extern __shared__ __attribute__((aligned(16))) char smem[];  // K0 | K1 | V0 | V1 | sidk[2][64]   (one array: keeps LDS-DMA waits exact)
   constexpr int TB = BKV * D * 2;
   long* sid_s = reinterpret_cast<long*>(smem + 4 * TB);
@@ -115,6 +176,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
     for (int r = 0; r < 16; ++r) oT[i][r] = 0.f;
   float m = -INFINITY, lsum = 0.f;
   const float c = a.scale_log2;
+  uint64_t drop_row = 0;
+  if constexpr (DROP) drop_row = ((uint64_t)bh * (uint64_t)((a.L + 1) >> 1) + (uint64_t)(qi >> 1)) * (uint64_t)((a.L + 3) >> 2);
 
   const bf16_t* kbase = a.k + rowbase * a.k_stride + h * D;
   const bf16_t* vbase = a.v + rowbase * a.v_stride + h * D;
@@ -239,6 +302,17 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
       }
     lsum += psum;
     }
+    if constexpr (DROP) {   // (after the row sum: l and lse are those of the undropped probabilities)
+      uint32_t zw[2];
+      drop_words_q(dr, drop_row, kv0, l31 & 1, hi, zw);
+#pragma unroll
+      for (int f = 0; f < 2; ++f)
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) {
+          const int n = f * 4 + rg;
+          drop_apply4(&p[f][rg * 4], zw[n & 1], n >> 1);
+        }
+    }
     // O^T += V^T P^T
 #pragma unroll
     for (int cc = 0; cc < 4; ++cc) {
@@ -264,7 +338,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
   if (HAS_SID && !doc_pure) UDM_WALK(std::true_type{}) else UDM_WALK(std::false_type{})
 #undef UDM_WALK
   const float ltot = lsum + __shfl_xor(lsum, 32, 64);
-  const float inv = ltot > 0.f ? 1.f / ltot : 0.f;
+  float inv = ltot > 0.f ? 1.f / ltot : 0.f;
+  if constexpr (DROP) inv *= dr.keep_scale;
   if (q_ok && hi == 0) a.lse[((long)b * a.H + h) * a.L + qi] = ltot > 0.f ? __builtin_fmaf(m, c, log2f(ltot)) : INFINITY;
   if constexpr (D == 128) {
     if (a.out_stride % 8 == 0) {   // block-uniform: whole-row stores through the (now idle) K / V stages
@@ -289,8 +364,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
 // ------------------------------------------------------------------------------------------------
 // backward, dQ: block owns 128 queries, walks key tiles.  dQ^T = K^T dS^T (lane owns a query column).
 // ------------------------------------------------------------------------------------------------
-template <int D, bool HAS_SID, bool USE_TR, bool CAUSAL = false>   // CAUSAL: the forward's walk (tiles below the diagonal, late query blocks first)
-__global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs a) {
+// DROP: dS = P o (s Z o dP - delta), s = 1 / (1 - p); delta = rowsum(dO o O) needs no change (O is the dropped output).
+template <int D, bool HAS_SID, bool USE_TR, bool CAUSAL = false, typename... DR>   // CAUSAL: the forward's walk (tiles below the diagonal, late query blocks first)
+__global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs a, DR... drop_arg) {
+  constexpr bool DROP = sizeof...(DR) != 0;
+  [[maybe_unused]] const AttnDrop dr = drop_of(drop_arg...);
   extern __shared__ __attribute__((aligned(16))) char smem[];  // K0 | K1 | V0 | V1 | sidk[2][64]
   constexpr int TB = BKV * D * 2;
   long* sid_s = reinterpret_cast<long*>(smem + 4 * TB);
@@ -339,6 +417,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs a) {
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]), "+v"(dof[ks]));
   asm volatile("" : "+v"(lse_q), "+v"(delta_q));
+  uint64_t drop_row = 0;
+  if constexpr (DROP) drop_row = ((uint64_t)bh * (uint64_t)((a.L + 1) >> 1) + (uint64_t)(qi >> 1)) * (uint64_t)((a.L + 3) >> 2);
 
   f32x16_t dqT[DB];
 #pragma unroll
@@ -383,6 +463,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs a) {
     }
     const bool diag = CAUSAL && kv0 + BKV - 1 > tile_x * BQ;   // block-uniform (see the forward)
     float ds[2][16];
+    uint32_t zw[2] = {0, 0};
+    if constexpr (DROP) drop_words_q(dr, drop_row, kv0, l31 & 1, hi, zw);
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
       f32x16_t sT, dpT;
@@ -393,6 +475,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs a) {
         const int off = tile_off<D>(f * 32 + l31, ks * 2 + hi);
         sT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(Ks, off), qf[ks], sT, 0, 0, 0);
         dpT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(Vs, off), dof[ks], dpT, 0, 0, 0);
+      }
+      if constexpr (DROP) {   // dP <- s Z o dP
+        float dpz[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dpz[r] = dpT[r];
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) drop_apply4(&dpz[rg * 4], zw[(f * 4 + rg) & 1], (f * 4 + rg) >> 1);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dpT[r] = dpz[r] * dr.keep_scale;
       }
       // per-element masks only for document masks and the ragged last tile: full tiles have no out-of-range keys, and an out-of-range
       // QUERY has lse = +inf (p = 0) and zero operands
@@ -454,8 +545,11 @@ constexpr int BQT = 64;
 // 32-query step, but twice the occupancy).
 // CAUSAL: a key block walks only the query tiles at or below its diagonal (from t = 2 tile_x: every query there sees some key of the block), with the
 // per-element test on the two tiles that cross it.  The early key blocks have the longest walks and are dispatched first anyway (tile-major order).
-template <int D, bool HAS_SID, bool USE_TR, int MODE, int WAVES, bool CAUSAL = false>
-__global__ __launch_bounds__(256, WAVES) void attn_bwd_dkv_kernel(AttnArgs a) {
+// DROP: dV^T += dO^T (Z o P) with s = 1 / (1 - p) applied to dV in the epilogue; dS = P o (s Z o dP - delta).
+template <int D, bool HAS_SID, bool USE_TR, int MODE, int WAVES, bool CAUSAL = false, typename... DR>
+__global__ __launch_bounds__(256, WAVES) void attn_bwd_dkv_kernel(AttnArgs a, DR... drop_arg) {
+  constexpr bool DROP = sizeof...(DR) != 0;
+  [[maybe_unused]] const AttnDrop dr = drop_of(drop_arg...);
   constexpr bool DO_DK = (MODE & 1) != 0, DO_DV = (MODE & 2) != 0;
   extern __shared__ __attribute__((aligned(16))) char smem[];  // Q0 | Q1 | dO0 | dO1 | lse[2][64] | delta[2][64] | sidq[2][64]
   constexpr int TB = BQT * D * 2;
@@ -508,6 +602,8 @@ __global__ __launch_bounds__(256, WAVES) void attn_bwd_dkv_kernel(AttnArgs a) {
     t_begin = sp.t_begin; t_end = sp.t_end; blk_id = sp.blk_id;
   }
   if (CAUSAL) t_begin = tile_x * (128 / BQT);
+  uint64_t drop_col = 0;   // (b H + h) ceil(L/2) ceil(L/4) + (ki >> 2): the counter of query pair 0 and this lane's key group
+  if constexpr (DROP) drop_col = (uint64_t)bh * (uint64_t)((a.L + 1) >> 1) * (uint64_t)((a.L + 3) >> 2) + (uint64_t)(ki >> 2);
   if (t_begin < t_end) {
     Stg::issue(qbase, a.q_stride, t_begin * BQT, a.L, smem + (t_begin & 1) * TB, wave, lane);
     Stg::issue(dobase, a.do_stride, t_begin * BQT, a.L, smem + (2 + (t_begin & 1)) * TB, wave, lane);
@@ -531,6 +627,20 @@ __global__ __launch_bounds__(256, WAVES) void attn_bwd_dkv_kernel(AttnArgs a) {
     if (t + 1 < t_end) {
       Stg::issue(qbase, a.q_stride, q0 + BQT, a.L, smem + (st ^ 1) * TB, wave, lane);
       Stg::issue(dobase, a.do_stride, q0 + BQT, a.L, smem + (2 + (st ^ 1)) * TB, wave, lane);
+    }
+    // keep bits of the tile: the run (qs, rg) of 4 queries is the query pairs n = 8 qs + 2 rg + (e >> 1) (rows q0 + 32 qs + 8 rg + 4 hi + e); lane jj = ki & 3
+    // draws pairs 4 m + jj into bits 8 m + 0..7 of its word, zq[o] is lane o's word shifted so that THIS lane's key column is bit 0 / 4 of each patch
+    uint32_t zq[4] = {0, 0, 0, 0};
+    if constexpr (DROP) {
+      const int jj = l31 & 3;
+      uint32_t mine = 0;
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        const int i2 = (q0 >> 1) + 16 * (m >> 1) + 8 * (m & 1) + 4 * (jj >> 1) + 2 * hi + (jj & 1);   // (row >> 1) of pair n = 4 m + jj
+        mine |= drop_patch_bits(dr.seed, drop_col + (uint64_t)(uint32_t)i2 * (uint64_t)(uint32_t)((a.L + 3) >> 2), dr.thr) << (8 * m);
+      }
+      zq[0] = drop_quad_perm<0x00>(mine) >> jj; zq[1] = drop_quad_perm<0x55>(mine) >> jj;
+      zq[2] = drop_quad_perm<0xAA>(mine) >> jj; zq[3] = drop_quad_perm<0xFF>(mine) >> jj;
     }
 #pragma unroll
     for (int qs = 0; qs < 2; ++qs) {
@@ -564,6 +674,12 @@ __global__ __launch_bounds__(256, WAVES) void attn_bwd_dkv_kernel(AttnArgs a) {
             if (decltype(IDT)::value) ok = ok && attn_pair_ok(sidq[ql0 + e], sid_k);
             if (decltype(CDT)::value) ok = ok && ki <= q0 + ql0 + e;
             p[r] = ok ? __builtin_amdgcn_exp2f(s[r] * c - lv[e]) : 0.f;
+            if constexpr (DROP) {
+              // pair n = 8 qs + 2 rg + (e >> 1) = 4 m + o: m = 2 qs + (rg >> 1), o = 2 (rg & 1) + (e >> 1); query parity e & 1
+              const uint32_t zv = zq[2 * (rg & 1) + (e >> 1)] >> (8 * (2 * qs + (rg >> 1)) + 4 * (e & 1));
+              ds[r] = p[r] * __builtin_fmaf(drop_keep<0>(dp[r], zv), dr.keep_scale, -dv[e]);
+              p[r] = drop_keep<0>(p[r], zv);
+            } else
             ds[r] = p[r] * (dp[r] - dv[e]);
           }
         }
@@ -599,6 +715,10 @@ __global__ __launch_bounds__(256, WAVES) void attn_bwd_dkv_kernel(AttnArgs a) {
         const int d0 = i * 32 + 8 * rg + 4 * hi;
         if (DO_DK) *reinterpret_cast<uint2*>(kp + d0) = make_uint2(pack2bf(dkT[i][rg * 4] * a.scale, dkT[i][rg * 4 + 1] * a.scale),
                                                                    pack2bf(dkT[i][rg * 4 + 2] * a.scale, dkT[i][rg * 4 + 3] * a.scale));
+        if constexpr (DROP) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) dvT[i][rg * 4 + e] *= dr.keep_scale;
+        }
         if (DO_DV) *reinterpret_cast<uint2*>(vp + d0) = make_uint2(pack2bf(dvT[i][rg * 4], dvT[i][rg * 4 + 1]), pack2bf(dvT[i][rg * 4 + 2], dvT[i][rg * 4 + 3]));
       }
   }
@@ -658,6 +778,35 @@ void launch_bwd(const AttnArgs& a, hipStream_t s) {
   } else hipLaunchKernelGGL(kk, gk, dim3(256), lds_k, s, a);
 }
 
+// p > 0: the 8-wave kernels with the mask, never the generated programs or the wave-specialised dK/dV kernel (none of them has a dropout form)
+template <int D, bool CAUSAL>
+void launch_fwd_drop(const AttnArgs& a, const AttnDrop& dr, hipStream_t s) {
+  dim3 grid(((a.L + BQ - 1) / BQ) * a.H * a.B);
+  const size_t lds = 4 * BKV * D * 2 + 2 * BKV * sizeof(long);
+  auto kern = attn_fwd_kernel<D, false, true, 0, CAUSAL, AttnDrop>;
+  static bool once = false;
+  if (!once) { set_lds(kern, lds); once = true; }
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, dr);
+}
+template <int D, bool CAUSAL>
+void launch_bwd_drop(const AttnArgs& a, const AttnDrop& dr, hipStream_t s) {
+  dim3 gq(((a.L + BQ - 1) / BQ) * a.H * a.B), gk(((a.L + 127) / 128) * a.H * a.B);
+  const size_t lds_q = 4 * BKV * D * 2 + 2 * BKV * sizeof(long);
+  const size_t lds_k = 4 * BQT * D * 2 + 4 * BQT * sizeof(float) + 2 * BQT * sizeof(long);
+  auto kq = attn_bwd_dq_kernel<D, false, true, CAUSAL, AttnDrop>;
+  auto kk = attn_bwd_dkv_kernel<D, false, true, 3, (D == 128) ? 1 : 2, CAUSAL, AttnDrop>;
+  static bool once = false;
+  if (!once) { set_lds(kq, lds_q); set_lds(kk, lds_k); once = true; }
+  hipLaunchKernelGGL(kq, gq, dim3(256), lds_q, s, a, dr);
+  hipLaunchKernelGGL(kk, gk, dim3(256), lds_k, s, a, dr);
+}
+#define ATTN_DISPATCH_DROP(FN, a, dr, D, s)                                                        \
+  do {                                                                                            \
+    if (D == 128) { if (a.causal) FN<128, true>(a, dr, s); else FN<128, false>(a, dr, s); }       \
+    else if (D == 64) { if (a.causal) FN<64, true>(a, dr, s); else FN<64, false>(a, dr, s); }     \
+    else { if (a.causal) FN<32, true>(a, dr, s); else FN<32, false>(a, dr, s); }                  \
+  } while (0)
+
 #define ATTN_DISPATCH(FN, a, D, sid, tr, s)                                    \
   do {                                                                         \
     if (D == 128) { if (sid) { if (tr) FN<128, true, true>(a, s); else FN<128, true, false>(a, s); } else { if (tr) FN<128, false, true>(a, s); else FN<128, false, false>(a, s); } } \
@@ -673,6 +822,18 @@ void launch_bwd(const AttnArgs& a, hipStream_t s) {
   } while (0)
 
 int g_use_tr = 1;
+
+// p_drop -> (thr, keep_scale, seed); thr == 0 means "no dropout: today's dispatch"
+int check_drop(const char* name, float p_drop, uint64_t seed, const void* sample_ids, const void* doc_ranges, AttnDrop& dr) {
+  UDM_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "%s: p_drop %g outside [0, 1)", name, (double)p_drop);
+  dr.seed = seed;
+  dr.thr = (uint32_t)(p_drop * 65536.0f + 0.5f);
+  dr.keep_scale = 1.f / (1.f - p_drop);
+  if (dr.thr == 0) return 0;
+  UDM_CHECK_ARG(!sample_ids && !doc_ranges, "%s: p_drop > 0 with sample_ids / doc_ranges", name);
+  UDM_CHECK_ARG(g_use_tr, "%s: p_drop > 0 needs the transposing LDS reads (attention_tr_read = 1)", name);
+  return 0;
+}
 
 int check_common(const char* name, int64_t B, int64_t H, int64_t L, int64_t D, int64_t qs, int64_t ks, int64_t vs) {
   UDM_CHECK_ARG(B > 0 && H > 0 && L > 0, "%s: empty problem", name);
@@ -696,14 +857,16 @@ extern "C" int udm_attention_doc_ranges(const int64_t* sample_ids, int64_t B, in
   return 0;
 }
 
-extern "C" int udm_attention_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const int64_t* sample_ids, const int32_t* doc_ranges, int64_t B, int64_t H, int64_t L,
-                                 int64_t D, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t flags, hipStream_t stream) {
-  UDM_CHECK_ARG(q && k && v && o && lse, "udm_attention_fwd: null pointer");
-  UDM_CHECK_ARG((flags & ~(int64_t)(UDM_ATTN_Q_PRESCALED | UDM_ATTN_CAUSAL)) == 0, "udm_attention_fwd: unknown flags %ld", (long)flags);
-  UDM_CHECK_ARG(!(flags & UDM_ATTN_CAUSAL) || (!sample_ids && !doc_ranges), "udm_attention_fwd: UDM_ATTN_CAUSAL with sample_ids / doc_ranges");
-  if (int rc = check_common("udm_attention_fwd", B, H, L, D, q_stride, k_stride, v_stride)) return rc;
-  UDM_CHECK_ARG(o_stride % 4 == 0, "udm_attention_fwd: o_stride must be a multiple of 4");
-  UDM_CHECK_ARG(sample_ids || !doc_ranges, "udm_attention_fwd: doc_ranges without sample_ids");
+namespace {
+// `drop`: null for udm_attention_fwd, the checked parameters for udm_attention_fwd_dropout (thr == 0: the same dispatch as without it)
+int attention_fwd_impl(const char* name, const void* q, const void* k, const void* v, void* o, float* lse, const int64_t* sample_ids, const int32_t* doc_ranges, int64_t B, int64_t H,
+                       int64_t L, int64_t D, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t flags, const AttnDrop* drop, hipStream_t stream) {
+  UDM_CHECK_ARG(q && k && v && o && lse, "%s: null pointer", name);
+  UDM_CHECK_ARG((flags & ~(int64_t)(UDM_ATTN_Q_PRESCALED | UDM_ATTN_CAUSAL)) == 0, "%s: unknown flags %ld", name, (long)flags);
+  UDM_CHECK_ARG(!(flags & UDM_ATTN_CAUSAL) || (!sample_ids && !doc_ranges), "%s: UDM_ATTN_CAUSAL with sample_ids / doc_ranges", name);
+  if (int rc = check_common(name, B, H, L, D, q_stride, k_stride, v_stride)) return rc;
+  UDM_CHECK_ARG(o_stride % 4 == 0, "%s: o_stride must be a multiple of 4", name);
+  UDM_CHECK_ARG(sample_ids || !doc_ranges, "%s: doc_ranges without sample_ids", name);
   AttnArgs a{};
   a.exp = udm_exp_flags();
   a.doc_ranges = doc_ranges;
@@ -714,22 +877,36 @@ extern "C" int udm_attention_fwd(const void* q, const void* k, const void* v, vo
   a.scale_log2 = a.scale * 1.4426950408889634f;
   if (flags & UDM_ATTN_Q_PRESCALED) { a.q_prescaled = 1; a.scale_log2 = 1.0f; }   // q already carries log2(e) / sqrt(D): the scores ARE the base-2 exponents
   a.causal = (flags & UDM_ATTN_CAUSAL) ? 1 : 0;
-  if (a.causal) ATTN_DISPATCH_CAUSAL(launch_fwd, a, D, g_use_tr, stream);
+  if (drop && drop->thr) ATTN_DISPATCH_DROP(launch_fwd_drop, a, *drop, D, stream);
+  else if (a.causal) ATTN_DISPATCH_CAUSAL(launch_fwd, a, D, g_use_tr, stream);
   else ATTN_DISPATCH(launch_fwd, a, D, sample_ids != nullptr, g_use_tr, stream);
-  UDM_CHECK_LAUNCH("udm_attention_fwd");
+  UDM_CHECK_LAUNCH(name);
   return 0;
 }
+}  // namespace
 
-extern "C" int udm_attention_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, float* delta, void* dq, void* dk,
-                                 void* dv, const int64_t* sample_ids, const int32_t* doc_ranges, int64_t B, int64_t H, int64_t L, int64_t D, int64_t q_stride, int64_t k_stride,
-                                 int64_t v_stride, int64_t o_stride, int64_t do_stride, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride,
-                                 int64_t flags, hipStream_t stream) {
-  UDM_CHECK_ARG(q && k && v && o && dout && lse && delta && dq && dk && dv, "udm_attention_bwd: null pointer");
-  UDM_CHECK_ARG((flags & ~(int64_t)(UDM_ATTN_Q_PRESCALED | UDM_ATTN_CAUSAL)) == 0, "udm_attention_bwd: unknown flags %ld", (long)flags);
-  UDM_CHECK_ARG(!(flags & UDM_ATTN_CAUSAL) || (!sample_ids && !doc_ranges), "udm_attention_bwd: UDM_ATTN_CAUSAL with sample_ids / doc_ranges");
-  if (int rc = check_common("udm_attention_bwd", B, H, L, D, q_stride, k_stride, v_stride)) return rc;
-  UDM_CHECK_ARG(o_stride % 8 == 0 && do_stride % 8 == 0 && dq_stride % 4 == 0 && dk_stride % 4 == 0 && dv_stride % 4 == 0, "udm_attention_bwd: bad strides");
-  UDM_CHECK_ARG(sample_ids || !doc_ranges, "udm_attention_bwd: doc_ranges without sample_ids");
+extern "C" int udm_attention_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const int64_t* sample_ids, const int32_t* doc_ranges, int64_t B, int64_t H, int64_t L,
+                                 int64_t D, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t flags, hipStream_t stream) {
+  return attention_fwd_impl("udm_attention_fwd", q, k, v, o, lse, sample_ids, doc_ranges, B, H, L, D, q_stride, k_stride, v_stride, o_stride, flags, nullptr, stream);
+}
+extern "C" int udm_attention_fwd_dropout(const void* q, const void* k, const void* v, void* o, float* lse, const int64_t* sample_ids, const int32_t* doc_ranges, int64_t B, int64_t H,
+                                         int64_t L, int64_t D, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t flags, float p_drop, uint64_t seed,
+                                         hipStream_t stream) {
+  AttnDrop dr{};
+  if (int rc = check_drop("udm_attention_fwd_dropout", p_drop, seed, sample_ids, doc_ranges, dr)) return rc;
+  return attention_fwd_impl("udm_attention_fwd_dropout", q, k, v, o, lse, sample_ids, doc_ranges, B, H, L, D, q_stride, k_stride, v_stride, o_stride, flags, &dr, stream);
+}
+
+namespace {
+int attention_bwd_impl(const char* name, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, float* delta, void* dq, void* dk, void* dv,
+                       const int64_t* sample_ids, const int32_t* doc_ranges, int64_t B, int64_t H, int64_t L, int64_t D, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                       int64_t o_stride, int64_t do_stride, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t flags, const AttnDrop* drop, hipStream_t stream) {
+  UDM_CHECK_ARG(q && k && v && o && dout && lse && delta && dq && dk && dv, "%s: null pointer", name);
+  UDM_CHECK_ARG((flags & ~(int64_t)(UDM_ATTN_Q_PRESCALED | UDM_ATTN_CAUSAL)) == 0, "%s: unknown flags %ld", name, (long)flags);
+  UDM_CHECK_ARG(!(flags & UDM_ATTN_CAUSAL) || (!sample_ids && !doc_ranges), "%s: UDM_ATTN_CAUSAL with sample_ids / doc_ranges", name);
+  if (int rc = check_common(name, B, H, L, D, q_stride, k_stride, v_stride)) return rc;
+  UDM_CHECK_ARG(o_stride % 8 == 0 && do_stride % 8 == 0 && dq_stride % 4 == 0 && dk_stride % 4 == 0 && dv_stride % 4 == 0, "%s: bad strides", name);
+  UDM_CHECK_ARG(sample_ids || !doc_ranges, "%s: doc_ranges without sample_ids", name);
   AttnArgs a{};
   a.exp = udm_exp_flags();
   a.doc_ranges = doc_ranges;
@@ -747,8 +924,27 @@ extern "C" int udm_attention_bwd(const void* q, const void* k, const void* v, co
   (void)env_once;
   a.causal = (flags & UDM_ATTN_CAUSAL) ? 1 : 0;
   // (delta is computed and stored by the dQ kernel, which launch_bwd runs first)
-  if (a.causal) ATTN_DISPATCH_CAUSAL(launch_bwd, a, D, g_use_tr, stream);
+  if (drop && drop->thr) ATTN_DISPATCH_DROP(launch_bwd_drop, a, *drop, D, stream);
+  else if (a.causal) ATTN_DISPATCH_CAUSAL(launch_bwd, a, D, g_use_tr, stream);
   else ATTN_DISPATCH(launch_bwd, a, D, sample_ids != nullptr, g_use_tr, stream);
-  UDM_CHECK_LAUNCH("udm_attention_bwd");
+  UDM_CHECK_LAUNCH(name);
   return 0;
+}
+}  // namespace
+
+extern "C" int udm_attention_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, float* delta, void* dq, void* dk,
+                                 void* dv, const int64_t* sample_ids, const int32_t* doc_ranges, int64_t B, int64_t H, int64_t L, int64_t D, int64_t q_stride, int64_t k_stride,
+                                 int64_t v_stride, int64_t o_stride, int64_t do_stride, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride,
+                                 int64_t flags, hipStream_t stream) {
+  return attention_bwd_impl("udm_attention_bwd", q, k, v, o, dout, lse, delta, dq, dk, dv, sample_ids, doc_ranges, B, H, L, D, q_stride, k_stride, v_stride, o_stride, do_stride,
+                            dq_stride, dk_stride, dv_stride, flags, nullptr, stream);
+}
+extern "C" int udm_attention_bwd_dropout(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, float* delta, void* dq, void* dk,
+                                         void* dv, const int64_t* sample_ids, const int32_t* doc_ranges, int64_t B, int64_t H, int64_t L, int64_t D, int64_t q_stride,
+                                         int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t do_stride, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride,
+                                         int64_t flags, float p_drop, uint64_t seed, hipStream_t stream) {
+  AttnDrop dr{};
+  if (int rc = check_drop("udm_attention_bwd_dropout", p_drop, seed, sample_ids, doc_ranges, dr)) return rc;
+  return attention_bwd_impl("udm_attention_bwd_dropout", q, k, v, o, dout, lse, delta, dq, dk, dv, sample_ids, doc_ranges, B, H, L, D, q_stride, k_stride, v_stride, o_stride,
+                            do_stride, dq_stride, dk_stride, dv_stride, flags, &dr, stream);
 }

@@ -257,8 +257,21 @@ class DIT(nn.Module, _HubMixin):
                                           "beside is_causal is an SDPA error in the reference")
         if cfg_get(tr, "image_mode", "discrete") == "continuous":
             raise NotImplementedError("unidisc_amd.DIT: continuous image mode is not on the denoising hot path")
-        if cfg_get(m, "attn_dropout", None):
-            raise NotImplementedError("unidisc_amd.DIT: attention dropout is not implemented (no shipped config enables it)")
+        # model.attn_dropout (configs/experiments/jan_cub.yaml; models/dit.py:1179, :1265 -> sdpa(dropout_p=attn_dropout if training else 0), :825-829, on the
+        # bidirectional and on the causal path): dropout on the softmax probabilities, inside the attention kernels.  The reference's FlexAttention path
+        # (:784-812: packed documents, modality masking) draws none; the key-padding mask shares the kernels' id slot with those and is left out with them.
+        self.attn_dropout = float(cfg_get(m, "attn_dropout", None) or 0.0)
+        if self.attn_dropout > 0.0:
+            if not self.attn_dropout < 1.0:
+                raise ValueError(f"unidisc_amd.DIT: model.attn_dropout = {self.attn_dropout} must be in [0, 1)")
+            if cfg_get(data, "require_sample_ids", False):
+                raise NotImplementedError("unidisc_amd.DIT: model.attn_dropout with data.require_sample_ids (packed documents) - the reference's FlexAttention "
+                                          "path applies no attention dropout")
+            if cfg_get(m, "flex_attention_txt_masking_prob", None) is not None or cfg_get(m, "flex_attention_img_masking_prob", None) is not None:
+                raise NotImplementedError("unidisc_amd.DIT: model.attn_dropout with model.flex_attention_{txt,img}_masking_prob (modality masking) - the "
+                                          "reference's FlexAttention path applies no attention dropout")
+            if cfg_get(m, "use_attention_mask", False):
+                raise NotImplementedError("unidisc_amd.DIT: model.attn_dropout with model.use_attention_mask - the dropout kernels take no key-padding mask")
 
         d, H = cfg_get(m, "hidden_size"), cfg_get(m, "n_heads")
         self.hidden_size, self.n_heads, self.head_dim = d, H, d // H
@@ -847,7 +860,15 @@ class DIT(nn.Module, _HubMixin):
             qbits = torch.where(qbits == 0, torch.full_like(qbits, 3), qbits)
             sid = ((base & 0xffffffff) | (kbits << 32) | (qbits << 40)).contiguous()
             doc_ranges = None
+        p_attn = self.attn_dropout if train else 0.0
+        if p_attn > 0.0 and sid is not None:
+            raise NotImplementedError("unidisc_amd.DIT: model.attn_dropout with packed sample_ids, a ModalityMask or an attention mask - the reference's "
+                                      "FlexAttention path applies no attention dropout")
         S = dict(B=B, L=L, ids=ids, modality=mod_flat, emb_mod=emb_mod, sid=sid, p_drop=p_drop, seed0=seed0, blocks=[])
+        # attention-probability dropout of block i: seed slot 4 i + 3 (4 i + 1, 4 i + 2 are the block's residual dropouts).  The keywords are passed only
+        # when p > 0, like _attn_mask_kw: every other call into the attention entry points is what it was.  The backward and the checkpointing recompute
+        # read the same function, so the three kernels of one attention regenerate one mask.
+        S["attn_drop_kw"] = (lambda i: dict(dropout_p=p_attn, seed=seed0 + 4 * i + 3)) if p_attn > 0.0 else (lambda i: {})
         S["doc_ranges"] = doc_ranges
         S["dgrad_form"] = {name: lin.dgrad_form() for name, lin in self._lins.items()}   # NN vs NT per Linear, fixed by THIS forward's shadows (not re-derived at backward time)
         # SUBS: only [MASK] rows have a non-zero log-probability (model.py:621-658), so in "logp" mode the vocabulary head (GEMM fwd,
@@ -939,7 +960,7 @@ class DIT(nn.Module, _HubMixin):
             if kv_sink is not None:   # KV-cache prefill: the post-rope k and the v of every position into cache slots [0, L)
                 kv_sink[i][0][:, :L].copy_(qkr.view(B, L, 2 * d)[:, :, d:])
                 kv_sink[i][1][:, :L].copy_(qkv.view(B, L, 3 * d)[:, :, 2 * d:])
-            o, lse = K.attention_fwd(qkr, qkv, B, L, H, D, sid, S["doc_ranges"], q_prescaled=True, **self._attn_mask_kw)
+            o, lse = K.attention_fwd(qkr, qkv, B, L, H, D, sid, S["doc_ranges"], q_prescaled=True, **self._attn_mask_kw, **S["attn_drop_kw"](i))
             rows_c = last_rows
             if not recompute and i + 1 == self.n_blocks and head_plan is not None and mode == "logp" and self.compact_last_block and not tc:
                 head_rows_c = self._masked_rows(head_plan, M)   # (the count was queued at the top of this forward: the host does not wait for the device here)
@@ -1433,7 +1454,8 @@ class DIT(nn.Module, _HubMixin):
                     self._wgrad(da, R["o"], lo, G)
             dqkr = torch.empty((M, 2 * d), dtype=BF16, device=dev)
             dqkv = torch.empty((M, 3 * d), dtype=BF16, device=dev)
-            K.attention_bwd(R["qkr"], R["qkv"], R["o"], do, R["lse"], dqkr, dqkv, B, L, H, D, S["sid"], S["doc_ranges"], q_prescaled=True, **self._attn_mask_kw)
+            K.attention_bwd(R["qkr"], R["qkv"], R["o"], do, R["lse"], dqkr, dqkv, B, L, H, D, S["sid"], S["doc_ranges"], q_prescaled=True, **self._attn_mask_kw,
+                            **S["attn_drop_kw"](i))
             qn = self.qk_norm
             K.qknorm_rope_bwd(dqkr, R["qkv"], dqkv, S["cos"], S["sin"], L, D, gq=at.q_norm.weight.detach() if qn else None,
                               gk=at.k_norm.weight.detach() if qn else None, stats=R["qstats"], dgq=G[id(at.q_norm.weight)] if qn else None,

@@ -793,44 +793,55 @@ def _attn_flags(q_prescaled, causal):
     return (ATTN_Q_PRESCALED if q_prescaled else 0) | (ATTN_CAUSAL if causal else 0)
 
 
-def attention_fwd(qkr, qkv, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False, causal=False):
+def _attn_call(name, args, dropout_p, seed):
+    """udm_attention_fwd / udm_attention_bwd as they always were; with attention-probability dropout (dropout_p > 0) the `_dropout` entry point, whose
+    argument list is the same plus (p_drop, seed) in front of the stream.  The forward and the backward of one attention must get the same pair."""
+    if dropout_p:
+        _lib.call(name + "_dropout", *args, float(dropout_p), int(seed) & 0xFFFFFFFFFFFFFFFF, _s())
+    else:
+        _lib.call(name, *args, _s())
+
+
+def attention_fwd(qkr, qkv, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False, causal=False, dropout_p=0.0, seed=0):
     """q, k from qkr [M,2d] (normalised+rotated), v from qkv [M,3d] columns [2d,3d).  q_prescaled: q holds q * attention_q_scale(D).
-    causal: query i sees keys j <= i (not combinable with sample_ids)."""
+    causal: query i sees keys j <= i (not combinable with sample_ids).  dropout_p, seed: dropout on the softmax probabilities (model.attn_dropout; the mask
+    is a function of seed and the element's (b, h, i, j), include/unidisc_hip.h; not combinable with sample_ids)."""
     d = H * D
     M = B * L
     o = torch.empty((M, d), dtype=BF16, device=qkr.device)
     lse = torch.empty((B, H, L), dtype=F32, device=qkr.device)
     q_ptr, k_ptr, v_ptr = qkr.data_ptr(), qkr.data_ptr() + 2 * d, qkv.data_ptr() + 4 * d
-    _lib.call("udm_attention_fwd", q_ptr, k_ptr, v_ptr, _p(o), _p(lse), _p(sample_ids), _p(doc_ranges), B, H, L, D, 2 * d, 2 * d, 3 * d, d,
-              _attn_flags(q_prescaled, causal), _s())
+    _attn_call("udm_attention_fwd", (q_ptr, k_ptr, v_ptr, _p(o), _p(lse), _p(sample_ids), _p(doc_ranges), B, H, L, D, 2 * d, 2 * d, 3 * d, d,
+                                     _attn_flags(q_prescaled, causal)), dropout_p, seed)
     return o, lse
 
 
-def attention_bwd(qkr, qkv, o, do, lse, dqkr, dqkv, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False, causal=False):
-    """Writes dq|dk (wrt the stored rotated q, k) into dqkr [M,2d] and dv into dqkv[:, 2d:3d]."""
+def attention_bwd(qkr, qkv, o, do, lse, dqkr, dqkv, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False, causal=False, dropout_p=0.0, seed=0):
+    """Writes dq|dk (wrt the stored rotated q, k) into dqkr [M,2d] and dv into dqkv[:, 2d:3d].  dropout_p, seed: those of the forward."""
     d = H * D
     delta = torch.empty((3, B, H, L), dtype=F32, device=qkr.device)   # delta | -lse | -delta (include/unidisc_hip.h)
     q_ptr, k_ptr, v_ptr = qkr.data_ptr(), qkr.data_ptr() + 2 * d, qkv.data_ptr() + 4 * d
     dq_ptr, dk_ptr, dv_ptr = dqkr.data_ptr(), dqkr.data_ptr() + 2 * d, dqkv.data_ptr() + 4 * d
-    _lib.call("udm_attention_bwd", q_ptr, k_ptr, v_ptr, _p(o), _p(do), _p(lse), _p(delta), dq_ptr, dk_ptr, dv_ptr, _p(sample_ids), _p(doc_ranges), B, H, L, D, 2 * d,
-              2 * d, 3 * d, d, do.stride(0), 2 * d, 2 * d, 3 * d, _attn_flags(q_prescaled, causal), _s())
+    _attn_call("udm_attention_bwd", (q_ptr, k_ptr, v_ptr, _p(o), _p(do), _p(lse), _p(delta), dq_ptr, dk_ptr, dv_ptr, _p(sample_ids), _p(doc_ranges), B, H, L, D, 2 * d,
+                                     2 * d, 3 * d, d, do.stride(0), 2 * d, 2 * d, 3 * d, _attn_flags(q_prescaled, causal)), dropout_p, seed)
 
 
-def attention_fwd_generic(q, k, v, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False, causal=False):
+def attention_fwd_generic(q, k, v, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False, causal=False, dropout_p=0.0, seed=0):
     """q, k, v: separate contiguous bf16 [B*L, H*D] (unit tests)."""
     d = H * D
     o = torch.empty((B * L, d), dtype=BF16, device=q.device)
     lse = torch.empty((B, H, L), dtype=F32, device=q.device)
-    _lib.call("udm_attention_fwd", _p(q), _p(k), _p(v), _p(o), _p(lse), _p(sample_ids), _p(doc_ranges), B, H, L, D, d, d, d, d, _attn_flags(q_prescaled, causal), _s())
+    _attn_call("udm_attention_fwd", (_p(q), _p(k), _p(v), _p(o), _p(lse), _p(sample_ids), _p(doc_ranges), B, H, L, D, d, d, d, d, _attn_flags(q_prescaled, causal)),
+               dropout_p, seed)
     return o, lse
 
 
-def attention_bwd_generic(q, k, v, o, do, lse, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False, causal=False):
+def attention_bwd_generic(q, k, v, o, do, lse, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False, causal=False, dropout_p=0.0, seed=0):
     d = H * D
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
     delta = torch.empty((3, B, H, L), dtype=F32, device=q.device)
-    _lib.call("udm_attention_bwd", _p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), _p(sample_ids), _p(doc_ranges), B, H, L, D, d, d, d, d,
-              d, d, d, d, _attn_flags(q_prescaled, causal), _s())
+    _attn_call("udm_attention_bwd", (_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), _p(sample_ids), _p(doc_ranges), B, H, L, D, d, d, d,
+                                     d, d, d, d, d, _attn_flags(q_prescaled, causal)), dropout_p, seed)
     return dq, dk, dv
 
 
