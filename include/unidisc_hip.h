@@ -176,6 +176,10 @@ int udm_qknorm_rope_bwd(const void* dqkr, const void* qkv, void* dqkv, const flo
  * partial blocks, model_utils.py:716-771); exact = the tile's one document occupies exactly [lo, hi) (such key blocks take the wave-specialised dK/dV
  * kernel).  The forward and dQ are bit-identical with and without it; dK/dV agree to summation order at head dim 128. */
 int udm_attention_doc_ranges(const int64_t* sample_ids, int64_t B, int64_t L, int32_t* ranges, hipStream_t stream);
+/* udm_attention_fwd, score floor of the generated forward (csrc/attention_fwd64.hip, see UDM_ATTN_Q_PRESCALED below): a query's reference exponent starts at 0 and only ever rises (the 8-wave kernels start from the first tile's maximum),
+ * so p = exp2(s - m) of a row ALL of whose base-2 scores lie below -126 leaves fp32's normal range and v_exp_f32 flushes it to zero by construction: l = 0,
+ * O and lse of that row are undefined.  Rows need one score above about -110 (qk-normed operands give |s| of a few tens); rows at -96 are tested
+ * (tests/test_gpu_attention_rowwise.py, family row_offset), the floor itself is not. */
 int udm_attention_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const int64_t* sample_ids, const int32_t* doc_ranges, int64_t B, int64_t H, int64_t L, int64_t D,
                       int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t flags, hipStream_t stream);
 int udm_attention_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, float* delta, void* dq, void* dk,

@@ -18,7 +18,8 @@
 //   - ring: step j+1 has landed (accum waves wait on their DMA before the barrier); the stage refilled after barrier j held step
 //     j-2, last read by Z(j-2) in iteration j-1;
 //   - exchange (double-buffered on j & 1): written by Y(j) in iteration j, read by Z(j) in iteration j+1, rewritten by Y(j+2).
-// Rows past L are clamped by the DMA and neutralised by writing lse = +inf for them (p = ds = 0); keys past L only pollute
+// Rows past L are clamped by the DMA and neutralised by writing lse = +inf for them (p = ds = 0; -inf into the negated plane of the pre-scaled form); the pad
+// is written by EVERY score wave after barrier j, because the pre-scaled form reads it in the same iteration (see `top`).  Keys past L only pollute
 // accumulator columns that are never stored.
 //
 // Measured (B8 H16 L1280 D128, MI355X): 0.27 ms vs 0.39 ms for the single-role kernel.  Per 32-query step the timeline reads
@@ -109,7 +110,10 @@ __device__ __forceinline__ void top(const Ctx& x, char* smem, int j, int jm) {
   __builtin_amdgcn_sched_barrier(0);
   stamp<TIMELINE>(x, j, 1);
   if (ROLE == 1 && j + 1 + PD < x.nsub) issue_sub(x, smem, j + 1 + PD, (jm + 1 + PD) % NST);
-  if (ROLE == 0 && x.wave == 0 && j + 1 < x.nsub && (j + 2) * SUB > x.L && x.lane >= x.L - (j + 1) * SUB && x.lane < 32)   // ragged last step (read at iteration j+1)
+  // ragged last step: the lse of the rows past the end.  EVERY score wave writes it (the same values): with PRE the chains of X(j+1) read this stage in this very
+  // iteration, with no barrier behind the write - a wave is only sure to see its own (LDS operations of one wave complete in order).  Written by wave 0 alone,
+  // waves 1-3 could read the clamped row's lse instead and count query L-1 once more per missing row (found by tests/test_gpu_attention_rowwise.py).
+  if (ROLE == 0 && j + 1 < x.nsub && (j + 2) * SUB > x.L && x.lane >= x.L - (j + 1) * SUB && x.lane < 32)
     *reinterpret_cast<float*>(smem + LD_OFF + ((jm + 1) % NST) * 256 + x.lane * 4) = x.lse_pad;
   stamp<TIMELINE>(x, j, 2);
 }
