@@ -262,6 +262,21 @@ int udm_ddpm_sample_rows_cfg(const void* logits, const void* logits_uncond, cons
                              const float* u, int64_t ldu, uint64_t seed, int64_t* out, int64_t M, int64_t V, int64_t Vt, int64_t mask_id,
                              int restrict_modality, int greedy, hipStream_t stream);
 
+/* ---- zero-shot likelihood scoring: `get_similarity` model_eval.py:268-378, `get_model_likelihood_score` :3569-3609 -------------------
+ * udm_subs_logp_rows: log_p[row] = z[x0[row]] - logsumexp(z over the ids valid for the row) for the rows of a compacted [MASK]-row list (every row is a
+ * [MASK] row; unmasked positions have log p = 0 under SUBS and are never given to the head), with the guidance of `cfg` (:2630-2640) fused in:
+ * z = (1 + w[row]) logits - w[row] logits_uncond in fp32.  logits_uncond / w NULL: z = logits, and log_p is bit-identical to udm_subs_ce_fwd's for the same
+ * all-masked rows (one shared loop).  Valid ids, mask_id and the -1e6 of an invalid x0 as in udm_subs_ce_fwd; columns outside the valid range never influence
+ * the result (they may hold anything).  logits / logits_uncond: bf16 [M, ld], 16-byte aligned, ld a multiple of 8.  M = 0 is a no-op. */
+int udm_subs_logp_rows(const void* logits, const void* logits_uncond, const float* w, int64_t ld, const int64_t* x0, const int64_t* modality, float* log_p,
+                       int64_t M, int64_t V, int64_t Vt, int64_t mask_id, int restrict_modality, hipStream_t stream);
+/* udm_likelihood_scores: per-sample scores (:358-370) from those log-probabilities.  rows: the ascending flat indices s L + l of the n contributing rows
+ * (sample s owns one contiguous segment); w_std[s] = dsigma / expm1(sigma); valid_count[s] = number of non-pad positions (fp32).
+ * unweighed[s] = sum(-log_p) / valid_count[s], weighted[s] = sum(-log_p w_std[s]) / valid_count[s].  One workgroup per sample, fixed summation order, no
+ * atomics (two runs are bit-identical); a sample without rows gives 0 / count, valid_count = 0 gives NaN as in the reference. */
+int udm_likelihood_scores(const float* log_p, const int64_t* rows, const float* w_std, const float* valid_count, float* weighted, float* unweighed, int64_t n,
+                          int64_t S, int64_t L, hipStream_t stream);
+
 /* `maskgit` predictor, per [MASK] row (`_maskgit_update` model_eval.py:3069-3074): x ~ Categorical(exp(SUBS log-probs)) - the exponential race
  * argmax p_i / (1e-10 - log(u_i + 1e-10)), explicit uniforms or Philox(seed) - or x = given[row] (replay of a recorded draw), and out_logp[row] =
  * log p(x).  Guidance (logits_uncond, w) as in udm_ddpm_sample_rows_cfg. */

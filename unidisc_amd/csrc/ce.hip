@@ -58,6 +58,46 @@ __device__ __forceinline__ void block_reduce_ms(float& m, float& s, float* sm, f
   m = M; s = S;
 }
 
+// One pass over a [MASK] row: per-thread online (max, sum-exp) over the ids of [lo, hi) minus mask_id, 16-byte loads.  GUIDED: the row is
+// z = (1 + gw) zc - gw zu, mixed in fp32 (`cfg`, model_eval.py:2630-2640).  Columns outside the valid range are loaded (whole 8-id groups) and replaced by
+// -inf BEFORE anything is computed from them, so whatever they hold - NaN included - never reaches the result.  Shared by udm_subs_ce_fwd and
+// udm_subs_logp_rows: with GUIDED = false both run exactly these statements.
+template <bool GUIDED>
+__device__ __forceinline__ void row_online_lse(const bf16_t* zc, const bf16_t* zu, float gw, int lo, int hi, int mask_id, float& m, float& s) {
+  const int tid = threadIdx.x;
+  m = -INFINITY; s = 0.f;
+  const int c_begin = (lo / 8) * 8;
+  for (int c = c_begin + tid * 8; c < hi; c += 256 * 8) {
+    uint4 u = *reinterpret_cast<const uint4*>(zc + c);
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+    float v[8];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { v[2 * k] = __uint_as_float(w[k] << 16); v[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u); }
+    if (GUIDED) {
+      uint4 uu = *reinterpret_cast<const uint4*>(zu + c);
+      const uint32_t wu[4] = {uu.x, uu.y, uu.z, uu.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        v[2 * k] = (1.0f + gw) * v[2 * k] - gw * __uint_as_float(wu[k] << 16);
+        v[2 * k + 1] = (1.0f + gw) * v[2 * k + 1] - gw * __uint_as_float(wu[k] & 0xffff0000u);
+      }
+    }
+    float cm = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int id = c + k;
+      const bool ok = id >= lo && id < hi && id != mask_id;
+      v[k] = ok ? v[k] : -INFINITY;
+      cm = fmaxf(cm, v[k]);
+    }
+    if (cm > m) { s = (m == -INFINITY) ? 0.f : s * __expf(m - cm); m = cm; }
+    if (m != -INFINITY) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) s += __expf(v[k] - m);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void subs_ce_fwd_kernel(CeArgs a) {
   __shared__ float sm[4], ss[4];
   const long row = blockIdx.x;
@@ -70,28 +110,8 @@ __global__ __launch_bounds__(256) void subs_ce_fwd_kernel(CeArgs a) {
   int lo, hi;
   valid_range(a, row, lo, hi);
   const bf16_t* z = a.logits + row * a.ld;
-  float m = -INFINITY, s = 0.f;
-  const int c_begin = (lo / 8) * 8;
-  for (int c = c_begin + tid * 8; c < hi; c += 256 * 8) {
-    uint4 u = *reinterpret_cast<const uint4*>(z + c);
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-    float v[8];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { v[2 * k] = __uint_as_float(w[k] << 16); v[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u); }
-    float cm = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int id = c + k;
-      const bool ok = id >= lo && id < hi && id != a.mask_id;
-      v[k] = ok ? v[k] : -INFINITY;
-      cm = fmaxf(cm, v[k]);
-    }
-    if (cm > m) { s = (m == -INFINITY) ? 0.f : s * __expf(m - cm); m = cm; }
-    if (m != -INFINITY) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) s += __expf(v[k] - m);
-    }
-  }
+  float m, s;
+  row_online_lse<false>(z, nullptr, 0.f, lo, hi, a.mask_id, m, s);
   block_reduce_ms(m, s, sm, ss);
   if (tid == 0) {
     const float lse = m + __logf(s);
@@ -99,6 +119,68 @@ __global__ __launch_bounds__(256) void subs_ce_fwd_kernel(CeArgs a) {
     const float zx = x0_ok ? bf2f(z[x0]) : NEG;
     a.lse[row] = lse;
     a.log_p[row] = zx - lse;
+  }
+}
+
+// log p(x0) of the rows of a compacted [MASK]-row list, with classifier-free guidance mixed in (likelihood scoring: `get_similarity`,
+// model_eval.py:268-378 - `cfg` :2630-2640, `_subs_parameterization` model.py:621-658, the gather :358).  Every row is a [MASK] row (a.xt unused);
+// a.lse unused.  The same valid-id and NEG rules as subs_ce_fwd_kernel.
+template <bool GUIDED>
+__global__ __launch_bounds__(256) void subs_logp_rows_kernel(CeArgs a, const bf16_t* logits_u, const float* w) {
+  __shared__ float sm[4], ss[4];
+  const long row = blockIdx.x;
+  const int tid = threadIdx.x;
+  const long x0 = a.x0[row];
+  int lo, hi;
+  valid_range(a, row, lo, hi);
+  const bf16_t* z = a.logits + row * a.ld;
+  const bf16_t* zu = GUIDED ? logits_u + row * a.ld : nullptr;
+  const float gw = GUIDED ? w[row] : 0.f;
+  float m, s;
+  row_online_lse<GUIDED>(z, zu, gw, lo, hi, a.mask_id, m, s);
+  block_reduce_ms(m, s, sm, ss);
+  if (tid == 0) {
+    const float lse = m + __logf(s);
+    const bool x0_ok = x0 >= lo && x0 < hi && x0 != a.mask_id && x0 >= 0 && x0 < a.V;
+    float zx = NEG;
+    if (x0_ok) zx = GUIDED ? (1.0f + gw) * bf2f(z[x0]) - gw * bf2f(zu[x0]) : bf2f(z[x0]);
+    a.log_p[row] = zx - lse;
+  }
+}
+
+// Per-sample likelihood score from the per-row log-probabilities (model_eval.py:358-370): rows[] holds the ascending flat indices s L + l of the rows that
+// contribute, so sample s owns one contiguous segment of it; every other position of the sample has log p = 0 (unmasked, padding or conditioning).
+//   unweighed[s] = sum(-log_p) / valid_count[s],   weighted[s] = sum(-log_p w_std[s]) / valid_count[s]
+// One workgroup per sample, a fixed summation order (thread-strided partial sums, butterfly per wave, the four waves in order), no atomics: two runs are
+// bit-identical.  No rows: 0 / count; count = 0: NaN, as the reference's 0 / 0.
+__global__ __launch_bounds__(256) void likelihood_scores_kernel(const float* log_p, const int64_t* rows, const float* w_std, const float* valid_count,
+                                                                float* weighted, float* unweighed, long n, long L) {
+  __shared__ float su[4], sw[4];
+  const long smp = blockIdx.x;
+  const int tid = threadIdx.x;
+  auto lower_bound = [&](long key) {   // first index with rows[i] >= key
+    long a = 0, b = n;
+    while (a < b) {
+      const long mid = (a + b) >> 1;
+      if (rows[mid] < key) a = mid + 1; else b = mid;
+    }
+    return a;
+  };
+  const long beg = lower_bound(smp * L), end = lower_bound((smp + 1) * L);
+  const float ws = w_std[smp];
+  float u = 0.f, wv = 0.f;
+  for (long i = beg + tid; i < end; i += 256) {
+    const float nl = -log_p[i];
+    u += nl;
+    wv += nl * ws;
+  }
+  u = wave_sum(u); wv = wave_sum(wv);
+  if ((tid & 63) == 0) { su[tid >> 6] = u; sw[tid >> 6] = wv; }
+  __syncthreads();
+  if (tid == 0) {
+    const float cnt = valid_count[smp];
+    unweighed[smp] = (((su[0] + su[1]) + su[2]) + su[3]) / cnt;
+    weighted[smp] = (((sw[0] + sw[1]) + sw[2]) + sw[3]) / cnt;
   }
 }
 
@@ -207,6 +289,33 @@ extern "C" int udm_subs_ce_bwd(void* logits, int64_t ld, const int64_t* x0, cons
   a.narrow_txt_rows = (int)narrow_txt_rows;
   hipLaunchKernelGGL(subs_ce_bwd_kernel, dim3((unsigned)M), dim3(256), 0, stream, a);
   UDM_CHECK_LAUNCH("udm_subs_ce_bwd");
+  return 0;
+}
+
+extern "C" int udm_subs_logp_rows(const void* logits, const void* logits_uncond, const float* w, int64_t ld, const int64_t* x0, const int64_t* modality,
+                                  float* log_p, int64_t M, int64_t V, int64_t Vt, int64_t mask_id, int restrict_modality, hipStream_t stream) {
+  if (M == 0) return 0;
+  if (int rc = check("udm_subs_logp_rows", logits, M, V, ld, Vt, mask_id)) return rc;
+  UDM_CHECK_ARG(x0 && log_p, "udm_subs_logp_rows: null pointer");
+  UDM_CHECK_ARG(!restrict_modality || modality, "udm_subs_logp_rows: restrict_modality needs the per-row modality");
+  UDM_CHECK_ARG((logits_uncond == nullptr) == (w == nullptr), "udm_subs_logp_rows: guidance needs both the unconditional logits and the per-row weights");
+  UDM_CHECK_ARG(((uintptr_t)logits_uncond % 16) == 0, "udm_subs_logp_rows: logits_uncond must be 16-byte aligned");
+  CeArgs a{(bf16_t*)logits, (long)ld, x0, nullptr, modality, log_p, nullptr, nullptr, (int)M, (int)V, (int)Vt, (int)mask_id, restrict_modality};
+  if (logits_uncond)
+    hipLaunchKernelGGL(subs_logp_rows_kernel<true>, dim3((unsigned)M), dim3(256), 0, stream, a, (const bf16_t*)logits_uncond, w);
+  else
+    hipLaunchKernelGGL(subs_logp_rows_kernel<false>, dim3((unsigned)M), dim3(256), 0, stream, a, (const bf16_t*)nullptr, (const float*)nullptr);
+  UDM_CHECK_LAUNCH("udm_subs_logp_rows");
+  return 0;
+}
+
+extern "C" int udm_likelihood_scores(const float* log_p, const int64_t* rows, const float* w_std, const float* valid_count, float* weighted, float* unweighed,
+                                     int64_t n, int64_t S, int64_t L, hipStream_t stream) {
+  UDM_CHECK_ARG(n >= 0 && S > 0 && L > 0, "udm_likelihood_scores: bad shape n=%ld S=%ld L=%ld", (long)n, (long)S, (long)L);
+  UDM_CHECK_ARG(n == 0 || (log_p && rows), "udm_likelihood_scores: null row list");
+  UDM_CHECK_ARG(w_std && valid_count && weighted && unweighed, "udm_likelihood_scores: null pointer");
+  hipLaunchKernelGGL(likelihood_scores_kernel, dim3((unsigned)S), dim3(256), 0, stream, log_p, rows, w_std, valid_count, weighted, unweighed, (long)n, (long)L);
+  UDM_CHECK_LAUNCH("udm_likelihood_scores");
   return 0;
 }
 

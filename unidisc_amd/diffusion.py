@@ -1203,3 +1203,254 @@ class Diffusion:
             self.test_metrics.update(losses.nlls, losses.token_mask)
             return None
         raise ValueError(f"Invalid prefix: {prefix}")
+
+    # ---- zero-shot likelihood scoring (model_eval.py:263-652, :3569-3609): the diffusion ELBO of an (image, text) pair as a match score, and the retrieval /
+    # Winoground accuracies built on it.  Under SUBS a position that is not [MASK] in x_t has log p(x0) = 0 (model.py:646-656), so per timestep only the rows
+    # with x_t = [MASK] that are not padding and (unless do_unconditional) not conditioning contribute: the backbone's head runs on exactly those rows
+    # (`forward_masked_logits(plan_ids=...)`), `udm_subs_logp_rows` turns their logits - both halves of a guided pass, mixed in fp32 - into log p(x0), and
+    # `udm_likelihood_scores` sums them per sample.  No [B, L, V] tensor is built.
+    def _pad_token_id(self):
+        pad = getattr(self.tokenizer, "pad_token_id", None) if self.tokenizer is not None else None
+        if pad is None:
+            pad = cfg_get(cfg_get(self.config, "eval", None), "pad_token_id", None)
+        if pad is None:
+            raise ValueError("unidisc_amd.get_similarity: the pad token id comes from tokenizer.pad_token_id or eval.pad_token_id; neither is set")
+        return int(pad)
+
+    def _similarity_refusals(self, batch, what):
+        m = cfg_get(self.config, "model")
+        if self.time_conditioning or cfg_get(m, "force_time_conditioning", False):
+            raise NotImplementedError(f"unidisc_amd.{what}: time_conditioning - the reference scores with sigma = None (model_eval.py:316), a time-conditioned "
+                                      "backbone has no such input")
+        if cfg_get(m, "img_first", False):
+            raise NotImplementedError(f"unidisc_amd.{what}: model.img_first - the [image, text] layout of the scoring branches (model_eval.py:580-627) is not built")
+        if batch is not None and batch.get("sample_ids") is not None:
+            raise NotImplementedError(f"unidisc_amd.{what}: packed sample_ids - the score assumes one (text, image) pair per row (model_eval.py:269)")
+
+    def _similarity_cfg_weight(self, t):
+        """`cfg` (model_eval.py:2630-2640): w = eval.cfg (1 - t) per sample, linspace(0, 10, B) (1 - t) for eval.cfg = -1, the scalar itself under
+        eval.force_cfg_value.  NOT get_cfg_weight: no cfg_min / cfg_max_timestep windows here."""
+        ev = cfg_get(self.config, "eval", None)
+        c = cfg_get(ev, "cfg", None)
+        if cfg_get(ev, "force_cfg_value", False):
+            return torch.full_like(t, float(c), dtype=torch.float32)
+        if c == -1:
+            c = torch.linspace(0, 10, t.shape[0]).to(t.device)
+        return (c * (1 - t)).to(torch.float32)
+
+    def _similarity_times(self, num_timesteps, B, device, randomize):
+        """model_eval.py:277-287: the interior points of linspace(0, 1, T + 2), or sorted uniforms - one set for the batch, or one per sample ([B, T])."""
+        ev = cfg_get(self.config, "eval", None)
+        times = torch.linspace(0, 1, steps=num_timesteps + 2)[1:-1].to(device).to(torch.float32)
+        if randomize and cfg_get(ev, "use_random_timesteps_same_batch", False):
+            times = torch.sort(self._rand(num_timesteps, device=device))[0]
+        if randomize and cfg_get(ev, "use_random_timesteps_diff_batch", False):
+            times = torch.sort(self._rand(B, num_timesteps, device=device))[0]
+        return times
+
+    @torch.no_grad()
+    def _likelihood_scores(self, x0, batch, times, valid, cond_mask, do_unconditional, guided, qxt_batch):
+        """The timestep loop shared by get_similarity and get_model_likelihood_score -> (weighted [T, B], unweighed [T, B]).
+        valid [B, L]: the positions that count (non-pad / attention mask); cond_mask [B, L] or None: the conditioning columns.
+        One `rand(B, L)` draw per timestep in ascending order (q_xt), whatever `eval.similarity_timesteps_per_pass` (k) is: k consecutive timesteps are
+        corrupted one by one and then stacked into one backbone pass of k B rows.  Nothing in the loop reads a device value on the host except the row count
+        that `forward_masked_logits` itself waits for (counted on a side stream while the blocks are queued)."""
+        ev = cfg_get(self.config, "eval", None)
+        B, L = x0.shape
+        T = times.shape[-1]
+        k = max(1, int(cfg_get(ev, "similarity_timesteps_per_pass", 1) or 1))
+        modality = batch["modality"]
+        mask_id = self.mask_index
+        other_id = (mask_id + 1) % self.vocab_size            # any id but [MASK]: marks the rows of plan_ids that need no logits
+        count = valid.sum(dim=-1).to(torch.float32)
+        full_mask = torch.full_like(x0, mask_id)
+        split = bool(cfg_get(ev, "split_cfg_batches", False))
+        out_w, out_u = [], []
+        record = getattr(self, "_similarity_trace", None)   # tests: a list that receives every timestep's t, x_t, model inputs, row selection and weights
+        for i0 in range(0, T, k):
+            steps = range(i0, min(i0 + k, T))
+            conds, unconds, plans, wstds, ws = [], [], [], [], []
+            for i in steps:
+                t = times[:, i] if times.dim() == 2 else times[i].expand(B)
+                sigma, dsigma = self.noise(t)
+                move_chance = 1 - torch.exp(-sigma[:, None])
+                xt = self.q_xt(x0, move_chance, batch=qxt_batch)
+                contributes = (xt == mask_id) & valid
+                if cond_mask is not None and not do_unconditional:
+                    contributes = contributes & ~cond_mask
+                conds.append(xt if (do_unconditional or cond_mask is None) else torch.where(cond_mask, x0, xt))
+                plans.append(torch.where(contributes, full_mask, torch.full_like(x0, other_id)))
+                wstds.append((dsigma / torch.expm1(sigma)).to(torch.float32))
+                if guided:
+                    unconds.append(torch.where(cond_mask, full_mask, xt))
+                    ws.append(self._similarity_cfg_weight(t))
+                if record is not None:
+                    record.append(dict(t=t, xt=xt, cond=conds[-1], uncond=unconds[-1] if guided else None, contributes=contributes,
+                                       w=ws[-1] if guided else None))
+            kk = len(conds)
+            cond, plan = torch.cat(conds, 0), torch.cat(plans, 0)
+            mod_k = modality.repeat(kk, 1) if modality is not None else None
+            logits_u = None
+            if not guided:
+                logits, rows, n = self.backbone.forward_masked_logits(cond, None, modality=mod_k, plan_ids=plan)
+            elif split:   # two passes of k B rows, the head on the same positions of both (as _guided_masked_logits)
+                logits, rows, n = self.backbone.forward_masked_logits(cond, None, modality=mod_k, plan_ids=plan)
+                logits_u, _, n_u = self.backbone.forward_masked_logits(torch.cat(unconds, 0), None, modality=mod_k, plan_ids=plan)
+                assert n_u == n
+            else:         # one pass over [cond ; uncond]: the stable partition lists the rows of the first half, then the same positions of the second
+                both, rows, n2 = self.backbone.forward_masked_logits(torch.cat([cond, torch.cat(unconds, 0)], 0), None,
+                                                                     modality=torch.cat([mod_k, mod_k], 0) if mod_k is not None else None,
+                                                                     plan_ids=torch.cat([plan, plan], 0))
+                n = n2 // 2
+                logits, logits_u = both, both[n:]
+            rows_n = rows[:n].contiguous()
+            w_rows = None
+            if guided:
+                w_rows = torch.cat(ws, 0).index_select(0, torch.div(rows_n, L, rounding_mode="floor")).contiguous()
+                logits_u = logits_u[:n]
+            x0_rows = x0.repeat(kk, 1).reshape(-1).index_select(0, rows_n)
+            log_p = K.subs_logp_rows(logits[:n], x0_rows, self._row_modality(rows_n, kk * B, L, mod_k), self.vocab_size, self.text_vocab_size, mask_id,
+                                     self._restrict(), logits_u=logits_u, w=w_rows)
+            weighted, unweighed = K.likelihood_scores(log_p, rows_n, torch.cat(wstds, 0).contiguous(), count.repeat(kk).contiguous(), L)
+            out_w.append(weighted.view(kk, B))
+            out_u.append(unweighed.view(kk, B))
+        return torch.cat(out_w, 0), torch.cat(out_u, 0)
+
+    @torch.no_grad()
+    def get_similarity(self, x0, batch, num_timesteps=None, txt_cond=True, return_unweighed=False, do_unconditional=False):
+        """model_eval.py:268-378 (nested in `zero_shot_eval_step` there): the score [B] of every row of x0 = [text ; image] - the mean over `num_timesteps`
+        of sum_l(-log p(x0_l | x_t) dsigma / expm1(sigma)) / #non-pad (or without the weight: `return_unweighed` / eval.return_unweighed_sim) over the positions
+        that are not padding and not conditioned on (text conditions when `txt_cond`, the image otherwise; `do_unconditional`: nothing does).  Lower = better
+        match.  With eval.cfg the logits are z = (1 + w) l_cond - w l_uncond (`cfg` :2630-2640).  A row without non-pad tokens scores NaN, as there."""
+        if self.parameterization == "ar":
+            raise ValueError("unidisc_amd.get_similarity is the diffusion score; parameterization=ar uses get_similarity_ar")
+        self._similarity_refusals(batch, "get_similarity")
+        ev = cfg_get(self.config, "eval", None)
+        m = cfg_get(self.config, "model")
+        return_unweighed = return_unweighed or bool(cfg_get(ev, "return_unweighed_sim", False))
+        num_timesteps = num_timesteps or cfg_get(cfg_get(self.config, "sampling", None), "steps", None)
+        if not num_timesteps:
+            raise ValueError("unidisc_amd.get_similarity: num_timesteps is not given and sampling.steps is not set")
+        B = batch["modality"].shape[0]
+        times = self._similarity_times(int(num_timesteps), B, x0.device, randomize=True)
+        do_unconditional = do_unconditional or bool(cfg_get(ev, "do_unconditional", False))
+        cond_mask = torch.zeros_like(x0, dtype=torch.bool)
+        if txt_cond:
+            cond_mask[:, :cfg_get(m, "txt_length")] = True
+        else:
+            cond_mask[:, cfg_get(m, "txt_length"):] = True
+        valid = x0 != self._pad_token_id()
+        weighted, unweighed = self._likelihood_scores(x0, batch, times, valid, cond_mask, do_unconditional, cfg_get(ev, "cfg", None) is not None, batch)
+        return (unweighed if return_unweighed else weighted).mean(dim=0)
+
+    @torch.no_grad()
+    def get_model_likelihood_score(self, batch, num_timesteps=100, return_unweighed=True):
+        """model_eval.py:3569-3609: the unconditional form on batch['input_ids'] - every position of batch['attention_mask'] counts, no guidance."""
+        if self.parameterization == "ar":
+            raise ValueError("unidisc_amd.get_model_likelihood_score is the diffusion score (parameterization=subs)")
+        self._similarity_refusals(batch, "get_model_likelihood_score")
+        x0 = batch["input_ids"]
+        times = self._similarity_times(int(num_timesteps), x0.shape[0], x0.device, randomize=False)
+        weighted, unweighed = self._likelihood_scores(x0, batch, times, batch["attention_mask"].bool(), None, True, False, None)
+        return (unweighed if return_unweighed else weighted).mean(dim=0)
+
+    @torch.no_grad()
+    def get_similarity_ar(self, x0, batch, txt_cond=True, do_unconditional=False, **kwargs):
+        """model_eval.py:380-422 (AR baseline): mean next-token NLL over the non-pad positions of the whole row (`do_unconditional`), of the image part
+        (`txt_cond`) or of the text part.  Runs on `Diffusion.forward`."""
+        if kwargs.get("img_first", False):
+            raise NotImplementedError("unidisc_amd.get_similarity_ar: img_first - the [image, text] order (model_eval.py:383-386) is not built")
+        ev = cfg_get(self.config, "eval", None)
+        Lt = cfg_get(cfg_get(self.config, "model"), "txt_length")
+        do_unconditional = do_unconditional or bool(cfg_get(ev, "do_unconditional", False))
+        mod = batch["modality"]
+        model_output = self.forward(x=x0, sigma=None, modality=mod)        # eval.cfg is not applied to AR scores (:392-393)
+        x0 = x0[:, 1:]
+        attention_mask = x0 != self._pad_token_id()
+        log_p_theta = model_output.float().gather(-1, x0[:, :, None])[:, :, 0]
+        txt_sl, img_sl = slice(None, Lt - 1), slice(Lt - 1, None)
+        nll = (-log_p_theta * attention_mask).sum(dim=-1) / attention_mask.sum(dim=-1)
+        txt_nll = (-log_p_theta[:, txt_sl] * attention_mask[:, txt_sl]).sum(dim=-1) / attention_mask[:, txt_sl].sum(dim=-1)
+        img_nll = (-log_p_theta[:, img_sl] * attention_mask[:, img_sl]).sum(dim=-1) / attention_mask[:, img_sl].sum(dim=-1)
+        if do_unconditional:
+            return nll
+        return img_nll if txt_cond else txt_nll
+
+    def _zero_shot_update(self, name, value):
+        """running means as plain sums on the object (the reference keeps torchmetrics objects: model_setup.py:241-246)"""
+        acc = self.__dict__.setdefault("zero_shot_metrics", {})
+        s, n = acc.get(name, (0.0, 0))
+        acc[name] = (s + float(value), n + 1)
+
+    def zero_shot_metric(self, name):
+        s, n = self.__dict__.get("zero_shot_metrics", {}).get(name, (0.0, 0))
+        return s / n if n else float("nan")
+
+    @torch.no_grad()
+    def zero_shot_eval_step(self, batch, batch_idx):
+        """model_eval.py:263-652, the token-level branches: Winoground-style (data.train = "facebook/winoground": the four token tensors
+        input_ids_{0,1}_{0,1} = caption i with image j are given in the batch) and DataComp-style retrieval (anything else) in both eval.only_one_correct
+        forms.  Returns the dict of this batch's accuracies (and per-row flags); the running means are `zero_shot_metric(name)`."""
+        ev = cfg_get(self.config, "eval", None)
+        m = cfg_get(self.config, "model")
+        dataset_name = cfg_get(cfg_get(self.config, "data"), "train", None)
+        if cfg_get(ev, "wino_chameleon", False):
+            raise NotImplementedError("unidisc_amd.zero_shot_eval_step: eval.wino_chameleon - scoring with a Chameleon model (model_eval.py:424-466) is outside this project")
+        if dataset_name == "nlphuji/flickr30k":
+            raise NotImplementedError("unidisc_amd.zero_shot_eval_step: the flickr30k captioning / CIDEr branch (model_eval.py:468-478) needs a VAE and a text decoder")
+        self._similarity_refusals(batch, "zero_shot_eval_step")
+        if "modality_mask" not in batch:   # zero_shot_update_batch, model.py:154
+            batch = dict(batch, modality_mask=F.one_hot(batch["modality"], num_classes=2).to(torch.bool))
+        ar = self.parameterization == "ar"
+        Lt = cfg_get(m, "txt_length")
+        if dataset_name == "facebook/winoground":
+            a = {(i, j): batch[f"input_ids_{i}_{j}"] for i in (0, 1) for j in (0, 1)}
+            results_cond, out = {}, {}
+            for mode in ("image", "text", "group"):
+                do_unconditional = mode == "group"
+                txt_cond = mode != "text"
+                if ar:
+                    if mode == "text":
+                        raise NotImplementedError("unidisc_amd.zero_shot_eval_step: the AR text mode scores img_first sequences (model_eval.py:519), which is not built")
+                    s = {ij: self.get_similarity_ar(x, batch, txt_cond=False, do_unconditional=do_unconditional) for ij, x in a.items()}
+                else:
+                    s = {ij: self.get_similarity(x, batch, txt_cond=txt_cond, do_unconditional=do_unconditional) for ij, x in a.items()}
+                # s[(i, j)]: caption i with image j; lower is better (:506-514)
+                text_ok = torch.logical_and(s[0, 0] < s[1, 0], s[1, 1] < s[0, 1])
+                image_ok = torch.logical_and(s[0, 0] < s[0, 1], s[1, 1] < s[1, 0])
+                out[f"scores_{mode}"] = torch.stack([s[0, 0], s[0, 1], s[1, 0], s[1, 1]])
+                if mode == "text":
+                    results_cond["text"] = text_ok
+                elif mode == "image":
+                    results_cond["image"] = image_ok
+                elif cfg_get(ev, "wino_group_conditional", False):
+                    results_cond["group"] = torch.logical_and(results_cond["text"], results_cond["image"])
+                else:
+                    results_cond["group"] = torch.logical_and(image_ok, text_ok)
+            bsz = a[0, 0].shape[0]
+            for mode, name in (("text", "win_text_accuracy"), ("image", "win_image_accuracy"), ("group", "win_group_accuracy")):
+                out[f"{mode}_correct"] = results_cond[mode]
+                out[name] = results_cond[mode].sum().item() / bsz
+                self._zero_shot_update(name, out[name])
+            return out
+        x0 = batch["input_ids"]
+        sim = self.get_similarity_ar if ar else self.get_similarity
+        if cfg_get(ev, "only_one_correct", False):
+            # rows 1.. get the image of the NEXT row (rolled within rows 1..): only row 0 keeps its own pair (:577-591)
+            x0c = x0.clone()
+            second_half = x0c[1:, Lt:]
+            x0c[1:, Lt:] = torch.cat([second_half[1:], second_half[0].unsqueeze(0)], dim=0)
+            class_sim = sim(x0c, batch, do_unconditional=True)
+            acc = (class_sim.topk(k=1, dim=0, largest=False).indices == 0).float().mean().item()
+            self._zero_shot_update("datacomp_img_acc", acc)
+            return dict(class_sim=class_sim, datacomp_img_acc=acc)
+        x0_txt, x0_img = x0.clone(), x0.clone()
+        x0_txt[:, :Lt] = x0[0, :Lt]      # image retrieval given text: every row gets the first text (:630)
+        x0_img[:, Lt:] = x0[0, Lt:]      # text retrieval given image: every row gets the first image (:633)
+        txt_class_sim = sim(x0_txt, batch, txt_cond=True)
+        img_class_sim = sim(x0_img, batch, txt_cond=True if ar else False)
+        img_acc = (img_class_sim.topk(k=1, dim=0, largest=False).indices == 0).float().mean().item()
+        txt_acc = (txt_class_sim.topk(k=1, dim=0, largest=False).indices == 0).float().mean().item()
+        self._zero_shot_update("datacomp_img_acc", img_acc)
+        self._zero_shot_update("datacomp_txt_acc", txt_acc)
+        return dict(txt_class_sim=txt_class_sim, img_class_sim=img_class_sim, datacomp_img_acc=img_acc, datacomp_txt_acc=txt_acc)

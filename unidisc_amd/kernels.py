@@ -906,6 +906,39 @@ def subs_logprobs(logits, xt, modality, V, Vt, mask_id, restrict, out_dtype=BF16
     return out
 
 
+def subs_logp_rows(logits, x0, modality, V, Vt, mask_id, restrict, logits_u=None, w=None):
+    """log p(x0) fp32 [M] of the rows of a compacted [MASK]-row list (`logits` bf16 [M, ld]); `logits_u` (same shape / stride) + `w` fp32 [M]:
+    classifier-free guidance, z = (1 + w) logits - w logits_u, mixed inside the kernel (udm_subs_logp_rows)."""
+    _chk(logits, BF16, "subs_logp_rows logits"), _chk(x0, torch.int64, "subs_logp_rows x0")
+    M = logits.shape[0]
+    if (logits_u is None) != (w is None):
+        raise ValueError("subs_logp_rows: guidance needs both logits_u and w")
+    if x0.numel() != M or not x0.is_contiguous() or (modality is not None and (modality.numel() != M or modality.dtype != torch.int64 or not modality.is_contiguous())):
+        raise ValueError("subs_logp_rows: x0 / modality must be contiguous int64 tensors with one entry per row")
+    if logits_u is not None:
+        _chk(logits_u, BF16, "subs_logp_rows logits_u"), _chk_packed_f32(w, "subs_logp_rows w", M)
+        if logits_u.shape != logits.shape or logits_u.stride(0) != logits.stride(0):
+            raise ValueError("subs_logp_rows: logits_u must match logits (shape and row stride)")
+    log_p = torch.empty(M, dtype=F32, device=logits.device)
+    if M:
+        _lib.call("udm_subs_logp_rows", _p(logits), _p(logits_u), _p(w), logits.stride(0), _p(x0), _p(modality), _p(log_p), M, V, Vt, mask_id,
+                  1 if restrict else 0, _s())
+    return log_p
+
+
+def likelihood_scores(log_p, rows, w_std, valid_count, L):
+    """(weighted [S], unweighed [S]) likelihood scores from the log-probabilities of the contributing rows (udm_likelihood_scores): `rows` int64 [n] ascending
+    flat indices s L + l, `w_std` / `valid_count` fp32 [S]."""
+    n, S = log_p.numel(), w_std.numel()
+    _chk_packed_f32(log_p, "likelihood_scores log_p"), _chk_packed_f32(w_std, "likelihood_scores w_std"), _chk_packed_f32(valid_count, "likelihood_scores valid_count", S)
+    if rows.dtype != torch.int64 or rows.numel() != n or not rows.is_contiguous():
+        raise TypeError("likelihood_scores: rows must be a contiguous int64 tensor with one index per log-probability")
+    weighted = torch.empty(S, dtype=F32, device=w_std.device)
+    unweighed = torch.empty(S, dtype=F32, device=w_std.device)
+    _lib.call("udm_likelihood_scores", _p(log_p) if n else None, _p(rows) if n else None, _p(w_std), _p(valid_count), _p(weighted), _p(unweighed), n, S, int(L), _s())
+    return weighted, unweighed
+
+
 def diffusion_loss(log_p, w_loss, w_std, attention_mask, modality_mask, *, weighted, full_mask=False, text_w=1.0, img_w=1.0, ratio=None):
     """The loss arithmetic of compute_loss in one launch: (nlls [B, L], coef [B, L] = d loss / d log_p, scalars [8] = loss, txt_loss, img_loss, txt_frac,
     img_frac, valid_frac, txt_count, img_count).  log_p fp32 [B, L]; w_loss / w_std fp32 [B] (weights of the optimised loss and of the reported NLLs);
