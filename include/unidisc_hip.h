@@ -35,7 +35,8 @@ typedef struct ihipStream_t* hipStream_t;
 #define UDM_EPI_BIAS 1      /* C = A·Bᵀ + bias[n]                                          */
 #define UDM_EPI_BIAS_GELU 2 /* u = bf16(A·Bᵀ + bias); C = gelu_tanh(u); aux = bf16(gelu_tanh'(u))   (mlp.0 + GELU: the derivative is saved, not u) */
 #define UDM_EPI_DGELU 3     /* C = (A·Bᵀ) ⊙ aux                              (GELU backward); a non-NULL `bias` is then an fp32 [N]
-                               OUTPUT accumulating the column sums of C (the bias gradient of the upstream Linear)         */
+                               OUTPUT accumulating the column sums of C (the bias gradient of the upstream Linear).  When C is bf16
+                               the sums are of the ROUNDED bf16 values (what the upstream colsum of C would add), of the fp32 values otherwise */
 
 const char* udm_last_error(void);
 /* Diagnostics / A-B switches, none of them needed by a caller (process-global; values as documented in csrc/capi.hip): keys "gemm_tile", "gemm_quad",

@@ -1,5 +1,6 @@
 """Per-kernel parity tests on a real MI355X (pytest -m gpu): every HIP kernel vs a plain-PyTorch fp32 reference
-of the same op (tests/fake_kernels.py, evaluated on CPU copies), called through the C ABI."""
+of the same op (tests/fake_kernels.py, evaluated on CPU copies), called through the C ABI.
+The GEMM family is also held to fp64 element for element on exactly representable operands, out of NaN arenas: tests/test_gpu_gemm_exact.py."""
 import math
 
 import pytest
