@@ -170,6 +170,7 @@ int udm_qknorm_rope_bwd(const void* dqkr, const void* qkv, void* dqkv, const flo
 
 /* ---- attention core: flash_attn_qkvpacked_func models/dit.py:843 / SDPA :826-829 / FlexAttention doc mask :784-812
  * bidirectional softmax(QKᵀ/√D)V; element (b,l,h,:) of a tensor lives at base + (b*L+l)*stride + h*D.
+ * Head dim D = 32 / 64 / 128 / 256 (256: the 8-wave kernels at one workgroup per CU; the backward runs dK and dV as two launches).
  * sample_ids [B,L] (or NULL): attend iff ids equal and != -1 (model_utils.py:740-771).  lse/delta fp32 [B,H,L].
  * doc_ranges int32 [B, ceil(L/64), 8] (or NULL), from udm_attention_doc_ranges on the same sample_ids: per 64-row tile {lo, hi, idmin, idmax, exact, 0, 0, 0}
  * - the [lo, hi) span of positions that can share a sample id with the tile, so the kernels walk only those tiles; the tile's id interval (idmin = -1
@@ -203,7 +204,7 @@ int udm_attention_bwd(const void* q, const void* k, const void* v, const void* o
  * take the same pair: the probabilities never exist in memory, so the forward, the dQ and the dK / dV kernel each regenerate the keep mask Z.
  *   thr = (uint32)(p_drop * 65536 + 0.5) (fp32), s = 1 / (1 - p_drop) (nominal p, as the residual dropout of udm_residual_fwd and as torch).
  *   thr == 0: the call IS udm_attention_fwd / _bwd - the same dispatch (generated programs included), bit-identical results.
- *   thr > 0: always the 8-wave kernels of csrc/attention.hip in their dropout form (head dim 32 / 64 / 128, with or without UDM_ATTN_CAUSAL and
+ *   thr > 0: always the 8-wave kernels of csrc/attention.hip in their dropout form (head dim 32 / 64 / 128 / 256, with or without UDM_ATTN_CAUSAL and
  *   UDM_ATTN_Q_PRESCALED); sample_ids / doc_ranges are an argument error (the reference's FlexAttention path, models/dit.py:784-812, has no dropout), and so
  *   is the "attention_tr_read" = 0 debug switch.
  * Mask: one Philox4x32-10 call (the generator of the residual dropout: key = seed, 64-bit counter, words x y z w) per patch of 2 queries x 4 keys,
@@ -354,7 +355,7 @@ int udm_adamw_step_shadow_ema(float* p, const float* g, float* m, float* v, int6
  * udm_attention_decode: one new token per sequence, every row at position p.  Writes the new key row (k_new: after qk-norm + rope, as udm_qknorm_rope_fwd
  *   leaves it) and value row (v_new) into slot p of k_cache / v_cache (bf16 [B, Lmax, H D]: element (b, l, h, :) at base + (b Lmax + l) H D + h D, the
  *   udm_attention_fwd layout) and o[b, h] = softmax(q Kc[b, :p+1, h]^T) Vc[b, :p+1, h] with q pre-scaled (UDM_ATTN_Q_PRESCALED semantics: the scores are
- *   base-2 exponents).  D = 32 / 64 / 128.  Keys are split over workgroups (fp32 partials in ws, (D + 2) floats per (b, h, split), at most 32 splits;
+ *   base-2 exponents).  D = 32 / 64 / 128 / 256.  Keys are split over workgroups (fp32 partials in ws, (D + 2) floats per (b, h, split), at most 32 splits;
  *   a second launch combines them); ws NULL or too small: fewer splits.  Every other cache slot is left as it is.
  * udm_ar_sample_rows: the token of position pos for each of the R rows, one launch per step: z = logits (or (1 + *w) logits - *w logits_uncond) in fp32,
  *   [MASK] excluded and, with restrict_modality, the ids of the other modality than modality[r, pos] (ids < Vt are text); y = argmax(z + g) (first index

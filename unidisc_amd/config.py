@@ -30,6 +30,7 @@ MODEL_PRESETS = {
     "plumbing": dict(hidden_size=256, n_heads=4, cond_dim=128, n_blocks=2),          # BASELINE configs[0]
     "small": dict(hidden_size=768, n_heads=12, cond_dim=128, n_blocks=12),           # UniDisc-S, ~115 M non-embedding
     "extra_large": dict(hidden_size=2048, n_heads=16, cond_dim=128, n_blocks=24),    # UniDisc 1.4 B
+    "xxl": dict(hidden_size=4096, n_heads=16, cond_dim=128, n_blocks=30),            # configs/model/xxl.yaml, ~6.4 B: head dim 256
 }
 
 

@@ -21,6 +21,10 @@ namespace {
 
 constexpr int BQ = 128;   // query rows per block (4 waves x 32)
 constexpr int BKV = 64;   // keys per tile
+// Workgroups per CU the forward and dQ kernels are compiled for.  D = 256: the four 32 KiB stages leave room for one workgroup per CU anyway (132 096 B of
+// 163 840), and O^T / dQ^T (128 registers) plus the Q (and dO) fragments (64 / 128) need more than the 256 registers a wave has at two per SIMD.
+template <int D>
+constexpr int ATTN_WGS = (D == 256) ? 1 : 2;
 
 __global__ __launch_bounds__(256) void attn_doc_ranges_kernel(const int64_t* __restrict__ sid, int* __restrict__ ranges, int L) {
   __shared__ long s_mn[4], s_mx[4];
@@ -139,7 +143,7 @@ __device__ __forceinline__ void drop_words_q(const AttnDrop& dr, uint64_t row_ct
 // Z o P, and 1 / (1 - p) goes onto 1 / l in the epilogue.
 // DR: empty, or AttnDrop - the dropout form takes its parameters as a second by-value argument (AttnArgs is full and its layout is shared with the generated kernels)
 template <int D, bool HAS_SID, bool USE_TR, int ABL = 0, bool CAUSAL = false, typename... DR>   // ABL (timing-only ablations, wrong results): 1 = no softmax VALU, 2 = no MFMAs
-__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a, DR... drop_arg) {
+__global__ __launch_bounds__(256, ATTN_WGS<D>) void attn_fwd_kernel(AttnArgs a, DR... drop_arg) {
   constexpr bool DROP = sizeof...(DR) != 0;
   [[maybe_unused]] const AttnDrop dr = drop_of(drop_arg...);
   extern __shared__ __attribute__((aligned(16))) char smem[];  // K0 | K1 | V0 | V1 | sidk[2][64]   (one array: keeps LDS-DMA waits exact)
@@ -366,7 +370,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a, DR... drop
 // ------------------------------------------------------------------------------------------------
 // DROP: dS = P o (s Z o dP - delta), s = 1 / (1 - p); delta = rowsum(dO o O) needs no change (O is the dropped output).
 template <int D, bool HAS_SID, bool USE_TR, bool CAUSAL = false, typename... DR>   // CAUSAL: the forward's walk (tiles below the diagonal, late query blocks first)
-__global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs a, DR... drop_arg) {
+__global__ __launch_bounds__(256, ATTN_WGS<D>) void attn_bwd_dq_kernel(AttnArgs a, DR... drop_arg) {
   constexpr bool DROP = sizeof...(DR) != 0;
   [[maybe_unused]] const AttnDrop dr = drop_of(drop_arg...);
   extern __shared__ __attribute__((aligned(16))) char smem[];  // K0 | K1 | V0 | V1 | sidk[2][64]
@@ -759,10 +763,22 @@ void launch_bwd(const AttnArgs& a, hipStream_t s) {
   // bound by that one wave's instruction issue (0.39 ms at B8 H16 L1280).  Without a document mask the wave-specialised kernel of
   // attention_dkv_ws.hip (two waves per SIMD with different roles, 0.27 ms) is used instead.  Causal calls keep the single-role kernel (0.30 ms at that
   // shape); dK and dV as two launches at two waves per SIMD measured the same (0.13 + 0.17 ms) and were not kept.
-  constexpr int W = (D == 128) ? 1 : 2;
-  auto kk = attn_bwd_dkv_kernel<D, SID, TR, 3, W, CAUSAL>;
+  // D = 256: dK^T and dV^T together are 256 registers on top of the K / V fragments (128): more than one wave has.  The pass runs as its dK half and its
+  // dV half (MODE 1, 2), each at one wave per SIMD; S is computed by both (80 instead of 64 MFMAs per 32-query step - DESIGN.md "Head dim 256").
+  constexpr int W = (D >= 128) ? 1 : 2;
+  constexpr int MODE_K = (D == 256) ? 1 : 3;   // D = 256: `kk` is the dK half, the dV half follows it
+  auto kk = attn_bwd_dkv_kernel<D, SID, TR, MODE_K, W, CAUSAL>;
   static bool once = false;
   if (!once) { set_lds(kq, lds_q); set_lds(kk, lds_k); once = true; }
+  if constexpr (D == 256) {
+    auto kdv = attn_bwd_dkv_kernel<D, SID, TR, 2, W, CAUSAL>;
+    static bool once_dv = false;
+    if (!once_dv) { set_lds(kdv, lds_k); once_dv = true; }
+    hipLaunchKernelGGL(kq, gq, dim3(256), lds_q, s, a);
+    hipLaunchKernelGGL(kk, gk, dim3(256), lds_k, s, a);
+    hipLaunchKernelGGL(kdv, gk, dim3(256), lds_k, s, a);
+    return;
+  }
   // D = 128, no mask, L % 256 == 0, q pre-scaled: both passes as generated one-wave-per-SIMD programs (round 6: attention_dq64.hip, attention_dkv64.hip)
   // (causal calls take neither generated program nor the wave-specialised dK/dV kernel: none of them has a causal form)
   if (!(D == 128 && !SID && TR && a.q_prescaled && !a.causal && udm_launch_attn_bwd_dq64(&a, s))) hipLaunchKernelGGL(kq, gq, dim3(256), lds_q, s, a);
@@ -794,29 +810,38 @@ void launch_bwd_drop(const AttnArgs& a, const AttnDrop& dr, hipStream_t s) {
   const size_t lds_q = 4 * BKV * D * 2 + 2 * BKV * sizeof(long);
   const size_t lds_k = 4 * BQT * D * 2 + 4 * BQT * sizeof(float) + 2 * BQT * sizeof(long);
   auto kq = attn_bwd_dq_kernel<D, false, true, CAUSAL, AttnDrop>;
-  auto kk = attn_bwd_dkv_kernel<D, false, true, 3, (D == 128) ? 1 : 2, CAUSAL, AttnDrop>;
+  auto kk = attn_bwd_dkv_kernel<D, false, true, (D == 256) ? 1 : 3, (D >= 128) ? 1 : 2, CAUSAL, AttnDrop>;   // D = 256: the dK half (see launch_bwd)
   static bool once = false;
   if (!once) { set_lds(kq, lds_q); set_lds(kk, lds_k); once = true; }
   hipLaunchKernelGGL(kq, gq, dim3(256), lds_q, s, a, dr);
   hipLaunchKernelGGL(kk, gk, dim3(256), lds_k, s, a, dr);
+  if constexpr (D == 256) {
+    auto kdv = attn_bwd_dkv_kernel<D, false, true, 2, 1, CAUSAL, AttnDrop>;
+    static bool once_dv = false;
+    if (!once_dv) { set_lds(kdv, lds_k); once_dv = true; }
+    hipLaunchKernelGGL(kdv, gk, dim3(256), lds_k, s, a, dr);
+  }
 }
 #define ATTN_DISPATCH_DROP(FN, a, dr, D, s)                                                        \
   do {                                                                                            \
-    if (D == 128) { if (a.causal) FN<128, true>(a, dr, s); else FN<128, false>(a, dr, s); }       \
+    if (D == 256) { if (a.causal) FN<256, true>(a, dr, s); else FN<256, false>(a, dr, s); }       \
+    else if (D == 128) { if (a.causal) FN<128, true>(a, dr, s); else FN<128, false>(a, dr, s); }  \
     else if (D == 64) { if (a.causal) FN<64, true>(a, dr, s); else FN<64, false>(a, dr, s); }     \
     else { if (a.causal) FN<32, true>(a, dr, s); else FN<32, false>(a, dr, s); }                  \
   } while (0)
 
 #define ATTN_DISPATCH(FN, a, D, sid, tr, s)                                    \
   do {                                                                         \
-    if (D == 128) { if (sid) { if (tr) FN<128, true, true>(a, s); else FN<128, true, false>(a, s); } else { if (tr) FN<128, false, true>(a, s); else FN<128, false, false>(a, s); } } \
+    if (D == 256) { if (sid) { if (tr) FN<256, true, true>(a, s); else FN<256, true, false>(a, s); } else { if (tr) FN<256, false, true>(a, s); else FN<256, false, false>(a, s); } } \
+    else if (D == 128) { if (sid) { if (tr) FN<128, true, true>(a, s); else FN<128, true, false>(a, s); } else { if (tr) FN<128, false, true>(a, s); else FN<128, false, false>(a, s); } } \
     else if (D == 64) { if (sid) { if (tr) FN<64, true, true>(a, s); else FN<64, true, false>(a, s); } else { if (tr) FN<64, false, true>(a, s); else FN<64, false, false>(a, s); } } \
     else { if (sid) { if (tr) FN<32, true, true>(a, s); else FN<32, true, false>(a, s); } else { if (tr) FN<32, false, true>(a, s); else FN<32, false, false>(a, s); } } \
   } while (0)
 // causal: never with sample ids (rejected at the entry points)
 #define ATTN_DISPATCH_CAUSAL(FN, a, D, tr, s)                                                     \
   do {                                                                                            \
-    if (D == 128) { if (tr) FN<128, false, true, true>(a, s); else FN<128, false, false, true>(a, s); } \
+    if (D == 256) { if (tr) FN<256, false, true, true>(a, s); else FN<256, false, false, true>(a, s); } \
+    else if (D == 128) { if (tr) FN<128, false, true, true>(a, s); else FN<128, false, false, true>(a, s); } \
     else if (D == 64) { if (tr) FN<64, false, true, true>(a, s); else FN<64, false, false, true>(a, s); } \
     else { if (tr) FN<32, false, true, true>(a, s); else FN<32, false, false, true>(a, s); }          \
   } while (0)
@@ -837,7 +862,7 @@ int check_drop(const char* name, float p_drop, uint64_t seed, const void* sample
 
 int check_common(const char* name, int64_t B, int64_t H, int64_t L, int64_t D, int64_t qs, int64_t ks, int64_t vs) {
   UDM_CHECK_ARG(B > 0 && H > 0 && L > 0, "%s: empty problem", name);
-  UDM_CHECK_ARG(D == 32 || D == 64 || D == 128, "%s: head_dim %ld unsupported (32, 64, 128)", name, (long)D);
+  UDM_CHECK_ARG(D == 32 || D == 64 || D == 128 || D == 256, "%s: head_dim %ld unsupported (32, 64, 128, 256)", name, (long)D);
   UDM_CHECK_ARG(qs % 8 == 0 && ks % 8 == 0 && vs % 8 == 0, "%s: row strides must be multiples of 8 elements", name);
   UDM_CHECK_ARG(B * H * ((L + 127) / 128) < (1LL << 31), "%s: grid too large", name);
   return 0;

@@ -9,13 +9,21 @@ using namespace udm;
 
 template <int D>
 __device__ __forceinline__ int swz(int row) {
-  if (D == 128) return (row & 15) ^ ((row & 3) << 2);
+  // D == 256: a row is 512 B = two bank wraps, so the bank of a slot depends on its low four bits alone and the head-dim-128 permutation of those
+  // bits serves unchanged (bit 4 of the slot, the 256-byte half of the row, is never touched): the same conflict-free ds_read_b128 / ds_read_b64_tr_b16
+  // patterns, and still an involution on the 32 slots
+  if (D == 128 || D == 256) return (row & 15) ^ ((row & 3) << 2);
   if (D == 64) { int x = row >> 1; return (x & 7) ^ ((x & 1) << 2); }
   return (row >> 2) & 3;  // D == 32
 }
 // byte offset of 16-byte slot `slot` of row `row` in a [rows][D] bf16 tile
 template <int D>
-__device__ __forceinline__ int tile_off(int row, int slot) { return row * (2 * D) + ((slot ^ swz<D>(row)) << 4); }
+__device__ __forceinline__ int tile_off(int row, int slot) {
+  // D == 256: the swizzle never touches bit 4 of the slot, so the two 256-byte halves of a row differ by a constant - written out, because every fragment
+  // address that is (per-lane register + immediate) instead of a register of its own is a register the one-wave-per-SIMD kernels do not spill
+  if constexpr (D == 256) return row * 512 + (((slot & 15) ^ swz<D>(row)) << 4) + ((slot >> 4) << 8);
+  else return row * (2 * D) + ((slot ^ swz<D>(row)) << 4);
+}
 
 __device__ __forceinline__ bf16x8_t lds_frag(const char* base, int off) { return *reinterpret_cast<const bf16x8_t*>(base + off); }
 
@@ -27,10 +35,22 @@ __device__ __forceinline__ bf16x8_t lds_frag_T(const char* tile, int r0, int c0,
   const int hi = lane >> 5;
   if (USE_TR) {
     const int g1 = (lane >> 4) & 1, p = lane & 15;
+    int o1, o2;
+    if constexpr (D == 256) {
+      // r0 is a multiple of 16 and c0 of 32 (compile-time constants at every call site): the per-lane part of the two addresses depends on (c0 >> 5) & 3 alone,
+      // 8 registers per tile; the chunk (r0), the 256-byte half (c0 >> 7) and the stage are immediates
+      const int rl = 4 * hi + (p >> 2), sl = ((c0 >> 5) & 3) * 4 + g1 * 2 + ((p & 3) >> 1), by = (p & 1) * 8;
+      const int l1 = rl * 512 + ((sl ^ swz<D>(rl)) << 4) + by;
+      const int l2 = (rl + 8) * 512 + ((sl ^ swz<D>(rl + 8)) << 4) + by;
+      const int k = r0 * 512 + (c0 >> 7) * 256;
+      o1 = l1 + k;
+      o2 = l2 + k;
+    } else {
     const int row = r0 + 4 * hi + (p >> 2);
     const int col = c0 + g1 * 16 + (p & 3) * 4;
-    const int o1 = tile_off<D>(row, col >> 3) + (col & 7) * 2;
-    const int o2 = tile_off<D>(row + 8, col >> 3) + (col & 7) * 2;
+    o1 = tile_off<D>(row, col >> 3) + (col & 7) * 2;
+    o2 = tile_off<D>(row + 8, col >> 3) + (col & 7) * 2;
+    }
     s16x4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((UDM_LDS s16x4_t*)(tile + o1));
     s16x4_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((UDM_LDS s16x4_t*)(tile + o2));
     s16x8_t r = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);

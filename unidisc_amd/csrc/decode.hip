@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(DecArgs a) {
 }
 
 template <int D>
-__global__ __launch_bounds__(128) void attn_decode_combine_kernel(DecArgs a) {
+__global__ __launch_bounds__(D > 128 ? D : 128) void attn_decode_combine_kernel(DecArgs a) {
   const int bh = blockIdx.x, t = threadIdx.x;
   if (t >= D) return;
   const int b = bh / a.H, h = bh % a.H;
@@ -387,7 +387,7 @@ extern "C" int udm_attention_decode(const void* q, const void* k_new, const void
                                     int64_t B, int64_t H, int64_t D, int64_t Lmax, int64_t p, int64_t q_stride, int64_t k_stride, int64_t v_stride,
                                     int64_t o_stride, hipStream_t stream) {
   UDM_CHECK_ARG(q && k_new && v_new && k_cache && v_cache && o, "udm_attention_decode: null pointer");
-  UDM_CHECK_ARG(D == 32 || D == 64 || D == 128, "udm_attention_decode: head dim %ld (32 / 64 / 128)", (long)D);
+  UDM_CHECK_ARG(D == 32 || D == 64 || D == 128 || D == 256, "udm_attention_decode: head dim %ld (32 / 64 / 128 / 256)", (long)D);
   UDM_CHECK_ARG(B >= 1 && H >= 1 && Lmax >= 1 && p >= 0 && p < Lmax && Lmax < (1L << 30) && B * H < (1L << 30), "udm_attention_decode: bad shape B=%ld H=%ld Lmax=%ld p=%ld",
                 (long)B, (long)H, (long)Lmax, (long)p);
   UDM_CHECK_ARG(q_stride % 8 == 0 && k_stride % 8 == 0 && v_stride % 8 == 0 && o_stride % 8 == 0 && q_stride >= H * D && k_stride >= H * D &&
@@ -410,6 +410,7 @@ extern "C" int udm_attention_decode(const void* q, const void* k_new, const void
   switch (D) {
     case 32: hipLaunchKernelGGL(attn_decode_kernel<32>, grid, dim3(256), 0, stream, a); break;
     case 64: hipLaunchKernelGGL(attn_decode_kernel<64>, grid, dim3(256), 0, stream, a); break;
+    case 256: hipLaunchKernelGGL(attn_decode_kernel<256>, grid, dim3(256), 0, stream, a); break;
     default: hipLaunchKernelGGL(attn_decode_kernel<128>, grid, dim3(256), 0, stream, a); break;
   }
   UDM_CHECK_LAUNCH("udm_attention_decode");
@@ -417,6 +418,7 @@ extern "C" int udm_attention_decode(const void* q, const void* k_new, const void
     switch (D) {
       case 32: hipLaunchKernelGGL(attn_decode_combine_kernel<32>, dim3((unsigned)BH), dim3(128), 0, stream, a); break;
       case 64: hipLaunchKernelGGL(attn_decode_combine_kernel<64>, dim3((unsigned)BH), dim3(128), 0, stream, a); break;
+      case 256: hipLaunchKernelGGL(attn_decode_combine_kernel<256>, dim3((unsigned)BH), dim3(256), 0, stream, a); break;   // one thread per output column
       default: hipLaunchKernelGGL(attn_decode_combine_kernel<128>, dim3((unsigned)BH), dim3(128), 0, stream, a); break;
     }
     UDM_CHECK_LAUNCH("udm_attention_decode (combine)");

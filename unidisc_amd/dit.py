@@ -278,8 +278,8 @@ class DIT(nn.Module, _HubMixin):
         self.cond_dim, self.n_blocks = cfg_get(m, "cond_dim"), cfg_get(m, "n_blocks")
         self.norm_type, self.qk_norm = cfg_get(m, "norm_type", "layernorm"), cfg_get(m, "qk_norm", False)
         self.dropout = float(cfg_get(m, "dropout", 0.0) or 0.0)
-        if self.head_dim not in (32, 64, 128):
-            raise NotImplementedError(f"unidisc_amd.DIT: head_dim {self.head_dim} unsupported (32/64/128)")
+        if self.head_dim not in (32, 64, 128, 256):
+            raise NotImplementedError(f"unidisc_amd.DIT: head_dim {self.head_dim} unsupported (32/64/128/256)")
 
         self.vocab_embed = EmbeddingLayer(d, vocab_size)
         self.sigma_map = TimestepEmbedder(self.cond_dim) if self.time_conditioning else None

@@ -803,7 +803,7 @@ def _attn_call(name, args, dropout_p, seed):
 
 
 def attention_fwd(qkr, qkv, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False, causal=False, dropout_p=0.0, seed=0):
-    """q, k from qkr [M,2d] (normalised+rotated), v from qkv [M,3d] columns [2d,3d).  q_prescaled: q holds q * attention_q_scale(D).
+    """q, k from qkr [M,2d] (normalised+rotated), v from qkv [M,3d] columns [2d,3d).  Head dim D = 32 / 64 / 128 / 256.  q_prescaled: q holds q * attention_q_scale(D).
     causal: query i sees keys j <= i (not combinable with sample_ids).  dropout_p, seed: dropout on the softmax probabilities (model.attn_dropout; the mask
     is a function of seed and the element's (b, h, i, j), include/unidisc_hip.h; not combinable with sample_ids)."""
     d = H * D
@@ -1010,7 +1010,7 @@ def attention_decode_ws(B, H, D, device):
 
 def attention_decode(q, k_new, v_new, k_cache, v_cache, p, H, D, out=None, ws=None):
     """o [B, H D] bf16 of one new token per row at position p against the caches [B, Lmax, H D] (q pre-scaled by attention_q_scale(D)); writes k_new / v_new
-    into cache slot p.  q / k_new / v_new / out: 2-D row views (any 16-byte aligned row stride)."""
+    into cache slot p.  q / k_new / v_new / out: 2-D row views (any 16-byte aligned row stride).  D = 32 / 64 / 128 / 256."""
     B, Lmax, d = k_cache.shape
     if out is None:
         out = torch.empty((B, d), dtype=BF16, device=q.device)
