@@ -181,9 +181,10 @@ def _case(K, test, tag, family, B, H, L, D, *, prescaled, causal=False, sample_i
     assert not faults, "\n".join(faults)
 
 
-def _switches(K, fwd64=1, dq64=1, dkv64=1, tr=1, cus=0):
-    """a setter: (True) puts the debug switches of the library where the test wants them, (False) puts them back: the three program switches to -1 (the library's
-    unset state: the environment's choice, or on), the transposing reads on (the library has no other start value), the CU plan to what it was before"""
+def _switches(K, fwd64=1, dq64=1, dkv64=1, tr=1, cus=0, dkv_ws=1):
+    """a setter: (True) puts the debug switches of the library where the test wants them, (False) puts them back: the three program switches and attention_dkv_ws
+    to -1 (the library's unset state: the environment's choice, or on), the transposing reads on (the library has no other start value), the CU plan to what it was
+    before"""
     before = {}
 
     def setter(on):
@@ -192,6 +193,7 @@ def _switches(K, fwd64=1, dq64=1, dkv64=1, tr=1, cus=0):
         K.set_attention_fwd64(fwd64 if on else -1)
         K.set_attention_dq64(dq64 if on else -1)
         K.set_attention_dkv64(dkv64 if on else -1)
+        K.debug_set("attention_dkv_ws", dkv_ws if on else -1)
         K.set_tr_read(bool(tr) if on else True)
         K.gemm_set_cus(cus if on else before.get("cus", 0))
     return setter
@@ -203,8 +205,9 @@ def _switches(K, fwd64=1, dq64=1, dkv64=1, tr=1, cus=0):
 @pytest.mark.parametrize("B,H,L,D", [(2, 3, 100, 32), (2, 3, 384, 64), (2, 3, 640, 128), (1, 1, 200, 128)])
 def test_generic_8wave(K, B, H, L, D, family, prescaled):
     """attn_fwd_kernel / attn_bwd_dq_kernel / attn_bwd_dkv_kernel without a mask (B H is not a multiple of 8: no generated program takes these shapes; at head dim
-    128 dK / dV come from the wave-specialised kernel, or - with attention_tr_read = 0 - from the single-role one).  The 384 x 64 shape also runs without the
-    transposing LDS reads."""
+    128 dK / dV come from the wave-specialised kernel).  The 384 x 64 and the 640 x 128 shape also run with attention_tr_read = 0: every pass is then the
+    USE_TR = false instantiation of its 8-wave kernel - at head dim 128 the single-role dK / dV kernel with the scalar LDS gathers, which is NOT the USE_TR = true
+    instantiation that attention_dkv_ws = 0 selects (test_single_role_dkv_d128 has that one)."""
     assert (B * H) % 8 != 0
     configs = [("", _switches(K))]
     if L == 384 or D == 128 and L == 640:
@@ -263,6 +266,14 @@ def test_wave_specialised_dkv(K, B, H, L, D, prescaled, family):
     generated dQ pass then leaves the planes this kernel starts its score chains from)"""
     configs = [("dkv64_off", _switches(K, 1, 1, 0))]
     _case(K, "test_wave_specialised_dkv", "dkv_ws", family, B, H, L, D, prescaled=prescaled, configs=configs)
+
+
+@pytest.mark.parametrize("prescaled", [True, False])
+@pytest.mark.parametrize("family", R.FAMILIES_SHORT)
+def test_single_role_dkv_d128(K, family, prescaled):
+    """attn_bwd_dkv_kernel<128, no ids, USE_TR = true, both accumulators, one wave per SIMD> without a mask: what head dim 128 falls back to when the
+    wave-specialised kernel is switched off (attention_dkv_ws = 0, UDM_DKV_WS=0), with a ragged last tile and B H = 3"""
+    _case(K, "test_single_role_dkv_d128", "dkv_single", family, 1, 3, 200, 128, prescaled=prescaled, configs=[("dkv_ws0", _switches(K, dkv_ws=0))])
 
 
 # ------------------------------------------------------------------------------------------------ decode

@@ -15,6 +15,8 @@
 // flight under the current tile's MFMAs.  The same swizzle is conflict-free for the ds_read_b128
 // fragment reads and for the transposing reads.
 #include "attention_common.h"
+#include "gemm_quad.h"
+#include <string.h>
 #include <type_traits>
 
 namespace {
@@ -142,7 +144,7 @@ __device__ __forceinline__ void drop_words_q(const AttnDrop& dr, uint64_t row_ct
 // DROP: attention-probability dropout.  Running maximum, row sum and lse come from the undropped probabilities; only the P operand of O^T += V^T P^T is
 // Z o P, and 1 / (1 - p) goes onto 1 / l in the epilogue.
 // DR: empty, or AttnDrop - the dropout form takes its parameters as a second by-value argument (AttnArgs is full and its layout is shared with the generated kernels)
-template <int D, bool HAS_SID, bool USE_TR, int ABL = 0, bool CAUSAL = false, typename... DR>   // ABL (timing-only ablations, wrong results): 1 = no softmax VALU, 2 = no MFMAs
+template <int D, bool HAS_SID, bool USE_TR, bool CAUSAL = false, typename... DR>
 __global__ __launch_bounds__(256, ATTN_WGS<D>) void attn_fwd_kernel(AttnArgs a, DR... drop_arg) {
   constexpr bool DROP = sizeof...(DR) != 0;
   [[maybe_unused]] const AttnDrop dr = drop_of(drop_arg...);
@@ -205,20 +207,17 @@ __global__ __launch_bounds__(256, ATTN_WGS<D>) void attn_fwd_kernel(AttnArgs a, 
   // IDS = false: the walk of a block whose whole key span is its own document - the tile body is then, instruction for instruction, the one of the kernel
   // without sample ids (with the id code merely branched around, the same single-document work ran 16 % slower: 127 vs 110 us at B = 8, L = 1152)
   auto tile = [&](auto st_c, int t, auto ids_c) {
-    constexpr int ST = decltype(st_c)::value;
+    constexpr int st = decltype(st_c)::value;
     constexpr bool IDS = HAS_SID && decltype(ids_c)::value;
     const int kv0 = t * BKV;
-    constexpr int st = (ABL & 4) ? 0 : ST;
     const char* Ks = smem + st * TB;
     const char* Vs = smem + (2 + st) * TB;
     const long* sidk = sid_s + st * BKV;
     const bool id_test = IDS && doc_pair_needs_mask(a.doc_ranges, b, a.L, t, blk_id);   // block-uniform
     if (IDS && id_test && tid < BKV) sid_s[st * BKV + tid] = (kv0 + tid < a.L) ? a.sample_ids[rowbase + kv0 + tid] : -2;
-    if (!(ABL & 4) || t == 0) {
     wait_all_vmem();   // this wave's share of tile t has landed
     __syncthreads();   // ... and everybody's; all waves are also done with tile t-1, so its stage may be refilled
-    }
-    if ((ABL & 4) || t + 1 >= t_end) {
+    if (t + 1 >= t_end) {
     } else if (kv0 + 2 * BKV <= a.L) {   // the next tile is a full one: offsets are precomputed, the tile base is wave-uniform
       plank.issue_full(kbase + (long)(kv0 + BKV) * a.k_stride, smem + (st ^ 1) * TB, wave);
       planv.issue_full(vbase + (long)(kv0 + BKV) * a.v_stride, smem + (2 + (st ^ 1)) * TB, wave);
@@ -246,10 +245,7 @@ __global__ __launch_bounds__(256, ATTN_WGS<D>) void attn_fwd_kernel(AttnArgs a, 
           for (int f = 0; f < 2; ++f) kq[(ks + 2) % 3][f] = lds_frag(Ks, tile_off<D>(f * 32 + l31, (ks + 2) * 2 + hi));
         }
 #pragma unroll
-        for (int f = 0; f < 2; ++f) {
-          if (ABL & 2) { sT[f][ks] += (float)kq[ks % 3][f][0]; continue; }
-          sT[f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kq[ks % 3][f], qf[ks], sT[f], 0, 0, 0);
-        }
+        for (int f = 0; f < 2; ++f) sT[f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kq[ks % 3][f], qf[ks], sT[f], 0, 0, 0);
       }
     }
     const bool diag = CAUSAL && kv0 + BKV - 1 > tile_x * BQ;   // block-uniform: some key of the tile lies past some query of the block
@@ -268,12 +264,6 @@ __global__ __launch_bounds__(256, ATTN_WGS<D>) void attn_fwd_kernel(AttnArgs a, 
         }
     }
     float p[2][16];
-    if (ABL & 1) {
-#pragma unroll
-      for (int f = 0; f < 2; ++f)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) p[f][r] = sT[f][r];
-    } else {
     float mloc = -INFINITY;
 #pragma unroll
     for (int f = 0; f < 2; ++f)
@@ -305,7 +295,6 @@ __global__ __launch_bounds__(256, ATTN_WGS<D>) void attn_fwd_kernel(AttnArgs a, 
         psum += p[f][r];
       }
     lsum += psum;
-    }
     if constexpr (DROP) {   // (after the row sum: l and lse are those of the undropped probabilities)
       uint32_t zw[2];
       drop_words_q(dr, drop_row, kv0, l31 & 1, hi, zw);
@@ -324,7 +313,6 @@ __global__ __launch_bounds__(256, ATTN_WGS<D>) void attn_fwd_kernel(AttnArgs a, 
 #pragma unroll
       for (int i = 0; i < DB; ++i) {
         bf16x8_t vt = lds_frag_T<D, USE_TR>(Vs, cc * 16, i * 32, lane);
-        if (ABL & 2) { oT[i][cc] += (float)vt[0] * (float)pb[0]; continue; }
         oT[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vt, pb, oT[i], 0, 0, 0);
       }
     }
@@ -728,135 +716,114 @@ __global__ __launch_bounds__(256, WAVES) void attn_bwd_dkv_kernel(AttnArgs a, DR
   }
 }
 
-int g_dkv_ws = 1;   // UDM_DKV_WS=0 in the environment selects the single-role dK/dV kernel at head dim 128 too (A/B measurements)
+// ------------------------------------------------------------------------------------------------
+// host: the debug switches, the 8-wave launches, the instantiation dispatcher.  WHICH program runs is attention_plan.h's decision alone.
+// ------------------------------------------------------------------------------------------------
+// The one AttnSwitches of the library.  Start values: the environment's (read once, on first use; variable names and defaults as ever).  udm_debug_set
+// reaches it through udm_attention_debug_set below; -1 puts a key back to the environment's choice.
+struct SwitchKey { const char* key; const char* env; int AttnSwitches::*field; };
+constexpr SwitchKey SWITCH_KEYS[] = {{"attention_fwd64", "UDM_ATTN_FWD64", &AttnSwitches::fwd64}, {"attention_dq64", "UDM_ATTN_DQ64", &AttnSwitches::dq64},
+                                     {"attention_dkv64", "UDM_ATTN_DKV64", &AttnSwitches::dkv64}, {"attention_dkv_ws", "UDM_DKV_WS", &AttnSwitches::dkv_ws},
+                                     {nullptr, "UDM_DKV_PRE", &AttnSwitches::dkv_pre}};   // (no key: an A/B switch of the environment only)
+const AttnSwitches& env_switches() {
+  static const AttnSwitches env = [] {
+    AttnSwitches s;
+    for (const SwitchKey& k : SWITCH_KEYS)
+      if (const char* e = getenv(k.env)) s.*k.field = atoi(e);
+    return s;
+  }();
+  return env;
+}
+AttnSwitches& switches() { static AttnSwitches sw = env_switches(); return sw; }
+struct { unsigned long long *fwd64, *dq64, *dkv64; } g_timeline{};   // diagnostic builds of the generated programs: stamps of the next launches, null = off
 
-template <typename KernT>
-void set_lds(KernT kern, size_t bytes) {
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+int device_cus() {
+  static const int n = [] { int dev = 0, cus = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); return cus; }();
+  return n;
 }
-template <int D, bool SID, bool TR, bool CAUSAL = false>
-void launch_fwd(const AttnArgs& a, hipStream_t s) {
-  dim3 grid(((a.L + BQ - 1) / BQ) * a.H * a.B);
-  const size_t lds = 4 * BKV * D * 2 + 2 * BKV * sizeof(long);
-  auto kern = attn_fwd_kernel<D, SID, TR, 0, CAUSAL>;
+
+// One 8-wave launch of `blocks` workgroups; the kernel's LDS attribute is set on its first use.  dr: nothing, or the AttnDrop of the dropout form.
+template <auto KERN, typename... DR>
+void launch(int blocks, size_t lds, const AttnArgs& a, hipStream_t s, const DR&... dr) {
   static bool once = false;
-  if (!once) { set_lds(kern, lds); once = true; }
-  // head dim 128, no mask, L % 256 == 0, q pre-scaled (the headline path): the one-wave-per-SIMD, 64-queries-per-wave kernel of attention_fwd64.hip
-  // (causal calls stay with this file's kernel: the generated program has no causal form)
-  if (D == 128 && !SID && TR && a.q_prescaled && !a.causal && udm_launch_attn_fwd64(&a, s)) return;
-  if (D == 128 && !SID && TR && !a.causal) {   // UDM_ATTN_ABL=1|2: timing-only ablations of the forward kernel (scripts/bench_attn.py)
-    static const int abl = [] { const char* e = getenv("UDM_ATTN_ABL"); return e ? atoi(e) : 0; }();
-    if (abl == 1) { auto k1 = attn_fwd_kernel<128, false, true, 1>; set_lds(k1, lds); hipLaunchKernelGGL(k1, grid, dim3(256), lds, s, a); return; }
-    if (abl == 2) { auto k2 = attn_fwd_kernel<128, false, true, 2>; set_lds(k2, lds); hipLaunchKernelGGL(k2, grid, dim3(256), lds, s, a); return; }
-    if (abl == 4) { auto k4 = attn_fwd_kernel<128, false, true, 4>; set_lds(k4, lds); hipLaunchKernelGGL(k4, grid, dim3(256), lds, s, a); return; }   // no refills / barriers
-    if (abl == 5) { auto k5 = attn_fwd_kernel<128, false, true, 5>; set_lds(k5, lds); hipLaunchKernelGGL(k5, grid, dim3(256), lds, s, a); return; }   // ... and no softmax
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
+  if (!once) { (void)hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); once = true; }
+  hipLaunchKernelGGL(KERN, dim3(blocks), dim3(256), lds, s, a, dr...);
 }
-template <int D, bool SID, bool TR, bool CAUSAL = false>
-void launch_bwd(const AttnArgs& a, hipStream_t s) {
-  dim3 gq(((a.L + BQ - 1) / BQ) * a.H * a.B), gk(((a.L + 127) / 128) * a.H * a.B);
-  const size_t lds_q = 4 * BKV * D * 2 + 2 * BKV * sizeof(long);
-  const size_t lds_k = 4 * BQT * D * 2 + 4 * BQT * sizeof(float) + 2 * BQT * sizeof(long);
-  auto kq = attn_bwd_dq_kernel<D, SID, TR, CAUSAL>;
-  // D = 128: both accumulators (128 registers) plus K/V operands (64) only fit one wave per SIMD in the single-role kernel, which is then
-  // bound by that one wave's instruction issue (0.39 ms at B8 H16 L1280).  Without a document mask the wave-specialised kernel of
-  // attention_dkv_ws.hip (two waves per SIMD with different roles, 0.27 ms) is used instead.  Causal calls keep the single-role kernel (0.30 ms at that
-  // shape); dK and dV as two launches at two waves per SIMD measured the same (0.13 + 0.17 ms) and were not kept.
-  // D = 256: dK^T and dV^T together are 256 registers on top of the K / V fragments (128): more than one wave has.  The pass runs as its dK half and its
-  // dV half (MODE 1, 2), each at one wave per SIMD; S is computed by both (80 instead of 64 MFMAs per 32-query step - DESIGN.md "Head dim 256").
+// DKV_SINGLE (MODE 3; one wave per SIMD from head dim 128 on), or DKV_HALVES_D256: the dK half (MODE 1), then the dV half (MODE 2); S is computed by both (80
+// instead of 64 MFMAs per 32-query step - DESIGN.md "Head dim 256").  Causal calls keep the single-role kernel at head dim 128 (0.30 ms at B8 H16 L1280); dK and dV
+// as two launches at two waves per SIMD measured the same (0.13 + 0.17 ms) and were not kept.
+template <int D, bool SID, bool TR, bool CAUSAL, typename... DR>
+void launch_dkv(const AttnArgs& a, hipStream_t s, const DR&... dr) {
+  const int blocks = ((a.L + 127) / 128) * a.H * a.B;
+  constexpr size_t lds = 4 * BQT * D * 2 + 4 * BQT * sizeof(float) + 2 * BQT * sizeof(long);
   constexpr int W = (D >= 128) ? 1 : 2;
-  constexpr int MODE_K = (D == 256) ? 1 : 3;   // D = 256: `kk` is the dK half, the dV half follows it
-  auto kk = attn_bwd_dkv_kernel<D, SID, TR, MODE_K, W, CAUSAL>;
-  static bool once = false;
-  if (!once) { set_lds(kq, lds_q); set_lds(kk, lds_k); once = true; }
   if constexpr (D == 256) {
-    auto kdv = attn_bwd_dkv_kernel<D, SID, TR, 2, W, CAUSAL>;
-    static bool once_dv = false;
-    if (!once_dv) { set_lds(kdv, lds_k); once_dv = true; }
-    hipLaunchKernelGGL(kq, gq, dim3(256), lds_q, s, a);
-    hipLaunchKernelGGL(kk, gk, dim3(256), lds_k, s, a);
-    hipLaunchKernelGGL(kdv, gk, dim3(256), lds_k, s, a);
-    return;
-  }
-  // D = 128, no mask, L % 256 == 0, q pre-scaled: both passes as generated one-wave-per-SIMD programs (round 6: attention_dq64.hip, attention_dkv64.hip)
-  // (causal calls take neither generated program nor the wave-specialised dK/dV kernel: none of them has a causal form)
-  if (!(D == 128 && !SID && TR && a.q_prescaled && !a.causal && udm_launch_attn_bwd_dq64(&a, s))) hipLaunchKernelGGL(kq, gq, dim3(256), lds_q, s, a);
-  if (D == 128 && !SID && TR && a.q_prescaled && !a.causal && udm_launch_attn_bwd_dkv64(&a, s)) return;   // the one-wave-per-SIMD, 64-keys-per-wave kernel (round 6)
-  if (D == 128 && !SID && TR && g_dkv_ws && !a.causal) udm_launch_attn_bwd_dkv_ws(&a, s);
-  else if (D == 128 && SID && TR && g_dkv_ws && a.doc_ranges) {
-    // packed documents: key blocks that lie inside one document and whose query span is exactly that document go to the wave-specialised
-    // kernel (no id test needed anywhere); the blocks at document boundaries / with padding stay with the single-role kernel
-    AttnArgs a2 = a;
-    a2.doc_pure_split = 1;
-    udm_launch_attn_bwd_dkv_ws(&a2, s);
-    hipLaunchKernelGGL(kk, gk, dim3(256), lds_k, s, a2);
-  } else hipLaunchKernelGGL(kk, gk, dim3(256), lds_k, s, a);
+    launch<attn_bwd_dkv_kernel<D, SID, TR, 1, W, CAUSAL, DR...>>(blocks, lds, a, s, dr...);
+    launch<attn_bwd_dkv_kernel<D, SID, TR, 2, W, CAUSAL, DR...>>(blocks, lds, a, s, dr...);
+  } else launch<attn_bwd_dkv_kernel<D, SID, TR, 3, W, CAUSAL, DR...>>(blocks, lds, a, s, dr...);
 }
 
-// p > 0: the 8-wave kernels with the mask, never the generated programs or the wave-specialised dK/dV kernel (none of them has a dropout form)
-template <int D, bool CAUSAL>
-void launch_fwd_drop(const AttnArgs& a, const AttnDrop& dr, hipStream_t s) {
-  dim3 grid(((a.L + BQ - 1) / BQ) * a.H * a.B);
-  const size_t lds = 4 * BKV * D * 2 + 2 * BKV * sizeof(long);
-  auto kern = attn_fwd_kernel<D, false, true, 0, CAUSAL, AttnDrop>;
-  static bool once = false;
-  if (!once) { set_lds(kern, lds); once = true; }
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, dr);
-}
-template <int D, bool CAUSAL>
-void launch_bwd_drop(const AttnArgs& a, const AttnDrop& dr, hipStream_t s) {
-  dim3 gq(((a.L + BQ - 1) / BQ) * a.H * a.B), gk(((a.L + 127) / 128) * a.H * a.B);
-  const size_t lds_q = 4 * BKV * D * 2 + 2 * BKV * sizeof(long);
-  const size_t lds_k = 4 * BQT * D * 2 + 4 * BQT * sizeof(float) + 2 * BQT * sizeof(long);
-  auto kq = attn_bwd_dq_kernel<D, false, true, CAUSAL, AttnDrop>;
-  auto kk = attn_bwd_dkv_kernel<D, false, true, (D == 256) ? 1 : 3, (D >= 128) ? 1 : 2, CAUSAL, AttnDrop>;   // D = 256: the dK half (see launch_bwd)
-  static bool once = false;
-  if (!once) { set_lds(kq, lds_q); set_lds(kk, lds_k); once = true; }
-  hipLaunchKernelGGL(kq, gq, dim3(256), lds_q, s, a, dr);
-  hipLaunchKernelGGL(kk, gk, dim3(256), lds_k, s, a, dr);
-  if constexpr (D == 256) {
-    auto kdv = attn_bwd_dkv_kernel<D, false, true, 2, 1, CAUSAL, AttnDrop>;
-    static bool once_dv = false;
-    if (!once_dv) { set_lds(kdv, lds_k); once_dv = true; }
-    hipLaunchKernelGGL(kdv, gk, dim3(256), lds_k, s, a, dr);
+// One pass of a plan.  The generated launchers get the timeline pointer of their diagnostic build in their copy of the arguments.
+template <int D, bool SID, bool TR, bool CAUSAL, typename... DR>
+void run_fwd(const AttnPlan& plan, const AttnArgs& a, hipStream_t s, const DR&... dr) {
+  switch (plan.fwd) {
+    case FWD_GEN64: { AttnArgs t = a; t.timeline = g_timeline.fwd64; udm_launch_attn_fwd64(t, plan.fwd_grid, s); break; }
+    case FWD_8WAVE: launch<attn_fwd_kernel<D, SID, TR, CAUSAL, DR...>>(((a.L + BQ - 1) / BQ) * a.H * a.B, 4 * BKV * D * 2 + 2 * BKV * sizeof(long), a, s, dr...); break;
   }
 }
-#define ATTN_DISPATCH_DROP(FN, a, dr, D, s)                                                        \
-  do {                                                                                            \
-    if (D == 256) { if (a.causal) FN<256, true>(a, dr, s); else FN<256, false>(a, dr, s); }       \
-    else if (D == 128) { if (a.causal) FN<128, true>(a, dr, s); else FN<128, false>(a, dr, s); }  \
-    else if (D == 64) { if (a.causal) FN<64, true>(a, dr, s); else FN<64, false>(a, dr, s); }     \
-    else { if (a.causal) FN<32, true>(a, dr, s); else FN<32, false>(a, dr, s); }                  \
-  } while (0)
+// (delta - and for pre-scaled q the planes - are computed and stored by the dQ program: it runs first)
+template <int D, bool SID, bool TR, bool CAUSAL, typename... DR>
+void run_bwd(const AttnPlan& plan, const AttnArgs& a, hipStream_t s, const DR&... dr) {
+  switch (plan.dq) {
+    case DQ_GEN64: { AttnArgs t = a; t.timeline = g_timeline.dq64; udm_launch_attn_bwd_dq64(t, plan.dq_grid, s); break; }
+    case DQ_8WAVE: launch<attn_bwd_dq_kernel<D, SID, TR, CAUSAL, DR...>>(((a.L + BQ - 1) / BQ) * a.H * a.B, 4 * BKV * D * 2 + 2 * BKV * sizeof(long), a, s, dr...); break;
+  }
+  switch (plan.dkv) {
+    case DKV_GEN64: { AttnArgs t = a; t.timeline = g_timeline.dkv64; udm_launch_attn_bwd_dkv64(t, plan.dkv_grid, s); break; }
+    case DKV_WS: case DKV_WS_PRE: udm_launch_attn_bwd_dkv_ws(a, plan.planes_needed, s); break;   // (the PRE form is the one that reads the planes)
+    case DKV_WS_SPLIT_SINGLE: {   // both kernels see doc_pure_split = 1: each returns at once from the key blocks of the other
+      AttnArgs a2 = a;
+      a2.doc_pure_split = 1;
+      udm_launch_attn_bwd_dkv_ws(a2, plan.planes_needed, s);
+      launch_dkv<D, SID, TR, CAUSAL>(a2, s, dr...);
+      break;
+    }
+    case DKV_SINGLE: case DKV_HALVES_D256: launch_dkv<D, SID, TR, CAUSAL>(a, s, dr...); break;
+  }
+}
 
-#define ATTN_DISPATCH(FN, a, D, sid, tr, s)                                    \
-  do {                                                                         \
-    if (D == 256) { if (sid) { if (tr) FN<256, true, true>(a, s); else FN<256, true, false>(a, s); } else { if (tr) FN<256, false, true>(a, s); else FN<256, false, false>(a, s); } } \
-    else if (D == 128) { if (sid) { if (tr) FN<128, true, true>(a, s); else FN<128, true, false>(a, s); } else { if (tr) FN<128, false, true>(a, s); else FN<128, false, false>(a, s); } } \
-    else if (D == 64) { if (sid) { if (tr) FN<64, true, true>(a, s); else FN<64, true, false>(a, s); } else { if (tr) FN<64, false, true>(a, s); else FN<64, false, false>(a, s); } } \
-    else { if (sid) { if (tr) FN<32, true, true>(a, s); else FN<32, true, false>(a, s); } else { if (tr) FN<32, false, true>(a, s); else FN<32, false, false>(a, s); } } \
-  } while (0)
-// causal: never with sample ids (rejected at the entry points)
-#define ATTN_DISPATCH_CAUSAL(FN, a, D, tr, s)                                                     \
-  do {                                                                                            \
-    if (D == 256) { if (tr) FN<256, false, true, true>(a, s); else FN<256, false, false, true>(a, s); } \
-    else if (D == 128) { if (tr) FN<128, false, true, true>(a, s); else FN<128, false, false, true>(a, s); } \
-    else if (D == 64) { if (tr) FN<64, false, true, true>(a, s); else FN<64, false, false, true>(a, s); } \
-    else { if (tr) FN<32, false, true, true>(a, s); else FN<32, false, false, true>(a, s); }          \
-  } while (0)
+// f(D, SID, TR, CAUSAL as integral constants, dr...) for the instantiation a call needs.  The ones that exist: every (D, SID, TR) without a mask flag; causal never
+// with sample ids; dropout (dr = the AttnDrop) never with sample ids or without the transposing reads - the entry points reject the rest.
+template <typename F>
+void attn_dispatch(int64_t D, bool sid, bool tr, bool causal, const AttnDrop* drop, F&& f) {
+  constexpr std::false_type N{};
+  constexpr std::true_type Y{};
+  const auto with_d = [&](auto d) {
+    if (drop) { if (causal) f(d, N, Y, Y, *drop); else f(d, N, Y, N, *drop); }
+    else if (causal) { if (tr) f(d, N, Y, Y); else f(d, N, N, Y); }
+    else if (sid) { if (tr) f(d, Y, Y, N); else f(d, Y, N, N); }
+    else { if (tr) f(d, N, Y, N); else f(d, N, N, N); }
+  };
+  if (D == 256) with_d(std::integral_constant<int, 256>{});
+  else if (D == 128) with_d(std::integral_constant<int, 128>{});
+  else if (D == 64) with_d(std::integral_constant<int, 64>{});
+  else with_d(std::integral_constant<int, 32>{});
+}
 
-int g_use_tr = 1;
+AttnProblem problem_of(const AttnArgs& a, int64_t D, const AttnDrop* drop) {
+  return AttnProblem{(int)D, a.B, a.H, a.L, a.sample_ids != nullptr, a.doc_ranges != nullptr, a.causal != 0, a.q_prescaled != 0, drop && drop->thr > 0,
+                     a.q_stride, a.k_stride, a.v_stride, a.o_stride, a.do_stride, a.out_stride, a.out2_stride, a.out3_stride};
+}
 
-// p_drop -> (thr, keep_scale, seed); thr == 0 means "no dropout: today's dispatch"
+// p_drop -> (thr, keep_scale, seed); thr == 0 means "no dropout": the plan of the call without it
 int check_drop(const char* name, float p_drop, uint64_t seed, const void* sample_ids, const void* doc_ranges, AttnDrop& dr) {
   UDM_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "%s: p_drop %g outside [0, 1)", name, (double)p_drop);
   dr.seed = seed;
-  dr.thr = (uint32_t)(p_drop * 65536.0f + 0.5f);
+  dr.thr = attn_drop_thr(p_drop);
   dr.keep_scale = 1.f / (1.f - p_drop);
   if (dr.thr == 0) return 0;
   UDM_CHECK_ARG(!sample_ids && !doc_ranges, "%s: p_drop > 0 with sample_ids / doc_ranges", name);
-  UDM_CHECK_ARG(g_use_tr, "%s: p_drop > 0 needs the transposing LDS reads (attention_tr_read = 1)", name);
+  UDM_CHECK_ARG(switches().tr_read, "%s: p_drop > 0 needs the transposing LDS reads (attention_tr_read = 1)", name);
   return 0;
 }
 
@@ -869,8 +836,16 @@ int check_common(const char* name, int64_t B, int64_t H, int64_t L, int64_t D, i
 }
 }  // namespace
 
-extern "C" __attribute__((visibility("hidden"))) int udm_attention_set_tr_read(int enable) {
-  g_use_tr = enable ? 1 : 0;
+// udm_debug_set's way to the switches and timeline pointers (capi.hip); 1 = not an attention key
+extern "C" __attribute__((visibility("hidden"))) int udm_attention_debug_set(const char* key, int64_t value) {
+  const auto is = [&](const char* k) { return strcmp(key, k) == 0; };
+  for (const SwitchKey& k : SWITCH_KEYS)
+    if (k.key && is(k.key)) { switches().*k.field = value < 0 ? env_switches().*k.field : (int)value; return 0; }
+  if (is("attention_tr_read")) switches().tr_read = value ? 1 : 0;   // 0 = gather V^T fragments with scalar LDS reads
+  else if (is("attention_fwd64_timeline")) g_timeline.fwd64 = reinterpret_cast<unsigned long long*>(value);
+  else if (is("attention_dq64_timeline")) g_timeline.dq64 = reinterpret_cast<unsigned long long*>(value);
+  else if (is("attention_dkv64_timeline")) g_timeline.dkv64 = reinterpret_cast<unsigned long long*>(value);
+  else return 1;
   return 0;
 }
 
@@ -883,7 +858,7 @@ extern "C" int udm_attention_doc_ranges(const int64_t* sample_ids, int64_t B, in
 }
 
 namespace {
-// `drop`: null for udm_attention_fwd, the checked parameters for udm_attention_fwd_dropout (thr == 0: the same dispatch as without it)
+// `drop`: null for udm_attention_fwd, the checked parameters for udm_attention_fwd_dropout (thr == 0: the same plan as without it)
 int attention_fwd_impl(const char* name, const void* q, const void* k, const void* v, void* o, float* lse, const int64_t* sample_ids, const int32_t* doc_ranges, int64_t B, int64_t H,
                        int64_t L, int64_t D, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t flags, const AttnDrop* drop, hipStream_t stream) {
   UDM_CHECK_ARG(q && k && v && o && lse, "%s: null pointer", name);
@@ -893,7 +868,6 @@ int attention_fwd_impl(const char* name, const void* q, const void* k, const voi
   UDM_CHECK_ARG(o_stride % 4 == 0, "%s: o_stride must be a multiple of 4", name);
   UDM_CHECK_ARG(sample_ids || !doc_ranges, "%s: doc_ranges without sample_ids", name);
   AttnArgs a{};
-  a.exp = udm_exp_flags();
   a.doc_ranges = doc_ranges;
   a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.out = (bf16_t*)o; a.lse = lse; a.sample_ids = sample_ids;
   a.q_stride = q_stride; a.k_stride = k_stride; a.v_stride = v_stride; a.out_stride = o_stride;
@@ -902,9 +876,11 @@ int attention_fwd_impl(const char* name, const void* q, const void* k, const voi
   a.scale_log2 = a.scale * 1.4426950408889634f;
   if (flags & UDM_ATTN_Q_PRESCALED) { a.q_prescaled = 1; a.scale_log2 = 1.0f; }   // q already carries log2(e) / sqrt(D): the scores ARE the base-2 exponents
   a.causal = (flags & UDM_ATTN_CAUSAL) ? 1 : 0;
-  if (drop && drop->thr) ATTN_DISPATCH_DROP(launch_fwd_drop, a, *drop, D, stream);
-  else if (a.causal) ATTN_DISPATCH_CAUSAL(launch_fwd, a, D, g_use_tr, stream);
-  else ATTN_DISPATCH(launch_fwd, a, D, sample_ids != nullptr, g_use_tr, stream);
+  const AttnProblem prob = problem_of(a, D, drop);
+  const AttnPlan plan = attn_plan_fwd(prob, switches(), device_cus(), udm_gemm_cus_available());
+  attn_dispatch(D, prob.sample_ids, switches().tr_read, prob.causal, prob.dropout ? drop : nullptr, [&](auto d, auto sid, auto tr, auto causal, const auto&... dr) {
+    run_fwd<decltype(d)::value, decltype(sid)::value, decltype(tr)::value, decltype(causal)::value>(plan, a, stream, dr...);
+  });
   UDM_CHECK_LAUNCH(name);
   return 0;
 }
@@ -933,7 +909,6 @@ int attention_bwd_impl(const char* name, const void* q, const void* k, const voi
   UDM_CHECK_ARG(o_stride % 8 == 0 && do_stride % 8 == 0 && dq_stride % 4 == 0 && dk_stride % 4 == 0 && dv_stride % 4 == 0, "%s: bad strides", name);
   UDM_CHECK_ARG(sample_ids || !doc_ranges, "%s: doc_ranges without sample_ids", name);
   AttnArgs a{};
-  a.exp = udm_exp_flags();
   a.doc_ranges = doc_ranges;
   a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o; a.dout = (const bf16_t*)dout;
   a.out = (bf16_t*)dq; a.out2 = (bf16_t*)dk; a.out3 = (bf16_t*)dv; a.lse = const_cast<float*>(lse); a.delta = delta; a.sample_ids = sample_ids;
@@ -945,13 +920,12 @@ int attention_bwd_impl(const char* name, const void* q, const void* k, const voi
   // q~ = q log2(e) / sqrt(D): scores are base-2 exponents as they come; dq~ = ln2 dS K and dk = ln2 dS^T q~ (dS wrt the natural-log scores): the factor
   // the kernels put on dQ / dK is ln 2 instead of 1 / sqrt(D)
   if (flags & UDM_ATTN_Q_PRESCALED) { a.q_prescaled = 1; a.scale_log2 = 1.0f; a.scale = 0.6931471805599453f; }
-  static const bool env_once = [] { if (const char* e = getenv("UDM_DKV_WS")) g_dkv_ws = atoi(e); return true; }();
-  (void)env_once;
   a.causal = (flags & UDM_ATTN_CAUSAL) ? 1 : 0;
-  // (delta is computed and stored by the dQ kernel, which launch_bwd runs first)
-  if (drop && drop->thr) ATTN_DISPATCH_DROP(launch_bwd_drop, a, *drop, D, stream);
-  else if (a.causal) ATTN_DISPATCH_CAUSAL(launch_bwd, a, D, g_use_tr, stream);
-  else ATTN_DISPATCH(launch_bwd, a, D, sample_ids != nullptr, g_use_tr, stream);
+  const AttnProblem prob = problem_of(a, D, drop);
+  const AttnPlan plan = attn_plan_bwd(prob, switches(), device_cus(), udm_gemm_cus_available());
+  attn_dispatch(D, prob.sample_ids, switches().tr_read, prob.causal, prob.dropout ? drop : nullptr, [&](auto d, auto sid, auto tr, auto causal, const auto&... dr) {
+    run_bwd<decltype(d)::value, decltype(sid)::value, decltype(tr)::value, decltype(causal)::value>(plan, a, stream, dr...);
+  });
   UDM_CHECK_LAUNCH(name);
   return 0;
 }

@@ -1,8 +1,33 @@
 // Shared device helpers of the attention kernels (attention.hip, attention_dkv_ws.hip): XOR-swizzled LDS tile layout, MFMA
-// fragment gathers, LDS-DMA staging, the kernel argument block.  Everything has internal linkage (included per translation unit).
+// fragment gathers, LDS-DMA staging, the kernel argument block.  The device helpers have internal linkage (included per translation unit).
 #pragma once
 #include "common.h"
 #include "../../include/unidisc_hip.h"
+#include "attention_plan.h"
+
+// the argument block of the attention kernels (named at file scope: the launchers of the other translation units take it by reference)
+struct AttnArgs {
+  const bf16_t* q; const bf16_t* k; const bf16_t* v; const bf16_t* o; const bf16_t* dout;
+  bf16_t* out;          // fwd: O;            bwd-dq: dQ
+  bf16_t* out2;         // bwd-dkv: dK
+  bf16_t* out3;         // bwd-dkv: dV
+  float* lse;           // [B,H,L] log2-domain log-sum-exp of scaled scores
+  const float* delta;   // [B,H,L] rowsum(dO * O)
+  const int64_t* sample_ids;  // [B,L] or null
+  const int* doc_ranges;      // [B, ceil(L/64), 8] or null: per 64-row tile {lo, hi, idmin, idmax, exact, -, -, -} (udm_attention_doc_ranges)
+  int doc_pure_split;         // dK/dV with documents: 1 = document-pure key blocks are computed by the wave-specialised kernel, the rest by the other
+  long q_stride, k_stride, v_stride, o_stride, do_stride, out_stride, out2_stride, out3_stride;
+  int B, H, L;
+  float scale_log2;     // log2(e) / sqrt(D)
+  float scale;          // 1 / sqrt(D)
+  int causal;           // UDM_ATTN_CAUSAL: query i sees keys j <= i (8-wave kernels only).  Sits in the alignment hole in front of `timeline`: no field
+                        // moves and the block keeps its size, so every kernarg layout - attn_fwd64_kernel's scalars behind it included - is unchanged
+  unsigned long long* timeline;   // diagnostics (experiments library): cycle stamps of a few blocks, or null
+  int exp;                        // experiment bits (udm_exp_flags), 0 in production
+  int q_prescaled;                // UDM_ATTN_Q_PRESCALED: q carries log2(e) / sqrt(D) (scale_log2 = 1; the backward's `scale` = ln 2)
+};
+
+static_assert(sizeof(AttnArgs) == 208 && offsetof(AttnArgs, causal) == 188 && offsetof(AttnArgs, timeline) == 192, "AttnArgs layout (kernarg segments)");
 
 namespace {
 using namespace udm;
@@ -79,29 +104,6 @@ __device__ __forceinline__ bf16x8_t load_frag_global(const bf16_t* p, bool ok) {
   uint4 u = ok ? *reinterpret_cast<const uint4*>(p) : make_uint4(0, 0, 0, 0);
   return __builtin_bit_cast(bf16x8_t, u);
 }
-
-struct AttnArgs {
-  const bf16_t* q; const bf16_t* k; const bf16_t* v; const bf16_t* o; const bf16_t* dout;
-  bf16_t* out;          // fwd: O;            bwd-dq: dQ
-  bf16_t* out2;         // bwd-dkv: dK
-  bf16_t* out3;         // bwd-dkv: dV
-  float* lse;           // [B,H,L] log2-domain log-sum-exp of scaled scores
-  const float* delta;   // [B,H,L] rowsum(dO * O)
-  const int64_t* sample_ids;  // [B,L] or null
-  const int* doc_ranges;      // [B, ceil(L/64), 8] or null: per 64-row tile {lo, hi, idmin, idmax, exact, -, -, -} (udm_attention_doc_ranges)
-  int doc_pure_split;         // dK/dV with documents: 1 = document-pure key blocks are computed by the wave-specialised kernel, the rest by the other
-  long q_stride, k_stride, v_stride, o_stride, do_stride, out_stride, out2_stride, out3_stride;
-  int B, H, L;
-  float scale_log2;     // log2(e) / sqrt(D)
-  float scale;          // 1 / sqrt(D)
-  int causal;           // UDM_ATTN_CAUSAL: query i sees keys j <= i (8-wave kernels only).  Sits in the alignment hole in front of `timeline`: no field
-                        // moves and the block keeps its size, so every kernarg layout - attn_fwd64_kernel's scalars behind it included - is unchanged
-  unsigned long long* timeline;   // diagnostics (experiments library): cycle stamps of a few blocks, or null
-  int exp;                        // experiment bits (udm_exp_flags), 0 in production
-  int q_prescaled;                // UDM_ATTN_Q_PRESCALED: q carries log2(e) / sqrt(D) (scale_log2 = 1; the backward's `scale` = ln 2)
-};
-
-static_assert(sizeof(AttnArgs) == 208 && offsetof(AttnArgs, causal) == 188 && offsetof(AttnArgs, timeline) == 192, "AttnArgs layout (kernarg segments)");
 
 // Attention mask codes.  `sample_ids` holds one int64 per position:  bits 0-31 = sample id (signed; < 0 = padding), bits 32-39 = the KEY classes this
 // position belongs to, bits 40-47 = the key classes this position may see as a QUERY.  A query sees a key iff both sample ids are equal and >= 0 and
@@ -270,8 +272,8 @@ __device__ __forceinline__ void store_rows_via_lds_d128(char* wave_lds, const f3
 }
 }  // namespace
 
-// dK/dV kernel for head dim 128 without a document mask (attention_dkv_ws.hip); grid = ceil(L / 128) * B * H blocks of 512 threads
-void udm_launch_attn_bwd_dkv_ws(const void* args, hipStream_t stream);
-bool udm_launch_attn_bwd_dq64(const void* args, hipStream_t stream);    // attention_dq64.hip: dQ (+ delta and the planes) at D = 128, no mask, L % 256 == 0, q pre-scaled (false = shape not taken)
-bool udm_launch_attn_bwd_dkv64(const void* args, hipStream_t stream);   // attention_dkv64.hip: dK / dV at D = 128, no mask, L % 256 == 0, q pre-scaled (false = shape not taken)
-bool udm_launch_attn_fwd64(const void* args, hipStream_t stream);      // attention_fwd64.hip: forward at D = 128, no mask, L % 256 == 0 (false = shape not taken)
+// The launchers of the other translation units.  attention.hip has chosen the program (attention_plan.h): these fill the parameter block and launch, nothing else.
+void udm_launch_attn_bwd_dkv_ws(const AttnArgs& a, bool pre, hipStream_t stream);            // attention_dkv_ws.hip: grid = ceil(L / 128) * B * H blocks of 512 threads
+void udm_launch_attn_fwd64(const AttnArgs& a, const AttnGrid& g, hipStream_t stream);       // attention_fwd64.hip (a.timeline: diagnostic builds)
+void udm_launch_attn_bwd_dq64(const AttnArgs& a, const AttnGrid& g, hipStream_t stream);    // attention_dq64.hip: dQ, delta and the planes
+void udm_launch_attn_bwd_dkv64(const AttnArgs& a, const AttnGrid& g, hipStream_t stream);   // attention_dkv64.hip: dK / dV from the planes

@@ -4,7 +4,6 @@
 // fills the program's parameter block and launches.  Replaces the dK / dV half of the backward of flash_attn_qkvpacked_func (reference models/dit.py:843) on
 // the headline path; attention_dkv_ws.hip keeps every other shape.
 #include "attention_common.h"
-#include "gemm_quad.h"
 #include "attention_dkv64_gen.h"
 
 #include <stdlib.h>
@@ -47,24 +46,10 @@ __global__ __launch_bounds__(256) void attn_dkv64_kernel(Dkv64Params p) {
 #undef UDM_DKV64_RUN
   (void)p;
 }
-int g_dkv64 = -1;
-unsigned long long* g_dkv64_timeline = nullptr;
 }  // namespace
 
-void udm_attention_set_dkv64(int enable) { g_dkv64 = enable; }                                     // tests / A-B measurements (through udm_debug_set)
-void udm_attention_set_dkv64_timeline(int64_t device_ptr) { g_dkv64_timeline = reinterpret_cast<unsigned long long*>(device_ptr); }
-
-// the dK / dV pass of attention.hip's backward dispatch for (D = 128, no sample ids): returns false when this kernel does not take the shape
-bool udm_launch_attn_bwd_dkv64(const void* args, hipStream_t stream) {
-  const AttnArgs& a = *reinterpret_cast<const AttnArgs*>(args);
-  if (g_dkv64 < 0) { const char* e = getenv("UDM_ATTN_DKV64"); g_dkv64 = e ? atoi(e) : 1; }
-  // whole 256-key blocks of at least two per (batch, head) (the magic divisions), the XCD-sequential block order (B H a multiple of 8), 16-byte row segments
-  if (!g_dkv64 || !a.q_prescaled || a.causal || a.H < 2 || a.L % 256 != 0 || a.L < 512 || (a.B * a.H) % 8 != 0) return false;
-  if (a.out2_stride % 8 != 0 || a.out3_stride % 8 != 0 || a.q_stride % 8 != 0 || a.do_stride % 8 != 0) return false;
-  const long lim = 1L << 31;     // 32-bit lane offsets: 64 rows of any operand, and the plane offset
-  if (a.q_stride * 2 * 64 >= lim || a.do_stride * 2 * 64 >= lim || a.k_stride * 2 * 256 >= lim || a.v_stride * 2 * 256 >= lim || a.out2_stride * 2 * 256 >= lim || a.out3_stride * 2 * 256 >= lim) return false;
-  const long nt = a.L / 256, nblk = nt * a.B * a.H, plane = (long)a.B * a.H * a.L;
-  if ((long)a.B * a.L >= (1L << 30) || nblk >= (1L << 24) || nt > 4096 || a.H > 4096 || plane >= (1L << 29)) return false;   // 32-bit row / plane indices, exact magic divisions
+// DKV_GEN64 of attention.hip's plan (attention_plan.h holds the gates and the grid arithmetic); a.timeline: stamps of this launch (a build with UDM_DKV64_ABL=16)
+void udm_launch_attn_bwd_dkv64(const AttnArgs& a, const AttnGrid& g, hipStream_t stream) {
   static const int abl = [] { const char* e = getenv("UDM_ATTN_DKV64_ABL"); return e ? atoi(e) : 0; }();
   auto kern = attn_dkv64_kernel<0>;
   switch (abl) {
@@ -74,7 +59,7 @@ bool udm_launch_attn_bwd_dkv64(const void* args, hipStream_t stream) {
     case 8: kern = attn_dkv64_kernel<8>; break;
     default: break;
   }
-  if (g_dkv64_timeline) {
+  if (a.timeline) {
 #ifdef UDM_DKV64_ASM_ABL16
     kern = attn_dkv64_kernel<16>;
 #else
@@ -83,24 +68,13 @@ bool udm_launch_attn_bwd_dkv64(const void* args, hipStream_t stream) {
   }
   static const void* attr_set = nullptr;
   if (attr_set != (const void*)kern) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, UDM_DKV64_LDS_BYTES); attr_set = (const void*)kern; }
-  static const int dev_cus = [] { int dev = 0, n = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n / 8 * 8; }();
-  // a persistent workgroup needs a whole CU: while a collective's channel kernels hold CUs (udm_gemm_set_cus, the data-parallel schedule `overlap_planned`) the grid is
-  // what is left - a workgroup that finds no CU would start its whole walk only when another has finished its own
-  const int plan_cus = udm_gemm_cus_available() / 8 * 8;
-  const int cus = plan_cus >= 8 && plan_cus < dev_cus ? plan_cus : dev_cus;
-  const auto magic = [](long d) { return (uint32_t)((1ULL << 32) / (unsigned long long)d + 1); };   // n / d == mulhi(n, magic) for n d < 2^32, d >= 2
-  const long grid = nblk < cus ? nblk : cus;    // persistent: one workgroup per CU walks blocks id, id + grid, ...
-  // balanced walk (as the forward): when the blocks behind the whole rounds are exactly half a grid (the headline's 640 blocks on 256 CUs) every workgroup ends with
-  // ONE 128-key half block instead of a third whole block for half of them
-  const long rem = nblk % grid;
-  const bool halves = g_dkv64 != 2 && rem * 2 == grid && nblk - rem >= grid && grid % 16 == 0;
+  const long nt = a.L / 256, plane = (long)a.B * a.H * a.L;
   Dkv64Params p{};
   p.q = a.q; p.dout = a.dout; p.nlse = a.delta + plane;        // delta | -lse | -delta: the planes the dQ kernel (launched first) leaves behind
   p.qstr = (uint32_t)(a.q_stride * 2); p.dostr = (uint32_t)(a.do_stride * 2); p.L = (uint32_t)a.L; p.nsteps = (uint32_t)(a.L / 32); p.H = (uint32_t)a.H; p.nt = (uint32_t)nt;
-  p.mg_nt = magic(nt); p.mg_H = magic(a.H); p.nfull = (uint32_t)(halves ? nblk - rem : nblk); p.hashalf = halves ? 1u : 0u; p.gstride = (uint32_t)grid; p.planeB = (uint32_t)(plane * 4);
+  p.mg_nt = g.mg_nt; p.mg_H = g.mg_H; p.nfull = g.nfull; p.hashalf = g.hashalf; p.gstride = g.grid; p.planeB = (uint32_t)(plane * 4);
   p.k = a.k; p.v = a.v; p.kstr = (uint32_t)(a.k_stride * 2); p.vstr = (uint32_t)(a.v_stride * 2);
   p.dk = a.out2; p.dv = a.out3; p.dkstr = (uint32_t)(a.out2_stride * 2); p.dvstr = (uint32_t)(a.out3_stride * 2); p.scale = a.scale;
-  p.timeline = g_dkv64_timeline;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), UDM_DKV64_LDS_BYTES, stream, p);
-  return true;
+  p.timeline = a.timeline;
+  hipLaunchKernelGGL(kern, dim3(g.grid), dim3(256), UDM_DKV64_LDS_BYTES, stream, p);
 }

@@ -243,7 +243,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_ws_kernel(AttnArgs a) {
   const bool k_ok = ki < a.L;
   const long rowbase = (long)b * a.L;
   const long sbase = ((long)b * a.H + h) * a.L;
-  // Packed documents (a.doc_ranges, launched by attention.hip::launch_bwd beside the single-role kernel): this kernel takes the key blocks that lie
+  // Packed documents (a.doc_ranges, DKV_WS_SPLIT_SINGLE: launched by attention.hip::run_bwd beside the single-role kernel): this kernel takes the key blocks that lie
   // inside ONE document whose rows are exactly the positions [lo, hi) - then no (query, key) pair of the walk needs an id test, and the walk is this
   // kernel's ordinary one over the `hi - lo` queries starting at `lo`.  Every other key block returns here and is computed by the other kernel.
   int q_lo = 0, q_n = a.L;
@@ -361,9 +361,9 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_ws_kernel(AttnArgs a) {
 }
 }  // namespace
 
-void udm_launch_attn_bwd_dkv_ws(const void* args, hipStream_t stream) {
+// DKV_WS / DKV_WS_PRE and the wave-specialised half of DKV_WS_SPLIT_SINGLE of attention.hip's plan (attention_plan.h); pre: the PRE form
+void udm_launch_attn_bwd_dkv_ws(const AttnArgs& a, bool pre, hipStream_t stream) {
   using namespace dkvw;
-  const AttnArgs& a = *static_cast<const AttnArgs*>(args);
   const dim3 grid(((a.L + 127) / 128) * a.H * a.B);
   static bool once = false;
   static int timeline = 0;
@@ -399,8 +399,7 @@ void udm_launch_attn_bwd_dkv_ws(const void* args, hipStream_t stream) {
       return;
     }
   }
-  static const int pre_on = [] { const char* e = getenv("UDM_DKV_PRE"); return e ? atoi(e) : 1; }();   // A/B switch: 0 = the plain arithmetic also for pre-scaled q
-  if (a.q_prescaled && pre_on) {   // the engine's form: score chains start from -lse / -delta (see score_step)
+  if (pre) {   // the engine's form: score chains start from -lse / -delta (see score_step)
     static bool once_p = false;
     if (!once_p) { (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_ws_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); once_p = true; }
     hipLaunchKernelGGL((attn_bwd_dkv_ws_kernel<false, true>), grid, dim3(512), LDS_BYTES, stream, a);

@@ -1,0 +1,121 @@
+// Which device programs one udm_attention_fwd / udm_attention_bwd call runs, as a pure host function of the problem and the debug switches.  Plain C++17 without
+// HIP: attention.hip executes the plan, tests/test_attention_plan.py compiles this header alone and prints the plan of every shape the GPU tests use.
+//   forward   FWD_8WAVE (attn_fwd_kernel)      | FWD_GEN64 (attention_fwd64.hip)
+//   dQ        DQ_8WAVE (attn_bwd_dq_kernel)    | DQ_GEN64 (attention_dq64.hip)
+//   dK / dV   DKV_SINGLE (attn_bwd_dkv_kernel) | DKV_HALVES_D256 (its dK half, then its dV half) | DKV_WS / DKV_WS_PRE (attention_dkv_ws.hip, PRE: the score
+//             chains start from the planes) | DKV_WS_SPLIT_SINGLE (packed documents: both, see below) | DKV_GEN64 (attention_dkv64.hip)
+// The planes: delta | -lse | -delta, B H L floats each, in the caller's `delta` scratch.  DKV_GEN64 and the PRE kernel read them, so the dQ program that runs first
+// must have written them: DQ_GEN64 always does, DQ_8WAVE does for pre-scaled q (attn_plan_bwd asserts that of the dQ program it chose).
+#pragma once
+#include <assert.h>
+#include <stdint.h>
+
+struct AttnProblem {
+  int D, B, H, L;
+  bool sample_ids, doc_ranges, causal, q_prescaled;
+  bool dropout;   // attn_drop_thr(p_drop) > 0 (thr == 0 is the call without dropout: the same plan, the same kernels)
+  long q_stride, k_stride, v_stride, o_stride, do_stride, out_stride, out2_stride, out3_stride;   // elements; out = O (forward) / dQ, out2 = dK, out3 = dV
+};
+// one field per debug key / environment variable (attention.hip owns the one instance); the defaults are those of an empty environment
+struct AttnSwitches {
+  int fwd64 = 1, dq64 = 1, dkv64 = 1;   // the generated programs: 0 off, 1 on, 2 on without the balanced walk
+  int dkv_ws = 1;                       // 0: the single-role dK/dV kernel at head dim 128 too
+  int dkv_pre = 1;                      // 0: the plain arithmetic of the wave-specialised kernel also for pre-scaled q
+  int tr_read = 1;                      // 0: the kernels that gather transposed fragments with scalar LDS reads (USE_TR = false)
+};
+enum AttnFwdProgram { FWD_8WAVE, FWD_GEN64 };
+enum AttnDqProgram { DQ_8WAVE, DQ_GEN64 };
+enum AttnDkvProgram { DKV_SINGLE, DKV_HALVES_D256, DKV_WS, DKV_WS_PRE, DKV_WS_SPLIT_SINGLE, DKV_GEN64 };
+
+// launch numbers of a generated (persistent) program: one workgroup per CU walks the 256-row blocks id, id + grid, ...
+struct AttnGrid {
+  uint32_t grid, nfull, hashalf;   // hashalf: blocks [0, nfull) are walked whole, the rest as 128-row halves (the balanced walk)
+  uint32_t mg_nt, mg_H;            // magic divisors of L / 256 and H
+};
+struct AttnPlan {
+  AttnFwdProgram fwd = FWD_8WAVE;
+  AttnDqProgram dq = DQ_8WAVE;
+  AttnDkvProgram dkv = DKV_SINGLE;
+  bool planes_needed = false;   // the dK/dV program reads the planes: DKV_GEN64, DKV_WS_PRE, and DKV_WS_SPLIT_SINGLE when its wave-specialised half is the PRE form
+  AttnGrid fwd_grid{}, dq_grid{}, dkv_grid{};   // of the FWD_GEN64 / DQ_GEN64 / DKV_GEN64 choices
+};
+
+// keep iff a 16-bit field >= thr (include/unidisc_hip.h); a p_drop that rounds to no step of the 65536 is no dropout
+inline uint32_t attn_drop_thr(float p_drop) { return (uint32_t)(p_drop * 65536.0f + 0.5f); }
+
+inline uint32_t attn_magic(long d) { return (uint32_t)((1ULL << 32) / (unsigned long long)d + 1); }   // n / d == mulhi(n, magic) for n d < 2^32, d >= 2 (magic(1) wraps)
+
+// dev_cus: the device's CU count; plan_cus: udm_gemm_cus_available().  A persistent workgroup needs a whole CU: while a collective's channel kernels hold CUs
+// (udm_gemm_set_cus, the data-parallel schedule `overlap_planned`) the grid is what is left - a workgroup that finds no CU would start its whole walk only when
+// another has finished its own.
+inline AttnGrid attn_persistent_grid(const AttnProblem& p, int sw, int dev_cus, int plan_cus) {
+  dev_cus = dev_cus / 8 * 8;
+  plan_cus = plan_cus / 8 * 8;
+  const int cus = plan_cus >= 8 && plan_cus < dev_cus ? plan_cus : dev_cus;
+  const long nt = p.L / 256, nblk = nt * p.B * p.H;
+  const long grid = nblk < cus ? nblk : cus;
+  // balanced walk: when the blocks left behind the whole rounds are exactly half a grid (the headline's 640 blocks on 256 CUs), every workgroup ends with ONE
+  // 128-row half block (2.5 units each) instead of a third whole block for half of them (3 vs 2)
+  const long rem = nblk % grid;
+  const bool halves = sw != 2 && rem * 2 == grid && nblk - rem >= grid && grid % 16 == 0;
+  return AttnGrid{(uint32_t)grid, (uint32_t)(halves ? nblk - rem : nblk), halves ? 1u : 0u, attn_magic(nt), attn_magic(p.H)};
+}
+
+// what the three generated programs ask alike: head dim 128 with the transposing reads, no mask of any kind, q pre-scaled, whole 256-row blocks with at least two
+// trips of the tile loop, H >= 2 (magic(1) wraps: the head divisor would read 0), the XCD-sequential block order (B H a multiple of 8), 32-bit row / lse / plane
+// indices and exact magic divisions
+inline bool attn_gen64_shape(const AttnProblem& p, const AttnSwitches& sw) {
+  if (p.D != 128 || p.sample_ids || !sw.tr_read || !p.q_prescaled || p.causal || p.dropout) return false;
+  if (p.H < 2 || p.L % 256 != 0 || p.L < 512 || (p.B * p.H) % 8 != 0) return false;
+  const long nt = p.L / 256, nblk = nt * p.B * p.H;
+  return !((long)p.B * p.L >= (1L << 30) || nblk >= (1L << 24) || nt > 4096 || p.H > 4096 || (long)p.B * p.H * p.L >= (1L << 29));
+}
+// What each program asks of the strides on top of that: 16-byte row segments of what it stores or loads as whole rows, and 32-bit lane offsets over the rows one
+// instruction spans.  The lists differ on purpose, each is its program's: the forward walks K / V 80 rows ahead and never checks q / k / v alignment (the entry
+// point's % 8 check covers them); dQ spans 256 rows of q / dO / O / dQ and 64 of K / V; dK/dV the other way round.
+inline bool attn_fwd64_takes(const AttnProblem& p, const AttnSwitches& sw) {
+  const long lim = 1L << 31;
+  if (!sw.fwd64 || !attn_gen64_shape(p, sw) || p.out_stride % 8 != 0) return false;
+  return !(p.q_stride * 2 * 256 >= lim || p.k_stride * 2 * 80 >= lim || p.v_stride * 2 * 80 >= lim || p.out_stride * 2 * 256 >= lim);
+}
+inline bool attn_dq64_takes(const AttnProblem& p, const AttnSwitches& sw) {
+  const long lim = 1L << 31;
+  if (!sw.dq64 || !attn_gen64_shape(p, sw)) return false;
+  if (p.out_stride % 8 != 0 || p.o_stride % 8 != 0 || p.q_stride % 8 != 0 || p.do_stride % 8 != 0) return false;
+  return !(p.q_stride * 2 * 256 >= lim || p.do_stride * 2 * 256 >= lim || p.o_stride * 2 * 256 >= lim || p.k_stride * 2 * 64 >= lim || p.v_stride * 2 * 64 >= lim ||
+           p.out_stride * 2 * 256 >= lim);
+}
+inline bool attn_dkv64_takes(const AttnProblem& p, const AttnSwitches& sw) {
+  const long lim = 1L << 31;
+  if (!sw.dkv64 || !attn_gen64_shape(p, sw)) return false;
+  if (p.out2_stride % 8 != 0 || p.out3_stride % 8 != 0 || p.q_stride % 8 != 0 || p.do_stride % 8 != 0) return false;
+  return !(p.q_stride * 2 * 64 >= lim || p.do_stride * 2 * 64 >= lim || p.k_stride * 2 * 256 >= lim || p.v_stride * 2 * 256 >= lim || p.out2_stride * 2 * 256 >= lim ||
+           p.out3_stride * 2 * 256 >= lim);
+}
+
+inline AttnPlan attn_plan_fwd(const AttnProblem& p, const AttnSwitches& sw, int dev_cus, int plan_cus) {
+  AttnPlan plan;
+  if (attn_fwd64_takes(p, sw)) { plan.fwd = FWD_GEN64; plan.fwd_grid = attn_persistent_grid(p, sw.fwd64, dev_cus, plan_cus); }
+  return plan;
+}
+
+inline AttnPlan attn_plan_bwd(const AttnProblem& p, const AttnSwitches& sw, int dev_cus, int plan_cus) {
+  AttnPlan plan;
+  if (attn_dq64_takes(p, sw)) { plan.dq = DQ_GEN64; plan.dq_grid = attn_persistent_grid(p, sw.dq64, dev_cus, plan_cus); }
+  // Head dim 128: both accumulators (128 registers) plus K/V operands (64) only fit one wave per SIMD in the single-role kernel, which is then bound by that one
+  // wave's instruction issue (0.39 ms at B8 H16 L1280); without a mask the wave-specialised kernel (0.27 ms) or the generated program runs instead.  Neither has a
+  // causal, dropout or USE_TR = false form.  Head dim 256: dK^T and dV^T together are more registers than a wave has - the dK half, then the dV half.
+  const bool d128 = p.D == 128 && sw.tr_read && !p.causal && !p.dropout;
+  const bool pre = p.q_prescaled && sw.dkv_pre;   // the wave-specialised kernel's score chains start from -lse / -delta
+  if (p.D == 256) plan.dkv = DKV_HALVES_D256;
+  else if (attn_dkv64_takes(p, sw)) { plan.dkv = DKV_GEN64; plan.dkv_grid = attn_persistent_grid(p, sw.dkv64, dev_cus, plan_cus); }
+  else if (d128 && !p.sample_ids && sw.dkv_ws) plan.dkv = pre ? DKV_WS_PRE : DKV_WS;
+  // packed documents: key blocks that lie inside one document and whose query span is exactly that document go to the wave-specialised kernel (no id test
+  // needed anywhere); the blocks at document boundaries / with padding stay with the single-role kernel
+  else if (d128 && p.sample_ids && p.doc_ranges && sw.dkv_ws) plan.dkv = DKV_WS_SPLIT_SINGLE;
+  plan.planes_needed = plan.dkv == DKV_GEN64 || plan.dkv == DKV_WS_PRE || (plan.dkv == DKV_WS_SPLIT_SINGLE && pre);
+  // what the chosen dQ program writes, not what the readers' gates happen to ask: a planes reader chosen for plain q while the 8-wave dQ kernel runs aborts here
+  // (and in tests/test_attention_plan.py, whose printer is built with assertions on and asks for every reader's shape with plain q)
+  assert(!plan.planes_needed || plan.dq == DQ_GEN64 || (plan.dq == DQ_8WAVE && p.q_prescaled));
+  return plan;
+}

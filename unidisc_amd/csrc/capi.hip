@@ -26,14 +26,7 @@ extern "C" int udm_abi_version(void) { return UDM_ABI_VERSION; }
 extern "C" __attribute__((visibility("hidden"))) int udm_gemm_set_tile(int tile);      // gemm.hip: force the tile family (-1 auto, 0 = 128x128 kernel, 192 / 256 / 320 = BM x 256 kernel)
 extern "C" __attribute__((visibility("hidden"))) int udm_gemm_set_quad(int mode);      // gemm.hip: one-wave-per-SIMD kernels 0 = off, 1 = auto (default; env UDM_GEMM_QUAD), 2 = wherever the shape fits
 extern "C" __attribute__((visibility("hidden"))) int udm_gemm_set_persist(int enable); // gemm.hip: 0 = one block per output tile (default 1: persistent blocks for multi-round NT shapes)
-extern "C" __attribute__((visibility("hidden"))) int udm_attention_set_tr_read(int enable);        // attention.hip: 0 = gather V^T fragments with scalar LDS reads
-extern "C" __attribute__((visibility("hidden"))) int udm_attention_set_fwd64_timeline(int64_t device_ptr);   // attention_fwd64.hip diagnostics
-extern "C" __attribute__((visibility("hidden"))) int udm_attention_set_fwd64(int enable);          // attention_fwd64.hip: 0 = the 8-wave forward also at D = 128, L % 256 == 0 (default 1; env UDM_ATTN_FWD64)
-
-void udm_attention_set_dkv64(int enable);                                     // attention_dkv64.hip: 0 = the wave-specialised dK / dV kernel everywhere, 2 = without the balanced walk
-void udm_attention_set_dkv64_timeline(int64_t device_ptr);
-void udm_attention_set_dq64(int enable);                                      // attention_dq64.hip: 0 = attn_bwd_dq_kernel everywhere, 2 = without the balanced walk
-void udm_attention_set_dq64_timeline(int64_t device_ptr);
+extern "C" __attribute__((visibility("hidden"))) int udm_attention_debug_set(const char* key, int64_t value);   // attention.hip: every "attention_*" key (1 = not one of them)
 
 namespace { int g_exp = [] { const char* e = getenv("UDM_EXP"); return e ? atoi(e) : 0; }(); }
 int udm_exp_flags() { return g_exp; }
@@ -47,13 +40,7 @@ extern "C" int udm_debug_set(const char* key, int64_t value) {
   if (is("gemm_persist")) return udm_gemm_set_persist((int)value);
   if (is("gemm_quad_timeline")) { g_quad_timeline = reinterpret_cast<unsigned*>(value); return 0; }
   if (is("gemm_quad_asm")) { g_quad_asm = (int)value; return 0; }   // 0 = the C++ K loop of gemm_quad.hip everywhere, 1 = the generated asm loop where it exists, -1 = env
-  if (is("attention_tr_read")) return udm_attention_set_tr_read((int)value);
-  if (is("attention_fwd64")) return udm_attention_set_fwd64((int)value);
-  if (is("attention_fwd64_timeline")) return udm_attention_set_fwd64_timeline(value);
-  if (is("attention_dkv64")) { udm_attention_set_dkv64((int)value); return 0; }
-  if (is("attention_dq64")) { udm_attention_set_dq64((int)value); return 0; }
-  if (is("attention_dq64_timeline")) { udm_attention_set_dq64_timeline(value); return 0; }
-  if (is("attention_dkv64_timeline")) { udm_attention_set_dkv64_timeline(value); return 0; }
+  if (udm_attention_debug_set(key, value) == 0) return 0;
   udm_set_error("udm_debug_set: unknown key '%s'", key);
   return 2;
 }
