@@ -1794,6 +1794,8 @@ inline int grid_rows(long M) {
   return (int)(g < 2048 ? (g < 1 ? 1 : g) : 2048);
 }
 inline int nch_for(long d) { return (int)((d + 511) / 512); }
+// template instance of the wave-per-row kernels: NCH chunks of 512 columns; 2048 < d <= 4096 runs the 8-chunk instance, a wider row has none (0: DISPATCH_NCH refuses)
+inline int nch_dispatch(long d) { const int n = nch_for(d); return n <= 4 ? n : (d <= 4096 ? 8 : 0); }
 
 #define DISPATCH_NCH_MOD(nch, KERNEL, grid, stream, args)                                            \
   switch (nch) {                                                                                     \
@@ -1823,7 +1825,7 @@ extern "C" int udm_norm_fwd(const float* x, void* y, float* rstd, float* mean, c
   UDM_CHECK_ARG((shift == nullptr) == (scale == nullptr), "udm_norm_fwd: shift and scale go together");
   NormArgs a{x, (bf16_t*)y, rstd, norm_type ? mean : nullptr, w, (const bf16_t*)shift, (const bf16_t*)scale, modality, any_img, (long)mod_stride,
              (int)M, (int)d, (int)L, norm_type, eps};
-  int nch = nch_for(d); if (nch > 4) nch = 8;
+  const int nch = nch_dispatch(d);
   DISPATCH_NCH(nch, norm_fwd_kernel, grid_rows(M), stream, a);
   UDM_CHECK_LAUNCH("udm_norm_fwd");
   return 0;
@@ -1837,7 +1839,7 @@ extern "C" int udm_norm_bwd(const void* dy, const float* x, const float* rstd, c
   UDM_CHECK_ARG(!shift || (scale && dshift && dscale), "udm_norm_bwd: modulated norm needs scale, dshift, dscale");
   NormBwdArgs a{(const bf16_t*)dy, x, rstd, mean, w, (const bf16_t*)shift, (const bf16_t*)scale, modality, any_img, dx, dw, dshift, dscale,
                 (long)mod_stride, (int)M, (int)d, (int)L, norm_type, accumulate, nullptr, 0};
-  int nch = nch_for(d); if (nch > 4) nch = 8;
+  const int nch = nch_dispatch(d);
   int grid = min(grid_rows(M), d < 2048 ? 1024 : 512);   // (measured: 48.6 vs 51.6 us at d = 768 with 1024 blocks, 60.7 vs 57.9 us at d = 2048)
   if (shift) {   // modulated: whole blocks per batch element (M = B L)
     UDM_CHECK_ARG(M % L == 0, "udm_norm_bwd: modulated norm needs M = B * L");
@@ -1872,7 +1874,7 @@ extern "C" int udm_residual_norm_fwd_ada(const float* x_in, const void* branch, 
               (int)M, (int)d, (int)L, norm_type, eps, p_drop, seed, w_next, (bf16_t*)h_out, rstd_next, norm_type ? mean_next : nullptr};
   a.n_shift = (const bf16_t*)next_shift; a.n_scale = (const bf16_t*)next_scale; a.n_mod_stride = (long)next_mod_stride; a.n_modality = next_modality;
   a.n_any_img = next_any_img;
-  int nch = nch_for(d); if (nch > 4) nch = 8;
+  const int nch = nch_dispatch(d);
   DISPATCH_NCH(nch, residual_fwd_kernel, grid_rows(M), stream, a);
   UDM_CHECK_LAUNCH("udm_residual_norm_fwd_ada");
   return 0;
@@ -1888,7 +1890,7 @@ extern "C" int udm_residual_fwd(const float* x_in, const void* branch, float* x_
   UDM_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "udm_residual_fwd: dropout p out of range");
   ResidArgs a{x_in, (const bf16_t*)branch, x_out, w_b, rstd_b, (w_b && norm_type) ? mean_b : nullptr, (const bf16_t*)gate, modality, (long)mod_stride,
               (int)M, (int)d, (int)L, norm_type, eps, p_drop, seed, nullptr, nullptr, nullptr, nullptr};
-  int nch = nch_for(d); if (nch > 4) nch = 8;
+  const int nch = nch_dispatch(d);
   DISPATCH_NCH(nch, residual_fwd_kernel, grid_rows(M), stream, a);
   UDM_CHECK_LAUNCH("udm_residual_fwd");
   return 0;
@@ -1905,7 +1907,7 @@ extern "C" int udm_residual_norm_fwd(const float* x_in, const void* branch, floa
   UDM_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "udm_residual_norm_fwd: dropout p out of range");
   ResidArgs a{x_in, (const bf16_t*)branch, x_out, w_b, rstd_b, (w_b && norm_type) ? mean_b : nullptr, (const bf16_t*)gate, modality, (long)mod_stride,
               (int)M, (int)d, (int)L, norm_type, eps, p_drop, seed, w_next, (bf16_t*)h_out, rstd_next, norm_type ? mean_next : nullptr};
-  int nch = nch_for(d); if (nch > 4) nch = 8;
+  const int nch = nch_dispatch(d);
   DISPATCH_NCH(nch, residual_fwd_kernel, grid_rows(M), stream, a);
   UDM_CHECK_LAUNCH("udm_residual_norm_fwd");
   return 0;
@@ -1923,7 +1925,7 @@ extern "C" int udm_residual_bwd(const float* dx, const void* branch, void* dbran
   if (gate) {   // gated (adaLN-Zero): whole blocks per batch element, the gate gradient's column sums in registers
     UDM_CHECK_ARG(M % L == 0, "udm_residual_bwd: a gate needs M = B * L");
     const int B = (int)(M / L);
-    int nch = nch_for(d); if (nch > 4) nch = 8;
+    const int nch = nch_dispatch(d);
     a.bpb = max(1, min(1024 / B, (int)((L + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)));
     const int grid = B * a.bpb;
     if (w_b && ws && ws_elems >= (int64_t)grid * d && grid >= 64) a.ws = ws;
@@ -1958,7 +1960,7 @@ extern "C" int udm_residual_bwd(const float* dx, const void* branch, void* dbran
     }
     return 0;
   }
-  int nch = nch_for(d); if (nch > 4) nch = 8;
+  const int nch = nch_dispatch(d);
   int grid = min(grid_rows(M), 512);
   if (w_b && ws && grid_rows(M) >= 1024 && ws_elems >= (int64_t)1024 * d) { grid = 1024; a.ws = ws; }   // wide grid, column sums through the workspace
   DISPATCH_NCH(nch, residual_bwd_kernel, grid, stream, a);
