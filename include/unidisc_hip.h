@@ -222,6 +222,20 @@ int udm_attention_bwd_dropout(const void* q, const void* k, const void* v, const
                               int64_t v_stride, int64_t o_stride, int64_t do_stride, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t flags, float p_drop,
                               uint64_t seed, hipStream_t stream);
 
+/* ---- rectangular forward (inference): Lq queries against Lk keys / values of another buffer - a per-layer K / V cache (csrc/attention_kv.hip).
+ * o[b, i, h, :] = softmax_j(q[b, i, h] . k[b, j, h]) v[b, j, h] over the keys 0 <= j < Lk, for the queries 0 <= i < Lq.  The reads the reference's
+ * `eval.attention_caching` states but never makes (models/dit.py:790-812: text queries against [fresh text keys ; cached image keys]).
+ * Addressing: element (b, l, h, :) of an operand lives at base + b * batch + l * stride + h * D (elements); the cache layout of udm_attention_decode
+ * (k_batch = Lmax * H * D, Lk <= Lmax) is one admissible case, q as columns of the [M, 2 d] qk-norm output another.  lse: fp32 [B, H, Lq] as
+ * udm_attention_fwd stores it, or NULL (o is bit-identical either way).
+ * flags: UDM_ATTN_Q_PRESCALED as in udm_attention_fwd, nothing else (bidirectional only: UDM_ATTN_CAUSAL is an argument error).
+ * D = 32 / 64 / 128 / 256.  Argument errors: Lq < 1, Lk < 1, another D, a row or batch stride that is no multiple of 8 elements (or a row stride below
+ * H * D), an operand base that is not 16-byte aligned.  The kernel only reads k and v - appending the current rows' keys is the caller's copy - and never
+ * addresses a key row >= Lk or a query / output row >= Lq.  No key split: ceil(Lq / 128) * B * H workgroups. */
+int udm_attention_fwd_kv(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t D, int64_t q_stride,
+                         int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t q_batch, int64_t k_batch, int64_t v_batch, int64_t o_batch, int64_t flags,
+                         hipStream_t stream);
+
 /* ---- embeddings: EmbeddingLayer models/dit.py:1036-1043 (+modality embedding :1402-1411) ------------- */
 int udm_embedding_fwd(const int64_t* ids, const float* E, const int64_t* modality, const float* Em, float* x, int64_t M, int64_t d, int64_t V,
                       hipStream_t stream);

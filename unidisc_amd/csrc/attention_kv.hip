@@ -1,0 +1,227 @@
+// Rectangular flash attention forward (inference only): Lq queries against Lk keys / values that live in another buffer - a per-layer K / V cache.
+//   o[b, i, h, :] = softmax_j(q[b, i, h] . k[b, j, h]) v[b, j, h],  0 <= i < Lq, 0 <= j < Lk
+// The consumer: the text steps of `eval.attention_caching` with eval.attention_caching_read_cache (text queries against [fresh text keys ; cached image
+// keys], the reference's stated intent at models/dit.py:790-792).  Bidirectional only: a causal form (chunked prefill) has no caller yet and is not built.
+//
+// The body is the 8-wave forward of attention.hip (attn_fwd_kernel) without sample ids and dropout: 128 queries per workgroup (4 waves x 32), 64-key tiles,
+// S^T = K Q^T so that a lane owns one query column and the softmax state is lane-local, K / V tiles by LDS-DMA into two XOR-swizzled stages each, the lazy
+// reference exponent, whole-row O stores through the idle stages at head dim 128.  What differs is the addressing - every operand has its own row AND batch
+// stride (element (b, l, h, :) at base + b batch + l stride + h D), queries are bounded by Lq and keys by Lk.
+// The kernel only reads k and v: appending the current rows' keys is the caller's copy (a fused append would make one workgroup read
+// rows another one writes).  Key rows >= Lk are never addressed (an overhanging tile re-reads row Lk - 1 and masks it), query rows >= Lq neither.
+#include "attention_common.h"
+#include <type_traits>
+
+namespace {
+
+constexpr int BQ = 128;   // query rows per block (4 waves x 32)
+constexpr int BKV = 64;   // keys per tile
+
+// its own argument block: AttnArgs is full and its layout is shared with the generated programs
+struct AttnKvArgs {
+  const bf16_t* q; const bf16_t* k; const bf16_t* v;
+  bf16_t* out;
+  float* lse;           // [B, H, Lq] log2-domain log-sum-exp of the scaled scores, or null
+  long q_stride, k_stride, v_stride, o_stride;   // row strides, elements
+  long q_batch, k_batch, v_batch, o_batch;       // batch strides, elements
+  int B, H, Lq, Lk;
+  float scale_log2;     // log2(e) / sqrt(D); 1 for pre-scaled q
+};
+
+template <int D>
+__global__ __launch_bounds__(256, ATTN_KV_WGS(D)) void attn_fwd_kv_kernel(AttnKvArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // K0 | K1 | V0 | V1   (one array: keeps LDS-DMA waits exact)
+  constexpr int TB = BKV * D * 2;
+  constexpr int KS = D / 16, DB = D / 32;
+  const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int bh, tile_x;
+  attn_block_to_work(blockIdx.x, a.B * a.H, bh, tile_x);   // all query tiles of one (b, h) on one XCD: they share its K / V through that L2
+  const int b = bh / a.H, h = bh % a.H;
+  const int qi = tile_x * BQ + wave * 32 + l31;
+  const bool q_ok = qi < a.Lq;
+
+  bf16x8_t qf[KS];
+  const bf16_t* qrow = a.q + (long)b * a.q_batch + (long)qi * a.q_stride + h * D + hi * 8;
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) qf[ks] = load_frag_global(qrow + ks * 16, q_ok);
+  // (as in attn_fwd_kernel: the compiler's wait for these loads must land before the loop, whose only outstanding vector-memory operations are the
+  // inline-asm LDS-DMA refills it must not wait for)
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));
+
+  f32x16_t oT[DB];
+#pragma unroll
+  for (int i = 0; i < DB; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) oT[i][r] = 0.f;
+  float m = -INFINITY, lsum = 0.f;
+  const float c = a.scale_log2;
+
+  const bf16_t* kbase = a.k + (long)b * a.k_batch + h * D;
+  const bf16_t* vbase = a.v + (long)b * a.v_batch + h * D;
+  using Stg = DmaStager<D, BKV>;
+  DmaPlan<D, BKV> plank, planv;
+  plank.init(a.k_stride, wave, lane);
+  planv.init(a.v_stride, wave, lane);
+  const int t_end = (a.Lk + BKV - 1) / BKV;
+  Stg::issue(kbase, a.k_stride, 0, a.Lk, smem, wave, lane);            // (rows past Lk - 1 are clamped to it: no key row >= Lk is ever addressed)
+  Stg::issue(vbase, a.v_stride, 0, a.Lk, smem + 2 * TB, wave, lane);
+  auto tile = [&](auto st_c, int t) {   // ST = t & 1 as a compile-time constant: fragment addresses are a hoisted per-lane register plus an immediate
+    constexpr int st = decltype(st_c)::value;
+    const int kv0 = t * BKV;
+    const char* Ks = smem + st * TB;
+    const char* Vs = smem + (2 + st) * TB;
+    wait_all_vmem();   // this wave's share of tile t has landed
+    __syncthreads();   // ... and everybody's; all waves are also done with tile t-1, so its stage may be refilled
+    if (t + 1 >= t_end) {
+    } else if (kv0 + 2 * BKV <= a.Lk) {   // the next tile is a full one: offsets are precomputed, the tile base is wave-uniform
+      plank.issue_full(kbase + (long)(kv0 + BKV) * a.k_stride, smem + (st ^ 1) * TB, wave);
+      planv.issue_full(vbase + (long)(kv0 + BKV) * a.v_stride, smem + (2 + (st ^ 1)) * TB, wave);
+    } else {
+      Stg::issue(kbase, a.k_stride, kv0 + BKV, a.Lk, smem + (st ^ 1) * TB, wave, lane);
+      Stg::issue(vbase, a.v_stride, kv0 + BKV, a.Lk, smem + (2 + (st ^ 1)) * TB, wave, lane);
+    }
+    // S^T = K Q^T : [64 keys] x [32 queries per wave]; two alternating 32-key chains, K fragments read two k-steps ahead of their MFMAs
+    f32x16_t sT[2];
+#pragma unroll
+    for (int f = 0; f < 2; ++f)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sT[f][r] = 0.f;
+    {
+      bf16x8_t kq[3][2];
+#pragma unroll
+      for (int pre = 0; pre < 2; ++pre)
+#pragma unroll
+        for (int f = 0; f < 2; ++f) kq[pre][f] = lds_frag(Ks, tile_off<D>(f * 32 + l31, pre * 2 + hi));
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        if (ks + 2 < KS) {
+#pragma unroll
+          for (int f = 0; f < 2; ++f) kq[(ks + 2) % 3][f] = lds_frag(Ks, tile_off<D>(f * 32 + l31, (ks + 2) * 2 + hi));
+        }
+#pragma unroll
+        for (int f = 0; f < 2; ++f) sT[f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kq[ks % 3][f], qf[ks], sT[f], 0, 0, 0);
+      }
+    }
+    if (kv0 + BKV > a.Lk) {   // the ragged last tile (before the running maximum: a masked score contributes exp2(-inf) = 0 exactly)
+#pragma unroll
+      for (int f = 0; f < 2; ++f)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int kl = f * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+          if (kv0 + kl >= a.Lk) sT[f][r] = -INFINITY;
+        }
+    }
+    float p[2][16];
+    float mloc = -INFINITY;
+#pragma unroll
+    for (int f = 0; f < 2; ++f)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, sT[f][r]);
+    mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
+    // Lazy rescale (attn_fwd_kernel): m is the REFERENCE exponent of this query, moved only when some query of the wave saw a score more than 2^8 above it.
+    const bool move = q_ok && (mloc * c > m * c + 8.0f);   // (lanes of query rows past Lq never vote)
+    if (__builtin_amdgcn_ballot_w64(move) != 0) {
+      const float m_new = fmaxf(m, mloc);
+      const float alpha = __builtin_amdgcn_exp2f((m - ((m_new == -INFINITY) ? 0.f : m_new)) * c);
+      lsum *= alpha;
+      m = m_new;
+#pragma unroll
+      for (int i = 0; i < DB; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) oT[i][r] *= alpha;
+    }
+    const float mc = (m == -INFINITY) ? 0.f : m * c;
+    float psum = 0.f;
+#pragma unroll
+    for (int f = 0; f < 2; ++f)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        p[f][r] = __builtin_amdgcn_exp2f(sT[f][r] * c - mc);
+        psum += p[f][r];
+      }
+    lsum += psum;
+    // O^T += V^T P^T
+#pragma unroll
+    for (int cc = 0; cc < 4; ++cc) {
+      bf16x8_t pb = pack8(&p[cc >> 1][8 * (cc & 1)]);
+#pragma unroll
+      for (int i = 0; i < DB; ++i) {
+        bf16x8_t vt = lds_frag_T<D, true>(Vs, cc * 16, i * 32, lane);
+        oT[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vt, pb, oT[i], 0, 0, 0);
+      }
+    }
+  };
+  {
+    int t = 0;
+    for (; t + 1 < t_end; t += 2) {
+      tile(std::integral_constant<int, 0>{}, t);
+      tile(std::integral_constant<int, 1>{}, t + 1);
+    }
+    if (t < t_end) tile(std::integral_constant<int, 0>{}, t);
+  }
+  const float ltot = lsum + __shfl_xor(lsum, 32, 64);
+  const float inv = ltot > 0.f ? 1.f / ltot : 0.f;
+  if (a.lse != nullptr && q_ok && hi == 0) a.lse[((long)b * a.H + h) * a.Lq + qi] = ltot > 0.f ? __builtin_fmaf(m, c, log2f(ltot)) : INFINITY;
+  bf16_t* obase = a.out + (long)b * a.o_batch + h * D;
+  if constexpr (D == 128) {   // whole-row stores through the (now idle) K / V stages; o_stride % 8 == 0 is an argument check of the entry point
+    __syncthreads();
+    const int q0 = tile_x * BQ + wave * 32;
+    store_rows_via_lds_d128(smem + wave * 8192, oT, inv, obase + (long)q0 * a.o_stride, a.o_stride, a.Lq - q0, lane);
+  } else {
+    if (q_ok) {
+      bf16_t* op = obase + (long)qi * a.o_stride;
+#pragma unroll
+      for (int i = 0; i < DB; ++i)
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) {
+          const int d0 = i * 32 + 8 * rg + 4 * hi;
+          *reinterpret_cast<uint2*>(op + d0) = make_uint2(pack2bf(oT[i][rg * 4] * inv, oT[i][rg * 4 + 1] * inv), pack2bf(oT[i][rg * 4 + 2] * inv, oT[i][rg * 4 + 3] * inv));
+        }
+    }
+  }
+}
+
+template <int D>
+void launch_kv(const AttnKvPlan& plan, const AttnKvArgs& a, hipStream_t s) {
+  static bool once = false;
+  if (!once) { (void)hipFuncSetAttribute((const void*)attn_fwd_kv_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes); once = true; }
+  hipLaunchKernelGGL((attn_fwd_kv_kernel<D>), dim3(plan.grid), dim3(256), plan.lds_bytes, s, a);
+}
+}  // namespace
+
+extern "C" int udm_attention_fwd_kv(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t D, int64_t q_stride,
+                                    int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t q_batch, int64_t k_batch, int64_t v_batch, int64_t o_batch, int64_t flags,
+                                    hipStream_t stream) {
+  const char* name = "udm_attention_fwd_kv";
+  UDM_CHECK_ARG(q && k && v && o, "%s: null pointer", name);
+  UDM_CHECK_ARG((flags & ~(int64_t)UDM_ATTN_Q_PRESCALED) == 0, "%s: unknown flags %ld (UDM_ATTN_Q_PRESCALED only: there is no causal form)", name, (long)flags);
+  UDM_CHECK_ARG(B > 0 && H > 0, "%s: empty problem", name);
+  UDM_CHECK_ARG(Lq >= 1 && Lk >= 1, "%s: Lq = %ld, Lk = %ld (both >= 1)", name, (long)Lq, (long)Lk);
+  UDM_CHECK_ARG(D == 32 || D == 64 || D == 128 || D == 256, "%s: head_dim %ld unsupported (32, 64, 128, 256)", name, (long)D);
+  UDM_CHECK_ARG(q_stride % 8 == 0 && k_stride % 8 == 0 && v_stride % 8 == 0 && o_stride % 8 == 0, "%s: row strides must be multiples of 8 elements", name);
+  UDM_CHECK_ARG(q_batch % 8 == 0 && k_batch % 8 == 0 && v_batch % 8 == 0 && o_batch % 8 == 0, "%s: batch strides must be multiples of 8 elements", name);
+  UDM_CHECK_ARG(q_stride >= H * D && k_stride >= H * D && v_stride >= H * D && o_stride >= H * D && q_batch >= 0 && k_batch >= 0 && v_batch >= 0 && o_batch >= 0,
+                "%s: a row stride below H * D, or a negative batch stride", name);
+  UDM_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15) == 0, "%s: operand bases must be 16-byte aligned", name);
+  // 32-bit lane offsets over the 64 rows one LDS-DMA tile spans; int shapes
+  UDM_CHECK_ARG(Lq < (1LL << 30) && Lk < (1LL << 30) && B * H < (1LL << 30) && k_stride * 2 * 64 < (1LL << 31) && v_stride * 2 * 64 < (1LL << 31),
+                "%s: shape or stride too large", name);
+  const AttnKvPlan plan = attn_plan_fwd_kv(AttnKvProblem{(int)D, B, H, Lq, Lk});
+  UDM_CHECK_ARG(plan.grid_ok, "%s: grid too large", name);
+  AttnKvArgs a{};
+  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.out = (bf16_t*)o; a.lse = lse;
+  a.q_stride = q_stride; a.k_stride = k_stride; a.v_stride = v_stride; a.o_stride = o_stride;
+  a.q_batch = q_batch; a.k_batch = k_batch; a.v_batch = v_batch; a.o_batch = o_batch;
+  a.B = (int)B; a.H = (int)H; a.Lq = (int)Lq; a.Lk = (int)Lk;
+  a.scale_log2 = (flags & UDM_ATTN_Q_PRESCALED) ? 1.0f : (1.0f / sqrtf((float)D)) * 1.4426950408889634f;   // pre-scaled q: the scores ARE the base-2 exponents
+  switch (plan.D) {
+    case 256: launch_kv<256>(plan, a, stream); break;
+    case 128: launch_kv<128>(plan, a, stream); break;
+    case 64: launch_kv<64>(plan, a, stream); break;
+    default: launch_kv<32>(plan, a, stream); break;
+  }
+  UDM_CHECK_LAUNCH(name);
+  return 0;
+}

@@ -119,3 +119,33 @@ inline AttnPlan attn_plan_bwd(const AttnProblem& p, const AttnSwitches& sw, int 
   assert(!plan.planes_needed || plan.dq == DQ_GEN64 || (plan.dq == DQ_8WAVE && p.q_prescaled));
   return plan;
 }
+
+// ---- the rectangular forward (attention_kv.hip, udm_attention_fwd_kv): Lq queries against Lk cached keys, inference only --------------------------------------
+// One program: the 8-wave body at 128 queries per workgroup and 64-key tiles, instantiated per head dim, always with the transposing LDS reads.  No key
+// split: the grid is ceil(Lq / 128) B H workgroups whatever Lk is (256 at B 8, H 16, Lq 256; 32 at B 1 - DESIGN.md "Modality KV cache" has the prices).
+// Workgroups per CU the kernel is compiled for (the square forward's numbers: at head dim 256 the four 32 KiB stages and 128 + 64 registers of O^T and Q leave
+// room for one).
+constexpr int ATTN_KV_WGS(int D) { return D == 256 ? 1 : 2; }
+struct AttnKvProblem {
+  int D;
+  long B, H, Lq, Lk;
+};
+struct AttnKvPlan {
+  int D = 0;
+  uint32_t q_tiles = 0;     // 128-query blocks per (b, h)
+  uint32_t kv_tiles = 0;    // 64-key tiles every block walks
+  uint32_t grid = 0;        // q_tiles * B * H workgroups of 256 threads
+  uint32_t lds_bytes = 0;   // K0 | K1 | V0 | V1
+  bool grid_ok = false;     // the grid fits 31 bits
+};
+inline AttnKvPlan attn_plan_fwd_kv(const AttnKvProblem& p) {
+  AttnKvPlan plan;
+  plan.D = p.D;
+  const long qt = (p.Lq + 127) / 128, grid = qt * p.B * p.H;
+  plan.grid_ok = grid > 0 && grid < (1L << 31);
+  plan.q_tiles = (uint32_t)qt;
+  plan.kv_tiles = (uint32_t)((p.Lk + 63) / 64);
+  plan.grid = plan.grid_ok ? (uint32_t)grid : 0;
+  plan.lds_bytes = (uint32_t)(4 * 64 * p.D * 2);
+  return plan;
+}

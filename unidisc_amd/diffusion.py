@@ -626,9 +626,10 @@ class Diffusion:
             sigma_t, _ = self.noise(t)
             sig = self._process_sigma(sigma_t)
             block_mask = kwargs.get("block_mask")
-            p_x0 = self._guided_masked_logits(x, t, sig, x0_unmask, modality, sample_ids) if block_mask is None else None
+            mc_kw = dict(modality_cache=kwargs["modality_cache"]) if kwargs.get("modality_cache") is not None else {}   # (eval.attention_caching_read_cache)
+            p_x0 = self._guided_masked_logits(x, t, sig, x0_unmask, modality, sample_ids) if (block_mask is None and not mc_kw) else None
             if p_x0 is None:
-                p_x0 = self.backbone.forward_masked_logits(x, sig, modality=modality, sample_ids=sample_ids, block_mask=block_mask)
+                p_x0 = self.backbone.forward_masked_logits(x, sig, modality=modality, sample_ids=sample_ids, block_mask=block_mask, **mc_kw)
             nfe = 1
         logits, rows, n = p_x0[:3]
         logits_u, w_rows = (p_x0[3], p_x0[4]) if len(p_x0) == 5 else (None, None)
@@ -989,11 +990,27 @@ class Diffusion:
                 raise NotImplementedError("unidisc_amd.Diffusion.sample: eval.attention_caching is built for the unconditional ddpm_cache predictor only")
             from .dit import ModalityMask
             Lt = int(cfg_get(cfg_get(self.config, "model"), "txt_length"))
-            self.backbone.set_flex_attention_cache(B, L, self.device, None)
+            # eval.attention_caching_read_cache (extension key, default false: the reference's behaviour above): the build step also fills a per-block K / V
+            # cache with every position's keys, and the text steps attend to [fresh text keys ; cached image keys] instead of the text keys alone - what the
+            # reference's comment at models/dit.py:790-792 intends.  The cached image keys are those of the x that ENTERED the last build step; they are not
+            # refreshed by the tokens that step or the next full step draw (the next build step does that).
+            read_cache = bool(cfg_get(ev, "attention_caching_read_cache", False))
+            if read_cache:
+                if self.time_conditioning:
+                    raise NotImplementedError("unidisc_amd.Diffusion.sample: eval.attention_caching_read_cache with time_conditioning - the cached image keys "
+                                              "would depend on sigma")
+                if modality is not None and not (bool((modality[:, :Lt] == 0).all()) and bool((modality[:, Lt:] != 0).all())):
+                    raise NotImplementedError("unidisc_amd.Diffusion.sample: eval.attention_caching_read_cache needs the text in the static slice [:txt_length] "
+                                              "of every sample")
+                self.backbone.set_flex_attention_cache(B, L, self.device, None, read_cache=True)
+            else:
+                self.backbone.set_flex_attention_cache(B, L, self.device, None)
         sliced, saved = False, None
+        read_cache = caching and read_cache
         for i in range(num_steps):
             t = timesteps[i] * torch.ones(B, 1, device=self.device)
             block_mask = None
+            mc_kw = {}
             if caching:
                 if i % ratio == 0:
                     if sliced:   # the saved full tensors take the text slice back
@@ -1005,12 +1022,16 @@ class Diffusion:
                 elif (i - 1) % ratio == 0:
                     block_mask = ModalityMask(torch.zeros(B, dtype=torch.bool, device=self.device), torch.ones(B, dtype=torch.bool, device=self.device), Lt)
                     self.sample_step_modes.append("build")
+                    if read_cache:   # the step must run its forward (a reused logits cache would leave the K / V cache unbuilt or stale)
+                        cache, mc_kw = None, dict(modality_cache="build")
                 else:
                     if not sliced:
                         saved = (x.clone(), modality, cache)
                         cache = self._cache_to_text(cache, L, Lt)
                         x, modality, sliced = x[:, :Lt].contiguous(), (None if modality is None else modality[:, :Lt].contiguous()), True
                     self.sample_step_modes.append("text")
+                    if read_cache:
+                        mc_kw = dict(modality_cache="read")
             if predictor in ("maskgit", "maskgit_nucleus"):   # replay: list of (pred [B, L] or None, gumbel [B, L] or None) per step
                 pr, gm = replay[i] if replay is not None else (None, None)
                 upd = self._maskgit_update if predictor == "maskgit" else self._maskgit_nucleus_update
@@ -1027,7 +1048,7 @@ class Diffusion:
                 nfe += n
                 continue
             cache, x_next, n = self._ddpm_caching_update(x, t, dt, p_x0=cache, x0=x0, x0_unmask=x0_unmask, modality=modality, sample_ids=sample_ids,
-                                                         u=noise[i] if noise is not None else None, seed=base_seed + 7919 * i, block_mask=block_mask)
+                                                         u=noise[i] if noise is not None else None, seed=base_seed + 7919 * i, block_mask=block_mask, **mc_kw)
             nfe += n
             if self.time_conditioning or not torch.equal(x_next, x):
                 cache = None  # the reference's `if not allclose(x_next, x) or time_conditioning: p_x0_cache = None`

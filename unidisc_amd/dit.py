@@ -243,6 +243,7 @@ class DIT(nn.Module, _HubMixin):
             raise NotImplementedError("unidisc_amd.DIT: model.use_kv_cache (inference KV cache) needs a causal backbone (model.full_attention=false, the AR "
                                       "baseline): a bidirectional block's keys change with every new token")
         self._kv = None
+        self._mc = None
         # model.full_attention=false (models/dit.py:1118, the AR baseline of configs/experiments/ar.yaml): every block attends causally (sdpa is_causal=True,
         # :768 / :826 / :843) - the attention kernels' UDM_ATTN_CAUSAL form.  The reference never combines it with another mask: an attention_mask beside
         # is_causal is an SDPA error, and the packed / flex-mask paths sit inside `parameterization != "ar"`.
@@ -362,8 +363,11 @@ class DIT(nn.Module, _HubMixin):
 
     # Reference API surface that callers touch.  `eval.attention_caching` (model_eval.py:2296-2366): the reference allocates a per-layer
     # K / V buffer here and WRITES it in the cache-building / text-only steps (models/dit.py:797-803), but no forward ever reads it back (:812 attends
-    # to the keys of the current input only) - so the sampler's three kinds of step need no state in the backbone: `Diffusion.sample` passes the
-    # image-queries-see-image-keys mask / the text slice itself.  The two calls are accepted and remembered for callers that probe them.
+    # to the keys of the current input only).  The default path reproduces that and needs no state in the backbone: `Diffusion.sample` passes the
+    # image-queries-see-image-keys mask / the text slice itself, and the two calls are accepted and remembered for callers that probe them.
+    # The read-cache path (extension key eval.attention_caching_read_cache, set_flex_attention_cache(..., read_cache=True)) does what the reference's
+    # comment at :790-792 intends and DOES need state: per block bf16 K / V [B, L, d], filled by the build step and read by every text step
+    # (forward_masked_logits(modality_cache=...)); reset_kv_cache() frees it.
     #
     # With arguments (`_ar_sampler`, model_eval.py:2736-2822) it is the AR baseline's KV cache: per block bf16 K / V [rows, seq_len, d] (rows padded to a
     # multiple of 8), the decode step's buffers and its rotary rows, allocated once here.  `modality` (extension, full length [batch_size, model.length]):
@@ -371,6 +375,7 @@ class DIT(nn.Module, _HubMixin):
     # (the ones training used), so decode step p equals row p of the causal forward.  set_to_none=True frees everything.
     def reset_kv_cache(self, batch_size=None, seq_len=None, dtype=None, device=None, set_to_none=False, modality=None):
         self.use_flex_attention_cache = False
+        self._mc = None   # the modality K / V cache of set_flex_attention_cache(read_cache=True)
         if set_to_none:
             self._kv = None
             return
@@ -503,8 +508,29 @@ class DIT(nn.Module, _HubMixin):
         kv.pos = n
         return out if last_only else out[:B]
 
-    def set_flex_attention_cache(self, batch_size=None, seq_len=None, device=None, dtype=None):
+    def set_flex_attention_cache(self, batch_size=None, seq_len=None, device=None, dtype=None, read_cache=False):
+        """read_cache (extension, eval.attention_caching_read_cache): allocate per block bf16 K / V [batch_size, seq_len, d] (2 GB at 1.4 B, B = 8) that the
+        build step fills (every position's post-rope k and its v) and the text steps read: forward_masked_logits(modality_cache="build" / "read")."""
         self.use_flex_attention_cache = True
+        self._mc = None
+        if not read_cache:
+            return
+        if self.time_conditioning:
+            raise NotImplementedError("unidisc_amd.DIT.set_flex_attention_cache(read_cache=True): with time_conditioning the cached image keys would depend on sigma")
+        if self.causal or self.require_sample_ids:
+            raise NotImplementedError("unidisc_amd.DIT.set_flex_attention_cache(read_cache=True): built for bidirectional backbones on unpacked batches")
+        sl = self.static_txt_sl
+        if self.txt_length <= 0 or self.img_length <= 0 or (sl is not None and ((sl.start or 0) != 0 or sl.stop != self.txt_length or sl.step not in (None, 1))):
+            raise NotImplementedError("unidisc_amd.DIT.set_flex_attention_cache(read_cache=True): the text must be the static slice [:txt_length] of the sequence "
+                                      f"(static_txt_sl = {sl}, txt_length = {self.txt_length}, img_length = {self.img_length})")
+        B, L = int(batch_size), int(seq_len)
+        if L != self.total_length:
+            raise ValueError(f"unidisc_amd.DIT.set_flex_attention_cache(read_cache=True): seq_len {L} is not model.length = {self.total_length}")
+        dev = torch.device(device) if device is not None else self.vocab_embed.embedding.device
+        mc = types.SimpleNamespace(B=B, L=L, Lt=int(self.txt_length), built=False, cos=None, sin=None, mod=None)
+        mc.K = [torch.zeros((B, L, self.hidden_size), dtype=BF16, device=dev) for _ in self.blocks]
+        mc.V = [torch.zeros((B, L, self.hidden_size), dtype=BF16, device=dev) for _ in self.blocks]
+        self._mc = mc
 
     # -------------------------------------------------------------------------------------------- parameters / shadows
     IMG_BLOCKS = ((256, 1), (1024, 2), (2304, 3), (4096, 4))   # (tokens of an image block, Lumina linear factor), models/dit.py:1210
@@ -695,13 +721,46 @@ class DIT(nn.Module, _HubMixin):
         return _DitFn.apply(self, "logp", inputs, *params)
 
     @torch.no_grad()
-    def forward_masked_logits(self, xt, sigma=None, modality=None, sample_ids=None, plan_ids=None, block_mask=None):
+    def forward_masked_logits(self, xt, sigma=None, modality=None, sample_ids=None, plan_ids=None, block_mask=None, modality_cache=None):
         """Sampler path: (logits [R, Vp] bf16 of the [MASK] positions of `xt` first, then padding rows; their flat row indices [R];
         the number of [MASK] rows).  Unmasked positions keep their token under SUBS (model.py:646-656), so they need no logits.
         `plan_ids` (same shape as xt): take the row selection from the [MASK] positions of this tensor instead of xt's (guided sampling runs
-        [x ; x_uncond] as one batch and needs the SAME positions from both halves)."""
+        [x ; x_uncond] as one batch and needs the SAME positions from both halves).
+        `modality_cache` (set_flex_attention_cache(read_cache=True) first): "build" - a full-length forward (the caller passes the image-queries-see-image-keys
+        ModalityMask) that also leaves every block's post-rope k and its v of all L positions in the cache; "read" - xt is the text slice [B, txt_length]: the
+        backbone runs on those rows alone, with the modality ids and rotary rows of the full-length forward, writes their k / v into cache slots [0, txt_length)
+        and attends to [fresh text keys ; cached image keys] (udm_attention_fwd_kv).  Under the build step's mask the image rows never see a text key, so their
+        K / V depend on the image tokens alone: a "read" step equals the text rows of the masked full-length forward on [xt ; image tokens of the build step]."""
         inputs = dict(indices=xt, sigma=sigma, modality=modality, sample_ids=sample_ids, x0=None, save=False, plan_ids=plan_ids,
                       block_mask=block_mask if isinstance(block_mask, ModalityMask) else None)
+        mc = self._mc
+        if modality_cache is not None:
+            if modality_cache not in ("build", "read"):
+                raise ValueError(f"unidisc_amd.DIT.forward_masked_logits: modality_cache={modality_cache!r} (\"build\", \"read\" or None)")
+            if mc is None:
+                raise RuntimeError("unidisc_amd.DIT.forward_masked_logits(modality_cache=...): no modality cache - call set_flex_attention_cache(B, L, device, dtype, "
+                                   "read_cache=True) first")
+            if sample_ids is not None or plan_ids is not None or sigma is not None and self.time_conditioning:
+                raise NotImplementedError("unidisc_amd.DIT.forward_masked_logits(modality_cache=...): no packed sample ids, guidance halves or time conditioning")
+            B, Lx = xt.shape
+            if B != mc.B or Lx != (mc.L if modality_cache == "build" else mc.Lt):
+                raise ValueError(f"unidisc_amd.DIT.forward_masked_logits(modality_cache={modality_cache!r}): xt {tuple(xt.shape)}, the cache serves "
+                                 f"[{mc.B}, {mc.L}] with {mc.Lt} text positions")
+        if modality_cache == "build":
+            inputs["kv_sink"] = list(zip(mc.K, mc.V))
+            out, S = self._engine_forward(inputs, "rows", save=False)
+            mc.cos, mc.sin = S["cos"], S["sin"]                                   # the full-length rotary tables ([L, D/2], or per sample [B, L, D/2])
+            mc.mod = modality.to(torch.int64).contiguous() if modality is not None else None
+            mc.built = True
+            return out
+        if modality_cache == "read":
+            if not mc.built:
+                raise RuntimeError("unidisc_amd.DIT.forward_masked_logits(modality_cache=\"read\"): the cache holds no image keys yet (no \"build\" step ran)")
+            Lt = mc.Lt
+            if mc.mod is not None:   # row p takes exactly the modality id and the rotary row of the full-length forward
+                inputs["modality"] = mc.mod[:, :Lt].contiguous()
+            inputs["rope"] = (mc.cos[..., :Lt, :].contiguous(), mc.sin[..., :Lt, :].contiguous())
+            inputs["kv_read"] = dict(K=mc.K, V=mc.V, slot0=0, Lk=mc.L)
         out, _ = self._engine_forward(inputs, "rows", save=False)
         return out
 
@@ -905,6 +964,9 @@ class DIT(nn.Module, _HubMixin):
             cos, sin = self._rotary(modality, L)
         S["cos"], S["sin"] = cos, sin
         kv_sink = inp.get("kv_sink")
+        kv_read = inp.get("kv_read")   # attend to a K / V cache: dict(K, V: per block [B, Lmax, d]; slot0: where this call's rows go; Lk: the slots the queries see)
+        if kv_read is not None and (sid is not None or save or kv_sink is not None or self.causal):
+            raise NotImplementedError("unidisc_amd.DIT: the cache-reading forward is an inference path without masks (no sample ids, ModalityMask, attention mask)")
 
         any_img = None
         if tc:
@@ -960,7 +1022,13 @@ class DIT(nn.Module, _HubMixin):
             if kv_sink is not None:   # KV-cache prefill: the post-rope k and the v of every position into cache slots [0, L)
                 kv_sink[i][0][:, :L].copy_(qkr.view(B, L, 2 * d)[:, :, d:])
                 kv_sink[i][1][:, :L].copy_(qkv.view(B, L, 3 * d)[:, :, 2 * d:])
-            o, lse = K.attention_fwd(qkr, qkv, B, L, H, D, sid, S["doc_ranges"], q_prescaled=True, **self._attn_mask_kw, **S["attn_drop_kw"](i))
+            if kv_read is not None:   # this call's post-rope k and v into cache slots [slot0, slot0 + L) (the kernel only reads), then the L queries against slots [0, Lk)
+                s0 = kv_read["slot0"]
+                kv_read["K"][i][:, s0:s0 + L].copy_(qkr.view(B, L, 2 * d)[:, :, d:])
+                kv_read["V"][i][:, s0:s0 + L].copy_(qkv.view(B, L, 3 * d)[:, :, 2 * d:])
+                o, lse = K.attention_fwd_kv(qkr[:, :d], kv_read["K"][i], kv_read["V"][i], B, L, kv_read["Lk"], H, D, q_prescaled=True), None
+            else:
+                o, lse = K.attention_fwd(qkr, qkv, B, L, H, D, sid, S["doc_ranges"], q_prescaled=True, **self._attn_mask_kw, **S["attn_drop_kw"](i))
             rows_c = last_rows
             if not recompute and i + 1 == self.n_blocks and head_plan is not None and mode == "logp" and self.compact_last_block and not tc:
                 head_rows_c = self._masked_rows(head_plan, M)   # (the count was queued at the top of this forward: the host does not wait for the device here)

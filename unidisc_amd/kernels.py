@@ -816,6 +816,22 @@ def attention_fwd(qkr, qkv, B, L, H, D, sample_ids=None, doc_ranges=None, q_pres
     return o, lse
 
 
+def attention_fwd_kv(q, k_cache, v_cache, B, Lq, Lk, H, D, q_prescaled=False, out=None, want_lse=False):
+    """Lq queries per sample against the first Lk slots of a K / V cache (udm_attention_fwd_kv; inference only, no key is written).  q: a 2-D row view
+    [B * Lq, H D] with any 16-byte aligned row stride (the q columns of the qk-norm output); k_cache / v_cache: bf16 [B, Lmax, H D] with Lk <= Lmax.
+    Bidirectional.  Returns o [B * Lq, H D] (and lse [B, H, Lq] with want_lse)."""
+    d = H * D
+    Bc, Lmax, dc = k_cache.shape
+    if Bc < B or dc != d or Lk > Lmax or tuple(v_cache.shape) != tuple(k_cache.shape) or k_cache.stride(2) != 1 or v_cache.stride(2) != 1 or q.stride(1) != 1:
+        raise ValueError(f"attention_fwd_kv: cache {tuple(k_cache.shape)} / {tuple(v_cache.shape)} does not serve B={B}, Lk={Lk}, H D={d}")
+    if out is None:
+        out = torch.empty((B * Lq, d), dtype=BF16, device=q.device)
+    lse = torch.empty((B, H, Lq), dtype=F32, device=q.device) if want_lse else None
+    _lib.call("udm_attention_fwd_kv", _p(q), _p(k_cache), _p(v_cache), _p(out), _p(lse), B, H, Lq, Lk, D, q.stride(0), k_cache.stride(1), v_cache.stride(1),
+              out.stride(0), Lq * q.stride(0), k_cache.stride(0), v_cache.stride(0), Lq * out.stride(0), _attn_flags(q_prescaled, False), _s())
+    return (out, lse) if want_lse else out
+
+
 def attention_bwd(qkr, qkv, o, do, lse, dqkr, dqkv, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False, causal=False, dropout_p=0.0, seed=0):
     """Writes dq|dk (wrt the stored rotated q, k) into dqkr [M,2d] and dv into dqkv[:, 2d:3d].  dropout_p, seed: those of the forward."""
     d = H * D
