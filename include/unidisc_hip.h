@@ -385,6 +385,26 @@ int udm_ar_sample_rows(const void* logits, const void* logits_uncond, const floa
                        int64_t ldg, int64_t g_col0, uint64_t seed, int64_t step, int64_t* x, int64_t ldx, const int64_t* x0, const void* x0_unmask, int64_t pos,
                        int64_t* next_ids, int64_t R, int64_t V, int64_t Vt, int64_t mask_id, int restrict_modality, hipStream_t stream);
 
+/* ---- Top-p (nucleus) sampling without a sort: `nucleus_sampling_batch` model_eval.py:2642-2685 (the maskgit_nucleus predictor) and `nucleus_sampling`
+ * :2691-2734 (the AR sampler's eval.top_p), one workgroup per row, the row read once into registers (V <= 65536, larger V is an argument error).
+ *   valid ids, z and the guidance mix as in udm_categorical_sample_rows; p = softmax(inv_temperature z) over the valid ids; the valid ids ordered by
+ *   descending p, ascending id among equal values; kept = the longest prefix of that order with cumulative p <= budget, the first id always kept; token =
+ *   argmax over the kept ids of p_i / (1e-10 - log(u_i + 1e-10)), first index on ties, u explicit ([M, ldu] fp32) or Philox keyed as in
+ *   udm_categorical_sample_rows.  nucleus_sampling_batch(top_p, T) is inv_temperature = 1, budget = top_p T; nucleus_sampling(top_p, T) is
+ *   inv_temperature = 1 / T, budget = top_p.  Columns that are not valid ids (mask_id, the other modality, V <= column < ld) are never looked at: they may
+ *   hold NaN.  Two launches on the same inputs give bit-identical outputs.
+ * udm_nucleus_sample_rows: out[row] = the token, out_logp[row] = log p_1(token) under the unfiltered distribution at temperature 1 (the maskgit
+ *   confidence), out_keep[row] (nullable) = the size of the kept prefix.  M = 0 is a no-op.
+ * udm_ar_nucleus_rows: the token choice of udm_ar_sample_rows with the nucleus draw in place of argmax(z + g): u[r * ldu + u_col0 + id] explicit uniforms
+ *   or Philox keyed by (seed, step, row, id); scalar *w; the same write-back to x[r, pos], next_ids[r] and next_ids[R + r]. */
+int udm_nucleus_sample_rows(const void* logits, const void* logits_uncond, const float* w, int64_t ld, const int64_t* modality, const float* u, int64_t ldu,
+                            uint64_t seed, float inv_temperature, float budget, int64_t* out, float* out_logp, int64_t* out_keep, int64_t M, int64_t V,
+                            int64_t Vt, int64_t mask_id, int restrict_modality, hipStream_t stream);
+int udm_ar_nucleus_rows(const void* logits, const void* logits_uncond, const float* w, int64_t ld, const int64_t* modality, int64_t ldm, const float* u,
+                        int64_t ldu, int64_t u_col0, uint64_t seed, int64_t step, float inv_temperature, float budget, int64_t* x, int64_t ldx,
+                        const int64_t* x0, const void* x0_unmask, int64_t pos, int64_t* next_ids, int64_t R, int64_t V, int64_t Vt, int64_t mask_id,
+                        int restrict_modality, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

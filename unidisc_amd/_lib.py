@@ -87,6 +87,8 @@ PROTOTYPES = {
     "udm_gemm_skinny_bf16": [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _P, _P, _I64, _P],
     "udm_attention_decode": [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P],
     "udm_ar_sample_rows": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _U64, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I, _P],
+    "udm_nucleus_sample_rows": [_P, _P, _P, _I64, _P, _P, _I64, _U64, _F, _F, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P],
+    "udm_ar_nucleus_rows": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _U64, _I64, _F, _F, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I, _P],
 }
 EXTRA_SYMBOLS = ["udm_last_error", "udm_abi_version"]
 ABI_VERSION = 4   # the UDM_ABI_VERSION of include/unidisc_hip.h that PROTOTYPES was written for (bumped whenever a signature changes)

@@ -701,7 +701,7 @@ class Diffusion:
     def _nucleus_draw(self, logits, logits_u, w_rows, row_modality, top_p, temperature, seed):
         """Token per [MASK] row from the nucleus-filtered SUBS distribution (`nucleus_sampling_batch`, model_eval.py:2642-2685, quirks included: the
         temperature divides probabilities, the top id always stays).  Sort / cumsum / multinomial over [rows, V] are device tensor ops in row
-        chunks (an evaluation-time sampler variant: no fused kernel)."""
+        chunks: the default path; with eval.fused_nucleus the step draws through `udm_nucleus_sample_rows` instead (`_maskgit_update`)."""
         V, Vt = self.vocab_size, self.text_vocab_size
         out = torch.empty(logits.shape[0], dtype=torch.int64, device=logits.device)
         gen = torch.Generator(device=logits.device).manual_seed(int(seed) + 2)
@@ -752,12 +752,28 @@ class Diffusion:
         logits_u, w_rows = (cache[3], cache[4]) if len(cache) == 5 else (None, None)
         rows_n = rows[:n]
         given = pred.reshape(-1).index_select(0, rows_n).contiguous() if pred is not None else None
+        if given is None and nucleus is not None and n > 0 and self._fused_nucleus(logits):
+            # eval.fused_nucleus: token and log p(token) from one launch (`udm_nucleus_sample_rows`); nucleus_sampling_batch divides the probabilities by the
+            # temperature, which is the temperature-1 distribution against the budget top_p * temperature
+            tok, logp = K.nucleus_sample_rows(logits[:n], self.vocab_size, self.text_vocab_size, self.mask_index, inv_temperature=1.0,
+                                              budget=nucleus[0] * nucleus[1], modality=self._row_modality(rows_n, B, L, modality), restrict=self._restrict(),
+                                              seed=int(seed if seed is not None else torch.initial_seed()) + 2, logits_u=logits_u, w=w_rows)
+            return self._maskgit_reveal(x, copy_flag, num_unmask, rows_n, tok, logp, gumbel, seed, r_temp, t_col)
         if given is None and nucleus is not None and n > 0:
             given = self._nucleus_draw(logits[:n], logits_u, w_rows, self._row_modality(rows_n, B, L, modality), nucleus[0], nucleus[1],
                                        int(seed if seed is not None else torch.initial_seed()))
         tok, logp = K.categorical_sample_rows(logits[:n], self.vocab_size, self.text_vocab_size, self.mask_index,
                                               modality=self._row_modality(rows_n, B, L, modality), restrict=self._restrict(), given=given,
                                               seed=int(seed if seed is not None else torch.initial_seed()), logits_u=logits_u, w=w_rows)
+        return self._maskgit_reveal(x, copy_flag, num_unmask, rows_n, tok, logp, gumbel, seed, r_temp, t_col)
+
+    def _fused_nucleus(self, logits):
+        """eval.fused_nucleus (extension key, default false) and a case the fused top-p kernels take: logits on the GPU, a vocabulary they hold in registers"""
+        return bool(cfg_get(cfg_get(self.config, "eval", None), "fused_nucleus", False)) and K.nucleus_supported(logits, self.vocab_size)
+
+    def _maskgit_reveal(self, x, copy_flag, num_unmask, rows_n, tok, logp, gumbel, seed, r_temp, t_col):
+        """the second half of a maskgit step: confidence = log p + r_temp * gumbel * t, each sample keeps its num_unmask most confident predictions"""
+        B, L = x.shape
         if gumbel is None:
             g = torch.Generator(device=x.device).manual_seed(int(seed if seed is not None else torch.initial_seed()) + 1)
             u = torch.rand(B, L, device=x.device, generator=g).clamp_(1e-20, 1.0)
@@ -902,7 +918,14 @@ class Diffusion:
         gen = torch.Generator(device=dev).manual_seed(base_seed + 3) if top_p is not None else None
         logits = kv.logits
 
+        fused_top_p = top_p is not None and self._fused_nucleus(logits)
+
         def choose(i):   # token of position i + 1 from kv.logits (the next-token logits of position i); writes x and kv.ids
+            if fused_top_p:   # eval.fused_nucleus: nucleus_sampling (softmax(z / T) against top_p) in one launch, no tensor operators
+                K.ar_nucleus_rows(logits, x, i + 1, V, Vt, self.mask_index, inv_temperature=1.0 / temperature, budget=float(top_p), step=i, modality=modality,
+                                  restrict=restrict, seed=base_seed, x0=x0, x0_unmask=x0_unmask, next_ids=kv.ids,
+                                  logits_u=logits[B:] if guided else None, w=w if guided else None, rows=B)
+                return
             if top_p is None:
                 K.ar_sample_rows(logits, x, i + 1, V, Vt, self.mask_index, step=i, modality=modality, restrict=restrict, g=noise,
                                  g_col0=i * V, seed=base_seed, x0=x0, x0_unmask=x0_unmask, next_ids=kv.ids,

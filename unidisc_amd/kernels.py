@@ -1054,3 +1054,57 @@ def ar_sample_rows(logits, x, pos, V, Vt, mask_id, *, step=0, modality=None, res
               g.stride(0) if g is not None else 0, int(g_col0), int(seed), int(step), _p(x), x.stride(0), _p(x0), _p(x0_unmask), int(pos), _p(next_ids), R, V, Vt,
               mask_id, 1 if restrict else 0, _s())
     return x
+
+
+NUCLEUS_V_MAX = 65536   # udm_nucleus_sample_rows / udm_ar_nucleus_rows hold the row in registers: a larger vocabulary is refused (the hosts keep the tensor path)
+
+
+def nucleus_supported(logits, V):
+    """whether the fused top-p kernels take this case: bf16 logits on a GPU and a vocabulary of at most NUCLEUS_V_MAX ids (the callers keep their tensor path
+    otherwise)"""
+    return bool(logits.is_cuda) and logits.dtype == BF16 and int(V) <= NUCLEUS_V_MAX
+
+
+def nucleus_sample_rows(logits, V, Vt, mask_id, *, inv_temperature, budget, modality=None, restrict=False, u=None, seed=0, logits_u=None, w=None,
+                        want_keep=False):
+    """(token, log p_1(token)[, kept]) per row of `logits` [rows, ld] bf16: the token drawn from the top-p filtered SUBS distribution in one launch.
+    p = softmax(inv_temperature z) over the valid ids, kept = the longest prefix of the stable descending order with cumulative p <= budget (the top id
+    always); log p_1 is the unfiltered log-probability at temperature 1.  `nucleus_sampling_batch(top_p, T)` is inv_temperature = 1, budget = top_p T;
+    `nucleus_sampling(top_p, T)` is inv_temperature = 1 / T, budget = top_p.  u fp32 [rows, >= V]: explicit uniforms (replay), else Philox(seed)."""
+    _chk(logits, BF16, "nucleus_sample_rows logits")
+    M = logits.shape[0]
+    if (logits_u is None) != (w is None):
+        raise ValueError("nucleus_sample_rows: guidance needs both logits_u and w")
+    if logits_u is not None and (logits_u.shape != logits.shape or logits_u.stride(0) != logits.stride(0) or w.numel() != M):
+        raise ValueError("nucleus_sample_rows: logits_u must match logits and w must have one weight per row")
+    if u is not None:
+        _chk(u, F32, "nucleus_sample_rows u")
+    tok = torch.empty(M, dtype=torch.int64, device=logits.device)
+    logp = torch.empty(M, dtype=torch.float32, device=logits.device)
+    keep = torch.empty(M, dtype=torch.int64, device=logits.device) if want_keep else None
+    _lib.call("udm_nucleus_sample_rows", _p(logits), _p(logits_u), _p(w), logits.stride(0), _p(modality), _p(u), u.stride(0) if u is not None else 0,
+              int(seed), float(inv_temperature), float(budget), _p(tok), _p(logp), _p(keep), M, V, Vt, mask_id, 1 if restrict else 0, _s())
+    return (tok, logp, keep) if want_keep else (tok, logp)
+
+
+def ar_nucleus_rows(logits, x, pos, V, Vt, mask_id, *, inv_temperature, budget, step=0, modality=None, restrict=False, u=None, u_col0=0, seed=0, x0=None,
+                    x0_unmask=None, next_ids=None, logits_u=None, w=None, rows=None):
+    """`ar_sample_rows` with the top-p draw in place of argmax(z + Gumbel): x[r, pos] = a token of the nucleus of softmax(inv_temperature z) for r < rows,
+    the x0 write-back and next_ids as there.  u: explicit uniforms [rows, ldu] fp32 read at column u_col0 + id, else Philox keyed by (seed, step, row, id)."""
+    _chk(logits, BF16, "ar_nucleus_rows logits")
+    R = x.shape[0] if rows is None else rows
+    if (logits_u is None) != (w is None):
+        raise ValueError("ar_nucleus_rows: guidance needs both logits_u and w")
+    if logits_u is not None and logits_u.stride(0) != logits.stride(0):
+        raise ValueError("ar_nucleus_rows: logits_u must have the row stride of logits")
+    for t, name in ((x, "x"), (x0, "x0"), (modality, "modality")):
+        if t is not None and (t.dtype != torch.int64 or t.stride(-1) != 1):
+            raise TypeError(f"ar_nucleus_rows: {name} must be int64 with contiguous rows")
+    if x0_unmask is not None and (x0_unmask.dtype != torch.bool or x0_unmask.stride(0) != x.stride(0) or x0.stride(0) != x.stride(0)):
+        raise TypeError("ar_nucleus_rows: x0 / x0_unmask must be laid out like x (bool mask)")
+    if u is not None:
+        _chk(u, F32, "ar_nucleus_rows u")
+    _lib.call("udm_ar_nucleus_rows", _p(logits), _p(logits_u), _p(w), logits.stride(0), _p(modality), modality.stride(0) if modality is not None else 0, _p(u),
+              u.stride(0) if u is not None else 0, int(u_col0), int(seed), int(step), float(inv_temperature), float(budget), _p(x), x.stride(0), _p(x0),
+              _p(x0_unmask), int(pos), _p(next_ids), R, V, Vt, mask_id, 1 if restrict else 0, _s())
+    return x
