@@ -268,7 +268,12 @@ int udm_silu_bwd(const void* x, const void* dy, void* dx, int64_t n, hipStream_t
  * p = exp(SUBS log-probs) (`_ddpm_forward` model_eval.py:1761-1834 no-CFG branch); q_i = p_i (t - s), q_mask = s (`_ddpm_caching_update`
  * :2073-2106); out = argmax_i q_i / (1e-10 - log(u_i + 1e-10)) (`_sample_categorical` model_utils.py:95-97; first index on ties).
  * logits: [M, ld] rows of masked positions only; t / s: per-row move chance now / next; u: explicit uniforms [M, ldu] (parity runs replay the
- * reference's rand stream) or NULL -> Philox(seed).  greedy != 0: argmax of the log-probs (`noise_removal` :2437-2444), t / s / u ignored. */
+ * reference's rand stream) or NULL -> Philox(seed).  greedy != 0: argmax of the log-probs (`noise_removal` :2437-2444), t / s / u ignored.
+ * Philox layout (this entry point, _cfg and udm_categorical_sample_rows): Philox4x32-10 with key = seed and the 64-bit counter row ceil(V / 4) + (id >> 2);
+ * id takes word id & 3 of the four words x y z w, and u = (word >> 8) 2^-24, in [0, 1).
+ * Columns a row does not depend on (they may hold NaN): logits and logits_uncond in [V, ld), on the other modality's ids under restrict_modality and - except
+ * with greedy, which ranks mask_id at -1e6 + its log-probability - on mask_id; u in [V, ldu) and on every id that is neither valid nor mask_id (such an id
+ * scores 0 whatever its u holds; a row whose scores are all 0, t = s = 0, gives id 0). */
 int udm_ddpm_sample_rows(const void* logits, int64_t ld, const int64_t* modality, const float* t, const float* s, const float* u, int64_t ldu,
                          uint64_t seed, int64_t* out, int64_t M, int64_t V, int64_t Vt, int64_t mask_id, int restrict_modality, int greedy,
                          hipStream_t stream);
@@ -296,7 +301,8 @@ int udm_likelihood_scores(const float* log_p, const int64_t* rows, const float* 
 
 /* `maskgit` predictor, per [MASK] row (`_maskgit_update` model_eval.py:3069-3074): x ~ Categorical(exp(SUBS log-probs)) - the exponential race
  * argmax p_i / (1e-10 - log(u_i + 1e-10)), explicit uniforms or Philox(seed) - or x = given[row] (replay of a recorded draw), and out_logp[row] =
- * log p(x).  Guidance (logits_uncond, w) as in udm_ddpm_sample_rows_cfg. */
+ * log p(x).  Guidance (logits_uncond, w) as in udm_ddpm_sample_rows_cfg; the Philox layout and the columns that may hold NaN as in udm_ddpm_sample_rows
+ * (mask_id's logit and u are never looked at here).  A given id that is not valid for its row gives out_logp = -inf. */
 int udm_categorical_sample_rows(const void* logits, const void* logits_uncond, const float* w, int64_t ld, const int64_t* modality, const float* u, int64_t ldu,
                                 uint64_t seed, const int64_t* given, int64_t* out, float* out_logp, int64_t M, int64_t V, int64_t Vt, int64_t mask_id,
                                 int restrict_modality, hipStream_t stream);
@@ -374,7 +380,10 @@ int udm_adamw_step_shadow_ema(float* p, const float* g, float* m, float* v, int6
  *   a second launch combines them); ws NULL or too small: fewer splits.  Every other cache slot is left as it is.
  * udm_ar_sample_rows: the token of position pos for each of the R rows, one launch per step: z = logits (or (1 + *w) logits - *w logits_uncond) in fp32,
  *   [MASK] excluded and, with restrict_modality, the ids of the other modality than modality[r, pos] (ids < Vt are text); y = argmax(z + g) (first index
- *   on ties), g = the explicit Gumbel noise g[r * ldg + g_col0 + id] (replay of a recorded draw) or Philox Gumbel keyed by (seed, step, row, id).  Writes
+ *   on ties), g = the explicit Gumbel noise g[r * ldg + g_col0 + id] (replay of a recorded draw) or Philox Gumbel keyed by (seed, step, row, id):
+ *   Philox4x32-10 with key = seed ^ (step + 1) 0x9E3779B97F4A7C15 (mod 2^64) and counter (row << 40) | (id >> 2); id takes word id & 3 of x y z w,
+ *   u = ((word >> 8) + 0.5) 2^-24 in (0, 1) and g = -log(-log(u)), finite on the whole grid (-2.85 ... 17.33).  Columns a row does not depend on (they may
+ *   hold NaN): logits and logits_uncond in [V, ld), on mask_id and on the other modality's ids; g outside [g_col0, g_col0 + V) and on those same ids.  Writes
  *   x[r, pos] = x0_unmask[r, pos] ? x0[r, pos] : y (x, x0 int64, x0_unmask bool bytes, all [R, ldx]; modality int64 [R, ldm]) and, when next_ids is given,
  *   next_ids[r] = that token and - with guidance - next_ids[R + r] = x0_unmask[r, pos] ? mask_id : that token (the unconditional half's next input). */
 int udm_gemm_skinny_bf16(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc, int out_f32,

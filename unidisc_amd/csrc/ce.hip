@@ -399,7 +399,7 @@ __global__ __launch_bounds__(256) void ddpm_sample_rows_kernel(SampleArgs a) {
         const uint32_t w = (c & 3) == 0 ? r.x : (c & 3) == 1 ? r.y : (c & 3) == 2 ? r.z : r.w;
         uu = (float)(w >> 8) * (1.0f / 16777216.0f);
       }
-      score = q / (1e-10f - __logf(uu + 1e-10f));
+      score = q == 0.f ? 0.f : q / (1e-10f - __logf(uu + 1e-10f));   // (a forbidden id scores 0 whatever its u holds, NaN included)
     }
     if (score > best) { best = score; besti = c; }   // c increases per thread: the first maximum is kept
   }

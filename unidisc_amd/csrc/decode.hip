@@ -274,8 +274,11 @@ struct ArArgs {
 __device__ __forceinline__ bool ar_better(float v, long i, float bv, long bi) { return v > bv || (v == bv && i < bi); }
 
 __device__ __forceinline__ float gumbel_of(uint32_t r) {
-  const float u = ((float)(r >> 8) + 0.5f) * (1.0f / 16777216.0f);   // (0, 1)
-  return -__logf(-__logf(u));
+  // u = ((r >> 8) + 0.5) 2^-24 in (0, 1).  x + 0.5 has 25 bits for x >= 2^23 and fp32 rounds it to an integer (u = 1 and a Gumbel of +inf at the top of the
+  // grid), so the upper half is held as 1 - u = ((2^24 - 1 - x) + 0.5) 2^-24, which is exact, and -log(u) = -log1p(-(1 - u)).
+  const uint32_t x = r >> 8;
+  const float e = x < (1u << 23) ? -__logf(((float)x + 0.5f) * (1.0f / 16777216.0f)) : -log1pf(-(((float)(0xFFFFFFu - x) + 0.5f) * (1.0f / 16777216.0f)));
+  return -__logf(e);
 }
 
 __global__ __launch_bounds__(512) void ar_sample_rows_kernel(ArArgs a) {
