@@ -101,12 +101,15 @@ int udm_small_batch_linear_bwd(const float* dY, int64_t lddy, const void* X, int
 int udm_small_batch_linear_bwd_blocks(int64_t out);
 /* out[C,R] = in[R,C]ᵀ (bf16); optional colsum[c] += Σ_r in[r,c] (bias gradient).  Feeds the wgrad GEMMs. */
 int udm_transpose_bf16(const void* in, void* out, int64_t R, int64_t C, int64_t ld_in, int64_t ld_out, float* colsum, hipStream_t stream);
-/* fp32 master weights -> bf16 shadow (and Kᵀ-major shadow for dgrad): the per-forward autocast weight cast. */
+/* fp32 master weights -> bf16 shadow (and Kᵀ-major shadow for dgrad): the per-forward autocast weight cast.  A leading dimension that allows the vector path
+ * (ld_in % 4 == 0: 16-byte loads; ld_out % 4 == 0: 8-byte stores; ld_t % 8 == 0: 16-byte stores) obliges the base pointer to that alignment: anything else is
+ * refused ("misaligned").  Other leading dimensions take the scalar paths and need no alignment. */
 int udm_cast_transpose_f32_bf16(const float* in, void* out, void* out_t, int64_t R, int64_t C, int64_t ld_in, int64_t ld_out, int64_t ld_t,
                                 hipStream_t stream);
 /* the same for MANY matrices in one launch.  jobs: device array of njobs 64-byte records, sorted by tile0:
  *   { const float* in; bf16* out (or null); bf16* out_t (or null); int64 ld_in, ld_out, ld_t; int32 R, C; int32 tile0, tiles_c }
- * with tiles_c = ceil(C / 64), tile0 = number of 64 x 64 tiles of all earlier records; total_tiles = sum of ceil(R/64) * tiles_c. */
+ * with tiles_c = ceil(C / 64), tile0 = number of 64 x 64 tiles of all earlier records; total_tiles = sum of ceil(R/64) * tiles_c.  The table lives on the
+ * device, so the alignment rule of the single-matrix entry is the duty of whoever fills it (kernels.cast_transpose_jobs checks it). */
 int udm_cast_transpose_multi_f32_bf16(const void* jobs, int64_t njobs, int64_t total_tiles, hipStream_t stream);
 int udm_cast_f32_bf16(const float* x, void* y, int64_t n, float scale, hipStream_t stream); /* DDP bf16 compress hook, main.py:645 */
 int udm_cast_bf16_f32(const void* x, float* y, int64_t n, float scale, hipStream_t stream); /* ... and decompress */
@@ -237,6 +240,8 @@ int udm_attention_fwd_kv(const void* q, const void* k, const void* v, void* o, f
                          hipStream_t stream);
 
 /* ---- embeddings: EmbeddingLayer models/dit.py:1036-1043 (+modality embedding :1402-1411) ------------- */
+/* ids outside [0, V): the forward CLAMPS them (a negative id reads row 0, an id >= V row V - 1); the backward DROPS them from dE and still counts their rows
+ * in dEm (which follows the modality alone).  hot_id: the row most ids hit, summed per block before it is added; outside [0, V) it means "no hot row". */
 int udm_embedding_fwd(const int64_t* ids, const float* E, const int64_t* modality, const float* Em, float* x, int64_t M, int64_t d, int64_t V,
                       hipStream_t stream);
 int udm_embedding_bwd(const int64_t* ids, const int64_t* modality, const float* dx, float* dE, float* dEm, int64_t M, int64_t d, int64_t V, int64_t hot_id,

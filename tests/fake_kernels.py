@@ -317,15 +317,21 @@ def attention_bwd(qkr, qkv, o, do, lse, dqkr, dqkv, B, L, H, D, sample_ids=None,
     dqkr[:, :d], dqkr[:, d:], dqkv[:, 2 * d:] = q.grad.bfloat16(), k.grad.bfloat16(), v.grad.bfloat16()
 
 
-def embedding_fwd(ids, E, modality=None, Em=None):
-    x = E[ids]
+def embedding_fwd(ids, E, modality=None, Em=None, out=None):
+    """ids outside [0, V) are clamped, as the kernel does"""
+    x = E[ids.clamp(0, E.shape[0] - 1)]
     if Em is not None:
         x = x + Em[(modality != 0).long()]
+    if out is not None:
+        out.copy_(x)
+        return out
     return x
 
 
 def embedding_bwd(ids, dx, dE, hot_id, modality=None, dEm=None):
-    dE.index_add_(0, ids, dx)
+    """ids outside [0, V) are dropped from dE and still counted in dEm, as the kernel does; hot_id only orders the kernel's additions"""
+    ok = (ids >= 0) & (ids < dE.shape[0])
+    dE.index_add_(0, ids[ok], dx[ok])
     if dEm is not None:
         dEm.index_add_(0, (modality != 0).long(), dx)
 
@@ -410,18 +416,24 @@ def timestep_embedding(sigma, out, B, dim=256):
     half = dim // 2
     freqs = torch.exp(-math.log(10000) * torch.arange(0, half, dtype=torch.float32) / half)
     args = sigma[:, None].float() * freqs[None]
-    out[:B] = torch.cat([torch.cos(args), torch.sin(args)], -1).bfloat16()
+    out[:B] = torch.cat([torch.cos(args), torch.sin(args), torch.zeros(args.shape[0], dim - 2 * half)], -1).bfloat16()   # an odd dim ends in a zero column
 
 
-def silu_fwd(x, n=None):
-    return F.silu(x.float()).bfloat16()
+def silu_fwd(x, n=None, out=None):
+    y = F.silu(x.float()).bfloat16()
+    if out is None:
+        return y
+    k = x.numel() if n is None else n
+    out.view(-1)[:k] = y.reshape(-1)[:k]
+    return out
 
 
 @torch.enable_grad()
-def silu_bwd(x, dy):
+def silu_bwd(x, dy, out=None):
     xf = x.float().requires_grad_()
     F.silu(xf).backward(dy.float())
-    return xf.grad.bfloat16()
+    g = xf.grad.bfloat16()
+    return g if out is None else out.copy_(g)
 
 
 def subs_logprobs(logits, xt, modality, V, Vt, mask_id, restrict, out_dtype=BF16):

@@ -1159,6 +1159,10 @@ extern "C" int udm_cast_transpose_f32_bf16(const float* in, void* out, void* out
                                            hipStream_t stream) {
   UDM_CHECK_ARG(in && (out || out_t), "udm_cast_transpose_f32_bf16: null pointer");
   UDM_CHECK_ARG(R > 0 && C > 0, "udm_cast_transpose_f32_bf16: empty");
+  // the leading dimensions select the 16-byte loads / 8-byte row stores / 16-byte transposed stores of cast_transpose_tile: the bases must allow them
+  UDM_CHECK_ARG((ld_in % 4 != 0 || (uintptr_t)in % 16 == 0) && (!out || ld_out % 4 != 0 || (uintptr_t)out % 8 == 0) &&
+                    (!out_t || ld_t % 8 != 0 || (uintptr_t)out_t % 16 == 0),
+                "udm_cast_transpose_f32_bf16: misaligned");
   dim3 grid((unsigned)((C + TT - 1) / TT), (unsigned)((R + TT - 1) / TT));
   hipLaunchKernelGGL(cast_transpose_kernel, grid, dim3(256), 0, stream, in, (bf16_t*)out, (bf16_t*)out_t, (int)R, (int)C, (long)ld_in, (long)ld_out, (long)ld_t);
   UDM_CHECK_LAUNCH("udm_cast_transpose_f32_bf16");

@@ -850,6 +850,8 @@ __global__ __launch_bounds__(256) void embedding_fwd_kernel(const int64_t* __res
 // before the first is used; the kernel is bound by its same-address atomics - the [MASK] row and the two modality rows - not by the reads).  Rows whose id is
 // `hot_id` (the [MASK] token: about half of all rows under the absorbing schedule) are summed in registers and leave the block as ONE atomic per column; other
 // rows scatter with atomics directly.
+// Contract on ids: an id outside [0, V) contributes nothing to dE (the forward CLAMPS such an id to row 0 / V - 1, the backward DROPS it) but still counts in
+// dEm, which depends on the modality alone.  A hot_id outside [0, V) means "no hot row": nothing is collected into `hot` and nothing is stored for it.
 __global__ __launch_bounds__(256) void embedding_bwd_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ modality, const float* __restrict__ dx,
                                                            float* __restrict__ dE, float* __restrict__ dEm, long M, int d, long V, long hot_id,
                                                            int rows_per_block) {
@@ -857,6 +859,7 @@ __global__ __launch_bounds__(256) void embedding_bwd_kernel(const int64_t* __res
   const long r1 = min(M, r0 + rows_per_block);
   const int c = blockIdx.y * 1024 + threadIdx.x * 4;
   if (c >= d) return;
+  const bool has_hot = hot_id >= 0 && hot_id < V;
   float hot[4] = {0.f, 0.f, 0.f, 0.f}, m0[4] = {0.f, 0.f, 0.f, 0.f}, m1[4] = {0.f, 0.f, 0.f, 0.f};
   constexpr int RU = 8;
   for (long rb = r0; rb < r1; rb += RU) {
@@ -869,7 +872,7 @@ __global__ __launch_bounds__(256) void embedding_bwd_kernel(const int64_t* __res
       if (rb + u >= r1) break;
       const long id = ids[rb + u];
       const float gv[4] = {g[u].x, g[u].y, g[u].z, g[u].w};
-      if (id == hot_id) {
+      if (has_hot && id == hot_id) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) hot[e] += gv[e];
       } else if (id >= 0 && id < V) {
@@ -885,7 +888,7 @@ __global__ __launch_bounds__(256) void embedding_bwd_kernel(const int64_t* __res
   }
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    if (hot[e] != 0.f) atomicAdd(dE + hot_id * d + c + e, hot[e]);
+    if (has_hot && hot[e] != 0.f) atomicAdd(dE + hot_id * d + c + e, hot[e]);
     if (dEm) { atomicAdd(dEm + c + e, m0[e]); atomicAdd(dEm + d + c + e, m1[e]); }
   }
 }
@@ -913,14 +916,25 @@ __global__ void silu_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float v = bf2f(x[i]);
-  y[i] = f2bf(v / (1.f + __expf(-v)));
+  // below -80, 1 + e^-v == e^-v in fp32 and e^-v soon leaves the fp32 range (v / inf = -0) while v e^v is a normal bf16 down to v = -96: e^v as (e^(v/2))^2
+  float r;
+  if (v < -80.f) {
+    const float h = __expf(0.5f * v);
+    r = (v * h) * h;
+  } else {
+    r = v / (1.f + __expf(-v));
+  }
+  y[i] = f2bf(r);
 }
 __global__ void silu_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy, bf16_t* __restrict__ dx, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float v = bf2f(x[i]);
-  const float s = 1.f / (1.f + __expf(-v));
-  dx[i] = f2bf(bf2f(dy[i]) * (s + v * s * (1.f - s)));
+  const float e = __expf(-v);
+  const float s = 1.f / (1.f + e);
+  // 1 - s without cancellation: above 16.6, 1 + e rounds to 1 and `1 - s` loses the whole x s (1 - s) term (16 fp32 ulps of the result); e may be inf below 0
+  const float c = v > 0.f ? e * s : 1.f - s;
+  dx[i] = f2bf(bf2f(dy[i]) * (s + v * s * c));
 }
 __global__ void cast_f32_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, long n) {
   const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;

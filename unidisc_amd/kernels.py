@@ -523,6 +523,11 @@ def cast_transpose_jobs(items, device):
     for w, out, out_t in items:
         _chk(w, F32, "cast_transpose_jobs")
         R, C = w.shape
+        # the kernel picks its 16-byte loads / 8-byte row stores / 16-byte transposed stores from the leading dimensions: the bases must allow them (the table lives
+        # on the device, so the entry point cannot look)
+        if ((w.stride(0) % 4 == 0 and _p(w) % 16) or (out is not None and out.stride(0) % 4 == 0 and _p(out) % 8)
+                or (out_t is not None and out_t.stride(0) % 8 == 0 and _p(out_t) % 16)):
+            raise RuntimeError("cast_transpose_jobs: misaligned (w 16-byte, out 8-byte, out_t 16-byte aligned wherever its leading dimension selects the vector path)")
         tiles_c = (C + 63) // 64
         buf += struct.pack("<QQQqqqiiii", _p(w), _p(out) or 0, _p(out_t) or 0, w.stride(0), out.stride(0) if out is not None else 0,
                            out_t.stride(0) if out_t is not None else 0, R, C, tile0, tiles_c)
@@ -885,6 +890,8 @@ def set_attention_dkv64(enable):
 
 # ------------------------------------------------------------------------------------------------ embedding / CE / adaLN helpers
 def embedding_fwd(ids, E, modality=None, Em=None, out=None):
+    """x[r] = E[ids[r]] (+ Em[0] on text rows, modality 0; Em[1] on every other modality value), fp32 [M, d]; `out`: written in place of a new tensor.
+    An id outside [0, V) is CLAMPED: a negative id reads row 0, an id >= V row V - 1 (`embedding_bwd` drops such rows)."""
     M = ids.numel()
     V, d = E.shape
     x = torch.empty((M, d), dtype=F32, device=E.device) if out is None else out
@@ -893,6 +900,9 @@ def embedding_fwd(ids, E, modality=None, Em=None, out=None):
 
 
 def embedding_bwd(ids, dx, dE, hot_id, modality=None, dEm=None):
+    """dE[ids[r]] += dx[r]; dEm[0] += the text rows of dx (modality 0), dEm[1] += every other row.  A row whose id is outside [0, V) is DROPPED from dE (the
+    forward clamps it, so the clamped row gets no gradient) but still counts in dEm.  `hot_id` names the row most ids hit (the [MASK] token), summed per block
+    before it is added; a hot_id outside [0, V) means "no hot row" - it changes the order of the additions, never the result."""
     M = ids.numel()
     V, d = dE.shape
     _lib.call("udm_embedding_bwd", _p(ids), _p(modality), _p(dx), _p(dE), _p(dEm), M, d, V, hot_id, _s())
@@ -977,14 +987,16 @@ def timestep_embedding(sigma, out, B, dim=256):
     _lib.call("udm_timestep_embedding", _p(sigma), _p(out), B, dim, _s())
 
 
-def silu_fwd(x, n=None):
-    y = torch.empty_like(x)
+def silu_fwd(x, n=None, out=None):
+    """y = x sigmoid(x) (bf16) of the first n elements (default: all); `out`: written in place of a new tensor, its elements past n are left alone."""
+    y = torch.empty_like(x) if out is None else out
     _lib.call("udm_silu_fwd", _p(x), _p(y), x.numel() if n is None else n, _s())
     return y
 
 
-def silu_bwd(x, dy):
-    dx = torch.empty_like(x)
+def silu_bwd(x, dy, out=None):
+    """dx = dy (s + x s (1 - s)), s = sigmoid(x) (bf16); `out`: written in place of a new tensor."""
+    dx = torch.empty_like(x) if out is None else out
     _lib.call("udm_silu_bwd", _p(x), _p(dy), _p(dx), x.numel(), _s())
     return dx
 
