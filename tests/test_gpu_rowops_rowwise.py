@@ -8,26 +8,9 @@ accumulated outputs (dx with accumulate = True, every column sum) start from a r
 every call; after it, everything outside the outputs is compared bit for bit.  (d branch of residual_bwd is allocated by the wrapper itself.)
 The backward kernels take the statistics the forward kernels saved (checked against the reference first); the backward reference takes the same fp32 values.
 
-Which parametrisation reaches which branch of the dispatchers (grid_rows caps at 2048 blocks of 4 rows):
-  widths 64 .. 4096              NCH = 1, 2 (520: partial chunk), 2 (768), 3 (1032: partial), 4 (2048), 8 (3072: partial, 4096) of every wave-per-row template;
-                                 udm_residual_bwd: generic (d < 2048), the wave-per-row d = 2048 form, block-per-row <2> (3072, 4096);
-                                 udm_qknorm_rope_*: NIT = 1 .. 4 (d < 2048), the two-rows-per-iteration forward (2048), block-per-row <2> (3072, 4096), <1> backward (2048)
-  B, L = 5, 37                   modulated / gated blocks own ragged row chunks of one batch element (DISPATCH_NCH_MOD, bpb = 10), M % 4 != 0, odd M at d = 2048
-  M = 1, 3, 37                   waves without a row; the ragged two-row group of qknorm_rope_fwd_brow_rows_kernel<2>
-  B, L = 2, 700                  more rows than blocks in the modulated / gated forms (bpb = 175 blocks x 4 rows); udm_qknorm_rope_bwd's workspace form (M >= 253)
-  M = 2048 (d = 768)             udm_norm_bwd: the first M with a workspace and the two-phase colreduce_kernel (grid 512 >= 64)
-  M = 8200 (d = 64)              past the 2048-block cap of udm_norm_fwd / udm_residual_fwd, the 1024-block cap of udm_norm_bwd, the 512-block cap of udm_residual_bwd
-  B, L = 2, 4100 (d = 64)        the modulated udm_norm_bwd with a workspace (grid = 2 x 512)
-  B, L = 2, 2050 (d = 64)        M = 4100: past the 1024-block cap of the narrow qk-norm forward, of the workspace form of its backward and the 256-block cap of its
-                                 atomics form
-  M = 4093 (d = 768, sandwich)   udm_residual_bwd's wide-grid workspace form (grid_rows(M) = 1024)
-  M = 2051 (d = 2048)            past the 1024-group cap of the two-row qk-norm forward with a ragged last group, the 1024-block caps of residual_bwd_kernel<4> and
-                                 qknorm_rope_bwd_brow_kernel<1>, the 512-block cap of udm_norm_bwd
-  M = 2050 (d = 4096)            past the 2048-block cap of qknorm_rope_fwd_brow_kernel<2>, the 1536-block cap of residual_bwd_brow_kernel<2>, 1024 of the qk backward
-  qk backward                    the four affine gradients in one allocation (workspace form) and in four tensors (atomics form)
-  fused norm + residual backward udm_norm_residual_bwd on every width (wave per row below 2048, block per row at 2048 / 4096), M = 4100 (d = 64) and M = 1000
-                                 (d = 2048, 4096) past its 1024- and 768-block grids; udm_norm_residual_bwd_ada at 2048 / 4096, one block per row (5 x 37) and
-                                 more rows than blocks (2 x 700)
+Which parametrisation reaches which kernel, instance and grid is asserted on the CPU by tests/test_rowops_plan.py, which lists every call made here with the plan
+csrc/rowops_plan.h gives it (B, L = 5, 37: ragged row chunks of one batch element and M % 4 != 0; M = 1, 3, 37: waves without a row and the ragged two-row group;
+B, L = 2, 700: more rows than blocks; the other row counts: the first M past each grid cap and each workspace gate).
 At M > 1024 the per-row outputs of the forward kernels are compared on a row sample (first, last, both sides of every grid seam); the backward reference runs
 over all rows in chunks of 512 (the column sums need every row), so the per-row outputs of the backward kernels are compared on every row.
 """

@@ -7,13 +7,13 @@
 // (bias_dropout_add_scale), :263-304 (modulate_fused), :680-682 (qk LayerNorm), models/standalone_rotary.py:14-31
 // (rotary), :1036-1043 + :1402-1411 (embedding + modality embedding), :415-449 (timestep embedding).
 #include "common.h"
+#include "rowops_plan.h"
 #include <stdlib.h>
+#include <type_traits>
 #include "../../include/unidisc_hip.h"
 
 namespace {
 using namespace udm;
-
-constexpr int ROWS_PER_BLOCK = 4;  // 256 threads = 4 waves = 4 rows in flight per block
 
 __device__ __forceinline__ void load8_f32(const float* p, float (&v)[8]) {
   float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
@@ -1803,32 +1803,48 @@ __global__ __launch_bounds__(256) void qknorm_rope_bwd_brow_kernel(QkBwdArgs a) 
   }
 }
 
-inline int grid_rows(long M) {
-  long g = (M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-  return (int)(g < 2048 ? (g < 1 ? 1 : g) : 2048);
-}
-inline int nch_for(long d) { return (int)((d + 511) / 512); }
-// template instance of the wave-per-row kernels: NCH chunks of 512 columns; 2048 < d <= 4096 runs the 8-chunk instance, a wider row has none (0: DISPATCH_NCH refuses)
-inline int nch_dispatch(long d) { const int n = nch_for(d); return n <= 4 ? n : (d <= 4096 ? 8 : 0); }
+// plan.inst -> the instantiation: f(std::integral_constant<int, N>{}) for the N of the list that plan.inst names; false when the list has no such instance
+template <int... Ns, typename F>
+bool with_inst(int inst, F&& f) { return ((inst == Ns && (f(std::integral_constant<int, Ns>{}), true)) || ...); }
 
-#define DISPATCH_NCH_MOD(nch, KERNEL, grid, stream, args)                                            \
-  switch (nch) {                                                                                     \
-    case 1: hipLaunchKernelGGL((KERNEL<1, true>), dim3(grid), dim3(256), 0, stream, args); break;   \
-    case 2: hipLaunchKernelGGL((KERNEL<2, true>), dim3(grid), dim3(256), 0, stream, args); break;   \
-    case 3: hipLaunchKernelGGL((KERNEL<3, true>), dim3(grid), dim3(256), 0, stream, args); break;   \
-    case 4: hipLaunchKernelGGL((KERNEL<4, true>), dim3(grid), dim3(256), 0, stream, args); break;   \
-    case 8: hipLaunchKernelGGL((KERNEL<8, true>), dim3(grid), dim3(256), 0, stream, args); break;   \
-    default: udm_set_error(#KERNEL ": unsupported hidden size (d <= 2048 or d == 4096, d %% 8 == 0)"); return 2; \
-  }
-#define DISPATCH_NCH(nch, KERNEL, grid, stream, args)                                          \
-  switch (nch) {                                                                               \
-    case 1: hipLaunchKernelGGL((KERNEL<1>), dim3(grid), dim3(256), 0, stream, args); break;   \
-    case 2: hipLaunchKernelGGL((KERNEL<2>), dim3(grid), dim3(256), 0, stream, args); break;   \
-    case 3: hipLaunchKernelGGL((KERNEL<3>), dim3(grid), dim3(256), 0, stream, args); break;   \
-    case 4: hipLaunchKernelGGL((KERNEL<4>), dim3(grid), dim3(256), 0, stream, args); break;   \
-    case 8: hipLaunchKernelGGL((KERNEL<8>), dim3(grid), dim3(256), 0, stream, args); break;   \
-    default: udm_set_error(#KERNEL ": unsupported hidden size (d <= 2048 or d == 4096, d %% 8 == 0)"); return 2; \
-  }
+template <typename A>
+void launch_rows(void (*kernel)(A), const RowPlan& p, hipStream_t stream, const A& a) { hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(256), p.lds_bytes, stream, a); }
+
+int unsupported_width(const char* kernel) { udm_set_error("%s: unsupported hidden size (d <= 2048 or d == 4096, d %% 8 == 0)", kernel); return 2; }
+
+// the tail of every backward entry point: the launch check of the row kernel (`launched` names it), then - for a plan with a workspace - the column sums of the
+// partial rows the blocks left there: one plane into out0 (colreduce_kernel), or planes = 3 into out0 | out1 | out2 (colreduce3_kernel; a null output is skipped)
+int reduce_rows(const char* launched, const char* reduced, const RowPlan& p, hipStream_t stream, const float* ws, float* out0, int planes = 1, float* out1 = nullptr,
+                float* out2 = nullptr) {
+  UDM_CHECK_LAUNCH(launched);
+  if (!p.use_ws) return 0;
+  const dim3 grid((p.reduce_cols + 63) / 64, 16, planes);
+  if (planes == 3) hipLaunchKernelGGL(colreduce3_kernel, grid, dim3(256), 0, stream, ws, out0, out1, out2, (int)p.reduce_rows, (int)p.reduce_cols);
+  else hipLaunchKernelGGL(colreduce_kernel, grid, dim3(256), 0, stream, ws, out0, (int)p.reduce_rows, (int)p.reduce_cols);
+  UDM_CHECK_LAUNCH(reduced);
+  return 0;
+}
+
+// udm_residual_fwd (w_next == nullptr), udm_residual_norm_fwd (the next pre-norm fused) and udm_residual_norm_fwd_ada (that norm modulated: ada)
+int residual_fwd(const char* name, bool next, bool ada, const float* x_in, const void* branch, float* x_out, const float* w_b, float* rstd_b, float* mean_b,
+                 const void* gate, int64_t mod_stride, const int64_t* modality, int64_t M, int64_t d, int64_t L, int norm_type, float eps, float p_drop, uint64_t seed,
+                 const float* w_next, void* h_out, float* rstd_next, float* mean_next, const void* next_shift, const void* next_scale, int64_t next_mod_stride,
+                 const int64_t* next_modality, const int* next_any_img, hipStream_t stream) {
+  UDM_CHECK_ARG(x_in && branch && x_out && (!next || (w_next && h_out && rstd_next)) && (!ada || (next_shift && next_scale)), "%s: null pointer", name);
+  UDM_CHECK_ARG(M > 0 && d > 0 && d % 8 == 0 && L > 0, "%s: bad shape", name);
+  UDM_CHECK_ARG(!w_b || rstd_b, "%s: sandwich norm needs rstd buffer", name);
+  UDM_CHECK_ARG(!(w_b && norm_type) || mean_b, "%s: sandwich LayerNorm needs mean buffer", name);
+  UDM_CHECK_ARG(!next || !norm_type || mean_next, "%s: LayerNorm needs mean_next", name);
+  UDM_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "%s: dropout p out of range", name);
+  ResidArgs a{x_in, (const bf16_t*)branch, x_out, w_b, rstd_b, (w_b && norm_type) ? mean_b : nullptr, (const bf16_t*)gate, modality, (long)mod_stride,
+              (int)M, (int)d, (int)L, norm_type, eps, p_drop, seed, w_next, (bf16_t*)h_out, rstd_next, norm_type ? mean_next : nullptr};
+  a.n_shift = (const bf16_t*)next_shift; a.n_scale = (const bf16_t*)next_scale; a.n_mod_stride = (long)next_mod_stride; a.n_modality = next_modality;
+  a.n_any_img = next_any_img;
+  const RowPlan plan = row_plan_fwd(M, d);
+  if (!with_inst<1, 2, 3, 4, 8>(plan.inst, [&](auto n) { launch_rows(residual_fwd_kernel<decltype(n)::value>, plan, stream, a); })) return unsupported_width("residual_fwd_kernel");
+  UDM_CHECK_LAUNCH(name);
+  return 0;
+}
 }  // namespace
 
 extern "C" int udm_norm_fwd(const float* x, void* y, float* rstd, float* mean, const float* w, const void* shift, const void* scale, int64_t mod_stride,
@@ -1839,8 +1855,8 @@ extern "C" int udm_norm_fwd(const float* x, void* y, float* rstd, float* mean, c
   UDM_CHECK_ARG((shift == nullptr) == (scale == nullptr), "udm_norm_fwd: shift and scale go together");
   NormArgs a{x, (bf16_t*)y, rstd, norm_type ? mean : nullptr, w, (const bf16_t*)shift, (const bf16_t*)scale, modality, any_img, (long)mod_stride,
              (int)M, (int)d, (int)L, norm_type, eps};
-  const int nch = nch_dispatch(d);
-  DISPATCH_NCH(nch, norm_fwd_kernel, grid_rows(M), stream, a);
+  const RowPlan plan = row_plan_fwd(M, d);
+  if (!with_inst<1, 2, 3, 4, 8>(plan.inst, [&](auto n) { launch_rows(norm_fwd_kernel<decltype(n)::value>, plan, stream, a); })) return unsupported_width("norm_fwd_kernel");
   UDM_CHECK_LAUNCH("udm_norm_fwd");
   return 0;
 }
@@ -1851,26 +1867,14 @@ extern "C" int udm_norm_bwd(const void* dy, const float* x, const float* rstd, c
   UDM_CHECK_ARG(dy && x && rstd && w && dx && dw, "udm_norm_bwd: null pointer");
   UDM_CHECK_ARG(M > 0 && d > 0 && d % 8 == 0 && L > 0, "udm_norm_bwd: bad shape");
   UDM_CHECK_ARG(!shift || (scale && dshift && dscale), "udm_norm_bwd: modulated norm needs scale, dshift, dscale");
+  UDM_CHECK_ARG(!shift || M % L == 0, "udm_norm_bwd: modulated norm needs M = B * L");
+  const RowPlan plan = row_plan_norm_bwd(M, d, L, shift != nullptr, ws ? ws_elems : 0);
   NormBwdArgs a{(const bf16_t*)dy, x, rstd, mean, w, (const bf16_t*)shift, (const bf16_t*)scale, modality, any_img, dx, dw, dshift, dscale,
-                (long)mod_stride, (int)M, (int)d, (int)L, norm_type, accumulate, nullptr, 0};
-  const int nch = nch_dispatch(d);
-  int grid = min(grid_rows(M), d < 2048 ? 1024 : 512);   // (measured: 48.6 vs 51.6 us at d = 768 with 1024 blocks, 60.7 vs 57.9 us at d = 2048)
-  if (shift) {   // modulated: whole blocks per batch element (M = B L)
-    UDM_CHECK_ARG(M % L == 0, "udm_norm_bwd: modulated norm needs M = B * L");
-    const int B = (int)(M / L);
-    a.bpb = max(1, min(grid / B, (int)((L + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)));
-    grid = B * a.bpb;
-  }
-  if (ws && ws_elems >= (int64_t)grid * d && grid >= 64) a.ws = ws;   // short chains (few blocks) stay on atomics
-  else if (!shift) grid = min(grid, 512);
-  if (shift) { DISPATCH_NCH_MOD(nch, norm_bwd_kernel, grid, stream, a); }
-  else { DISPATCH_NCH(nch, norm_bwd_kernel, grid, stream, a); }
-  UDM_CHECK_LAUNCH("udm_norm_bwd");
-  if (a.ws) {
-    hipLaunchKernelGGL(colreduce_kernel, dim3((unsigned)((d + 63) / 64), 16), dim3(256), 0, stream, (const float*)ws, dw, grid, (int)d);
-    UDM_CHECK_LAUNCH("udm_norm_bwd(colreduce)");
-  }
-  return 0;
+                (long)mod_stride, (int)M, (int)d, (int)L, norm_type, accumulate, plan.use_ws ? ws : nullptr, plan.bpb};
+  const bool ok = shift ? with_inst<1, 2, 3, 4, 8>(plan.inst, [&](auto n) { launch_rows(norm_bwd_kernel<decltype(n)::value, true>, plan, stream, a); })
+                        : with_inst<1, 2, 3, 4, 8>(plan.inst, [&](auto n) { launch_rows(norm_bwd_kernel<decltype(n)::value>, plan, stream, a); });
+  if (!ok) return unsupported_width("norm_bwd_kernel");
+  return reduce_rows("udm_norm_bwd", "udm_norm_bwd(colreduce)", plan, stream, ws, dw);
 }
 
 // residual add + the next pre-norm WITH adaLN modulation in one pass (time_conditioning = True)
@@ -1878,53 +1882,22 @@ extern "C" int udm_residual_norm_fwd_ada(const float* x_in, const void* branch, 
                                          int64_t mod_stride, const int64_t* modality, int64_t M, int64_t d, int64_t L, int norm_type, float eps, float p_drop,
                                          uint64_t seed, const float* w_next, void* h_out, float* rstd_next, float* mean_next, const void* next_shift,
                                          const void* next_scale, int64_t next_mod_stride, const int64_t* next_modality, const int* next_any_img, hipStream_t stream) {
-  UDM_CHECK_ARG(x_in && branch && x_out && w_next && h_out && rstd_next && next_shift && next_scale, "udm_residual_norm_fwd_ada: null pointer");
-  UDM_CHECK_ARG(M > 0 && d > 0 && d % 8 == 0 && L > 0, "udm_residual_norm_fwd_ada: bad shape");
-  UDM_CHECK_ARG(!w_b || rstd_b, "udm_residual_norm_fwd_ada: sandwich norm needs rstd buffer");
-  UDM_CHECK_ARG(!(w_b && norm_type) || mean_b, "udm_residual_norm_fwd_ada: sandwich LayerNorm needs mean buffer");
-  UDM_CHECK_ARG(!norm_type || mean_next, "udm_residual_norm_fwd_ada: LayerNorm needs mean_next");
-  UDM_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "udm_residual_norm_fwd_ada: dropout p out of range");
-  ResidArgs a{x_in, (const bf16_t*)branch, x_out, w_b, rstd_b, (w_b && norm_type) ? mean_b : nullptr, (const bf16_t*)gate, modality, (long)mod_stride,
-              (int)M, (int)d, (int)L, norm_type, eps, p_drop, seed, w_next, (bf16_t*)h_out, rstd_next, norm_type ? mean_next : nullptr};
-  a.n_shift = (const bf16_t*)next_shift; a.n_scale = (const bf16_t*)next_scale; a.n_mod_stride = (long)next_mod_stride; a.n_modality = next_modality;
-  a.n_any_img = next_any_img;
-  const int nch = nch_dispatch(d);
-  DISPATCH_NCH(nch, residual_fwd_kernel, grid_rows(M), stream, a);
-  UDM_CHECK_LAUNCH("udm_residual_norm_fwd_ada");
-  return 0;
+  return residual_fwd("udm_residual_norm_fwd_ada", true, true, x_in, branch, x_out, w_b, rstd_b, mean_b, gate, mod_stride, modality, M, d, L, norm_type, eps, p_drop, seed,
+                      w_next, h_out, rstd_next, mean_next, next_shift, next_scale, next_mod_stride, next_modality, next_any_img, stream);
 }
 
 extern "C" int udm_residual_fwd(const float* x_in, const void* branch, float* x_out, const float* w_b, float* rstd_b, float* mean_b, const void* gate,
                                 int64_t mod_stride, const int64_t* modality, int64_t M, int64_t d, int64_t L, int norm_type, float eps, float p_drop,
                                 uint64_t seed, hipStream_t stream) {
-  UDM_CHECK_ARG(x_in && branch && x_out, "udm_residual_fwd: null pointer");
-  UDM_CHECK_ARG(M > 0 && d > 0 && d % 8 == 0 && L > 0, "udm_residual_fwd: bad shape");
-  UDM_CHECK_ARG(!w_b || rstd_b, "udm_residual_fwd: sandwich norm needs rstd buffer");
-  UDM_CHECK_ARG(!(w_b && norm_type) || mean_b, "udm_residual_fwd: sandwich LayerNorm needs mean buffer");
-  UDM_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "udm_residual_fwd: dropout p out of range");
-  ResidArgs a{x_in, (const bf16_t*)branch, x_out, w_b, rstd_b, (w_b && norm_type) ? mean_b : nullptr, (const bf16_t*)gate, modality, (long)mod_stride,
-              (int)M, (int)d, (int)L, norm_type, eps, p_drop, seed, nullptr, nullptr, nullptr, nullptr};
-  const int nch = nch_dispatch(d);
-  DISPATCH_NCH(nch, residual_fwd_kernel, grid_rows(M), stream, a);
-  UDM_CHECK_LAUNCH("udm_residual_fwd");
-  return 0;
+  return residual_fwd("udm_residual_fwd", false, false, x_in, branch, x_out, w_b, rstd_b, mean_b, gate, mod_stride, modality, M, d, L, norm_type, eps, p_drop, seed,
+                      nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, stream);
 }
 
 extern "C" int udm_residual_norm_fwd(const float* x_in, const void* branch, float* x_out, const float* w_b, float* rstd_b, float* mean_b, const void* gate,
                                      int64_t mod_stride, const int64_t* modality, int64_t M, int64_t d, int64_t L, int norm_type, float eps, float p_drop,
                                      uint64_t seed, const float* w_next, void* h_out, float* rstd_next, float* mean_next, hipStream_t stream) {
-  UDM_CHECK_ARG(x_in && branch && x_out && w_next && h_out && rstd_next, "udm_residual_norm_fwd: null pointer");
-  UDM_CHECK_ARG(M > 0 && d > 0 && d % 8 == 0 && L > 0, "udm_residual_norm_fwd: bad shape");
-  UDM_CHECK_ARG(!w_b || rstd_b, "udm_residual_norm_fwd: sandwich norm needs rstd buffer");
-  UDM_CHECK_ARG(!(w_b && norm_type) || mean_b, "udm_residual_norm_fwd: sandwich LayerNorm needs mean buffer");
-  UDM_CHECK_ARG(!norm_type || mean_next, "udm_residual_norm_fwd: LayerNorm needs mean_next");
-  UDM_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "udm_residual_norm_fwd: dropout p out of range");
-  ResidArgs a{x_in, (const bf16_t*)branch, x_out, w_b, rstd_b, (w_b && norm_type) ? mean_b : nullptr, (const bf16_t*)gate, modality, (long)mod_stride,
-              (int)M, (int)d, (int)L, norm_type, eps, p_drop, seed, w_next, (bf16_t*)h_out, rstd_next, norm_type ? mean_next : nullptr};
-  const int nch = nch_dispatch(d);
-  DISPATCH_NCH(nch, residual_fwd_kernel, grid_rows(M), stream, a);
-  UDM_CHECK_LAUNCH("udm_residual_norm_fwd");
-  return 0;
+  return residual_fwd("udm_residual_norm_fwd", true, false, x_in, branch, x_out, w_b, rstd_b, mean_b, gate, mod_stride, modality, M, d, L, norm_type, eps, p_drop, seed,
+                      w_next, h_out, rstd_next, mean_next, nullptr, nullptr, 0, nullptr, nullptr, stream);
 }
 
 extern "C" int udm_residual_bwd(const float* dx, const void* branch, void* dbranch, const float* w_b, const float* rstd_b, const float* mean_b,
@@ -1934,86 +1907,32 @@ extern "C" int udm_residual_bwd(const float* dx, const void* branch, void* dbran
   UDM_CHECK_ARG(M > 0 && d > 0 && d % 8 == 0 && L > 0, "udm_residual_bwd: bad shape");
   UDM_CHECK_ARG(!w_b || (rstd_b && dw_b), "udm_residual_bwd: sandwich norm needs rstd and dw");
   UDM_CHECK_ARG(!gate || dgate, "udm_residual_bwd: gate needs dgate");
-  ResidBwdArgs a{dx, (const bf16_t*)branch, (bf16_t*)dbranch, w_b, rstd_b, mean_b, (const bf16_t*)gate, modality, dw_b, nullptr, dgate, (long)mod_stride,
-                 (int)M, (int)d, (int)L, norm_type, p_drop, seed, 0};
-  if (gate) {   // gated (adaLN-Zero): whole blocks per batch element, the gate gradient's column sums in registers
-    UDM_CHECK_ARG(M % L == 0, "udm_residual_bwd: a gate needs M = B * L");
-    const int B = (int)(M / L);
-    const int nch = nch_dispatch(d);
-    a.bpb = max(1, min(1024 / B, (int)((L + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)));
-    const int grid = B * a.bpb;
-    if (w_b && ws && ws_elems >= (int64_t)grid * d && grid >= 64) a.ws = ws;
-    DISPATCH_NCH_MOD(nch, residual_bwd_kernel, grid, stream, a);
-    UDM_CHECK_LAUNCH("udm_residual_bwd(gated)");
-    if (a.ws) {
-      hipLaunchKernelGGL(colreduce_kernel, dim3((unsigned)((d + 63) / 64), 16), dim3(256), 0, stream, (const float*)ws, dw_b, grid, (int)d);
-      UDM_CHECK_LAUNCH("udm_residual_bwd(colreduce)");
-    }
-    return 0;
-  }
-  if (d == 2048 && (!w_b || (ws && ws_elems >= (int64_t)1024 * d))) {
-    // d = 2048 still fits a wave per row (32 values per lane): no block-wide reductions; measured 41.8 us vs 52.9 us for the
-    // block-per-row form without dropout, equal with dropout (Philox regeneration dominates there)
-    const int grid = 1024;
-    a.ws = w_b ? ws : nullptr;
-    hipLaunchKernelGGL((residual_bwd_kernel<4>), dim3(grid), dim3(256), 0, stream, a);
-    UDM_CHECK_LAUNCH("udm_residual_bwd");
-    if (a.ws) hipLaunchKernelGGL(colreduce_kernel, dim3((unsigned)((d + 63) / 64), 16), dim3(256), 0, stream, (const float*)ws, dw_b, grid, (int)d);
-    return 0;
-  }
-  if (d >= 2048 && d <= 4096) {  // wide rows: block-per-row form (8 elements per thread, high occupancy)
-    int g = (int)(M < 1536 ? M : 1536);
-    if (w_b && ws && ws_elems >= (int64_t)g * d) a.ws = ws;
-    else if (w_b) g = g < 256 ? g : 256;  // no workspace: keep the same-address atomic chains short
-    if (d <= 2048) hipLaunchKernelGGL((residual_bwd_brow_kernel<1>), dim3(g), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((residual_bwd_brow_kernel<2>), dim3(g), dim3(256), 0, stream, a);
-    UDM_CHECK_LAUNCH("udm_residual_bwd");
-    if (a.ws) {
-      hipLaunchKernelGGL(colreduce_kernel, dim3((unsigned)((d + 63) / 64), 16), dim3(256), 0, stream, (const float*)ws, dw_b, g, (int)d);
-      UDM_CHECK_LAUNCH("udm_residual_bwd(colreduce)");
-    }
-    return 0;
-  }
-  const int nch = nch_dispatch(d);
-  int grid = min(grid_rows(M), 512);
-  if (w_b && ws && grid_rows(M) >= 1024 && ws_elems >= (int64_t)1024 * d) { grid = 1024; a.ws = ws; }   // wide grid, column sums through the workspace
-  DISPATCH_NCH(nch, residual_bwd_kernel, grid, stream, a);
-  UDM_CHECK_LAUNCH("udm_residual_bwd");
-  if (a.ws) {
-    hipLaunchKernelGGL(colreduce_kernel, dim3((unsigned)((d + 63) / 64), 16), dim3(256), 0, stream, (const float*)ws, dw_b, grid, (int)d);
-    UDM_CHECK_LAUNCH("udm_residual_bwd(colreduce)");
-  }
-  return 0;
+  UDM_CHECK_ARG(!gate || M % L == 0, "udm_residual_bwd: a gate needs M = B * L");
+  const RowPlan plan = row_plan_residual_bwd(M, d, L, gate != nullptr, w_b != nullptr, ws ? ws_elems : 0);
+  ResidBwdArgs a{dx, (const bf16_t*)branch, (bf16_t*)dbranch, w_b, rstd_b, mean_b, (const bf16_t*)gate, modality, dw_b, plan.use_ws ? ws : nullptr, dgate,
+                 (long)mod_stride, (int)M, (int)d, (int)L, norm_type, p_drop, seed, plan.bpb};
+  bool ok;   // gated (adaLN-Zero): the gate gradient's column sums in registers
+  if (gate) ok = with_inst<1, 2, 3, 4, 8>(plan.inst, [&](auto n) { launch_rows(residual_bwd_kernel<decltype(n)::value, true>, plan, stream, a); });
+  else if (plan.form == BLOCK_ROW) ok = with_inst<1, 2>(plan.inst, [&](auto n) { launch_rows(residual_bwd_brow_kernel<decltype(n)::value>, plan, stream, a); });
+  else ok = with_inst<1, 2, 3, 4>(plan.inst, [&](auto n) { launch_rows(residual_bwd_kernel<decltype(n)::value>, plan, stream, a); });
+  if (!ok) return unsupported_width("residual_bwd_kernel");
+  return reduce_rows(gate ? "udm_residual_bwd(gated)" : "udm_residual_bwd", "udm_residual_bwd(colreduce)", plan, stream, ws, dw_b);
 }
 
 extern "C" int udm_norm_residual_bwd(const void* dy, const float* x, const float* rstd, const float* mean, const float* w, float* dx, float* dw, int accumulate,
                                      const void* branch, void* dbranch, const float* w_b, const float* rstd_b, const float* mean_b, float* dw_b, float* dbias,
                                      int64_t M, int64_t d, int norm_type, float p_drop, uint64_t seed, float* ws, int64_t ws_elems, hipStream_t stream) {
+  const RowPlan plan = row_plan_norm_residual_bwd(M, d);   // (plan.ok checked below: the instance is one of the lists, the dispatcher's result is not needed)
   UDM_CHECK_ARG(dy && x && rstd && w && dx && dw && branch && dbranch && ws, "udm_norm_residual_bwd: null pointer");
-  UDM_CHECK_ARG(M > 0 && (d == 2048 || d == 4096 || (d % 8 == 0 && d >= 64 && d < 2048)),
-                "udm_norm_residual_bwd: the fused form is built for d = 2048 / 4096 (block per row) and d < 2048, d %% 8 == 0 (wave per row); got %ld", (long)d);
+  UDM_CHECK_ARG(plan.ok, "udm_norm_residual_bwd: the fused form is built for d = 2048 / 4096 (block per row) and d < 2048, d %% 8 == 0 (wave per row); got %ld", (long)d);
   UDM_CHECK_ARG(norm_type == 0 || mean, "udm_norm_residual_bwd: LayerNorm needs the saved mean");
   UDM_CHECK_ARG(!w_b || (rstd_b && dw_b && (norm_type == 0 || mean_b)), "udm_norm_residual_bwd: sandwich norm needs rstd_b, dw_b (and mean_b for LayerNorm)");
-  // 3 blocks per CU: every block leaves a [3][d] fp32 partial for colreduce3, and at 1536 blocks that workspace (38 MB written + read per call) cost more
-  // than the extra occupancy gave (in the step: 3.95 ms at 1536 blocks, 4.12 at 1024, 3.73 at 768, 3.77 at 512)
-  const bool wrow = d < 2048;
-  const int grid = wrow ? min(grid_rows(M), 1024) : (int)(M < 768 ? M : 768);
-  UDM_CHECK_ARG(ws_elems >= (int64_t)grid * 3 * d, "udm_norm_residual_bwd: workspace too small (need %ld floats)", (long)grid * 3 * d);
+  UDM_CHECK_ARG(ws_elems >= plan.ws_need, "udm_norm_residual_bwd: workspace too small (need %ld floats)", plan.ws_need);
   NormResidBwdArgs a{(const bf16_t*)dy, x, rstd, mean, w, dx, dw, accumulate, (const bf16_t*)branch, (bf16_t*)dbranch, w_b, rstd_b, mean_b, dw_b, dbias, ws,
                      (int)M, (int)d, norm_type, p_drop, seed};
-  if (wrow) {
-    switch (nch_for(d)) {
-      case 1: hipLaunchKernelGGL((norm_residual_bwd_wrow_kernel<1>), dim3(grid), dim3(256), 0, stream, a); break;
-      case 2: hipLaunchKernelGGL((norm_residual_bwd_wrow_kernel<2>), dim3(grid), dim3(256), 0, stream, a); break;
-      case 3: hipLaunchKernelGGL((norm_residual_bwd_wrow_kernel<3>), dim3(grid), dim3(256), 0, stream, a); break;
-      default: hipLaunchKernelGGL((norm_residual_bwd_wrow_kernel<4>), dim3(grid), dim3(256), 0, stream, a); break;
-    }
-  } else if (d == 2048) hipLaunchKernelGGL((norm_residual_bwd_kernel<1>), dim3(grid), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((norm_residual_bwd_kernel<2>), dim3(grid), dim3(256), 0, stream, a);
-  UDM_CHECK_LAUNCH("udm_norm_residual_bwd");
-  hipLaunchKernelGGL(colreduce3_kernel, dim3((unsigned)((d + 63) / 64), 16, 3), dim3(256), 0, stream, (const float*)ws, dw, w_b ? dw_b : nullptr, dbias, grid, (int)d);
-  UDM_CHECK_LAUNCH("udm_norm_residual_bwd(colreduce)");
-  return 0;
+  if (plan.form == WAVE_ROW) (void)with_inst<1, 2, 3, 4>(plan.inst, [&](auto n) { launch_rows(norm_residual_bwd_wrow_kernel<decltype(n)::value>, plan, stream, a); });
+  else (void)with_inst<1, 2>(plan.inst, [&](auto n) { launch_rows(norm_residual_bwd_kernel<decltype(n)::value>, plan, stream, a); });
+  return reduce_rows("udm_norm_residual_bwd", "udm_norm_residual_bwd(colreduce)", plan, stream, ws, dw, 3, w_b ? dw_b : nullptr, dbias);
 }
 
 // the fused pass with adaLN-Zero modulation of the norm and / or a gated residual branch (d = 2048 / 4096: the block-per-row form)
@@ -2022,27 +1941,22 @@ extern "C" int udm_norm_residual_bwd_ada(const void* dy, const float* x, const f
                                          const void* shift, const void* scale, float* dshift, float* dscale, const void* gate, float* dgate, int64_t mod_stride,
                                          const int64_t* modality, const int* any_img, const int64_t* modality_r, int64_t M, int64_t d, int64_t L, int norm_type,
                                          float p_drop, uint64_t seed, float* ws, int64_t ws_elems, hipStream_t stream) {
+  const RowPlan plan = row_plan_norm_residual_bwd_ada(M, d, L);
   UDM_CHECK_ARG(dy && x && rstd && w && dx && dw && branch && dbranch && ws, "udm_norm_residual_bwd_ada: null pointer");
-  UDM_CHECK_ARG(M > 0 && L > 0 && M % L == 0 && (d == 2048 || d == 4096), "udm_norm_residual_bwd_ada: d = 2048 / 4096 and M = B * L (got M=%ld L=%ld d=%ld)", (long)M, (long)L, (long)d);
+  UDM_CHECK_ARG(plan.ok, "udm_norm_residual_bwd_ada: d = 2048 / 4096 and M = B * L (got M=%ld L=%ld d=%ld)", (long)M, (long)L, (long)d);
   UDM_CHECK_ARG(norm_type == 0 || mean, "udm_norm_residual_bwd_ada: LayerNorm needs the saved mean");
   UDM_CHECK_ARG(!w_b || (rstd_b && dw_b && (norm_type == 0 || mean_b)), "udm_norm_residual_bwd_ada: sandwich norm needs rstd_b, dw_b (and mean_b for LayerNorm)");
   UDM_CHECK_ARG(!shift || (scale && dshift && dscale), "udm_norm_residual_bwd_ada: a modulated norm needs scale, dshift, dscale");
   UDM_CHECK_ARG(!gate || dgate, "udm_norm_residual_bwd_ada: a gate needs dgate");
-  const int B = (int)(M / L);
-  const int bpb = max(1, min(768 / B, (int)L));
-  const int grid = B * bpb;
-  UDM_CHECK_ARG(ws_elems >= (int64_t)grid * 6 * d, "udm_norm_residual_bwd_ada: workspace too small (need %ld floats)", (long)grid * 6 * d);
+  UDM_CHECK_ARG(ws_elems >= plan.ws_need, "udm_norm_residual_bwd_ada: workspace too small (need %ld floats)", plan.ws_need);
   NormResidBwdArgs a{(const bf16_t*)dy, x, rstd, mean, w, dx, dw, accumulate, (const bf16_t*)branch, (bf16_t*)dbranch, w_b, rstd_b, mean_b, dw_b, dbias, ws,
                      (int)M, (int)d, norm_type, p_drop, seed};
   a.shift = (const bf16_t*)shift; a.scale = (const bf16_t*)scale; a.dshift = dshift; a.dscale = dscale; a.gate = (const bf16_t*)gate; a.dgate = dgate;
-  a.mod_stride = (long)mod_stride; a.modality = modality; a.any_img = any_img; a.modality_r = modality_r; a.L = (int)L; a.bpb = bpb;
-  if (d == 2048) hipLaunchKernelGGL((norm_residual_bwd_kernel<1, true>), dim3(grid), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((norm_residual_bwd_kernel<2, true>), dim3(grid), dim3(256), 0, stream, a);
-  UDM_CHECK_LAUNCH("udm_norm_residual_bwd_ada");
-  hipLaunchKernelGGL(colreduce3_kernel, dim3((unsigned)((d + 63) / 64), 16, 3), dim3(256), 0, stream, (const float*)ws, dw, w_b ? dw_b : nullptr, dbias, grid, (int)d);
-  UDM_CHECK_LAUNCH("udm_norm_residual_bwd_ada(colreduce)");
-  hipLaunchKernelGGL(ada_reduce_kernel, dim3((unsigned)((d + 255) / 256), B, 3), dim3(256), 0, stream, (const float*)(ws + (long)grid * 3 * d), shift ? dshift : nullptr,
-                     shift ? dscale : nullptr, gate ? dgate : nullptr, (long)mod_stride, bpb, (int)d);
+  a.mod_stride = (long)mod_stride; a.modality = modality; a.any_img = any_img; a.modality_r = modality_r; a.L = (int)L; a.bpb = plan.bpb;
+  (void)with_inst<1, 2>(plan.inst, [&](auto n) { launch_rows(norm_residual_bwd_kernel<decltype(n)::value, true>, plan, stream, a); });
+  if (const int rc = reduce_rows("udm_norm_residual_bwd_ada", "udm_norm_residual_bwd_ada(colreduce)", plan, stream, ws, dw, 3, w_b ? dw_b : nullptr, dbias)) return rc;
+  hipLaunchKernelGGL(ada_reduce_kernel, dim3((unsigned)((d + 255) / 256), (unsigned)(M / L), 3), dim3(256), 0, stream, (const float*)(ws + 3L * plan.reduce_rows * plan.reduce_cols),
+                     shift ? dshift : nullptr, shift ? dscale : nullptr, gate ? dgate : nullptr, (long)mod_stride, plan.bpb, (int)d);
   UDM_CHECK_LAUNCH("udm_norm_residual_bwd_ada(ada reduce)");
   return 0;
 }
@@ -2055,32 +1969,11 @@ extern "C" int udm_qknorm_rope_fwd(const void* qkv, void* qkr, const float* gq, 
   UDM_CHECK_ARG(!gq || (bq && gk && bk && stats), "udm_qknorm_rope_fwd: qk-norm needs all four affine vectors and stats");
   QkArgs a{(const bf16_t*)qkv, (bf16_t*)qkr, gq, bq, gk, bk, stats, cos_t, sin_t, (int)M, (int)d, (int)L, (int)D, rope_per_sample, eps, q_scale};
   UDM_CHECK_ARG(D % 16 == 0 && d % 16 == 0, "udm_qknorm_rope_fwd: head_dim and hidden size must be multiples of 16");
-  const int nit = (int)((2 * (d / 16) + 63) / 64);
-  UDM_CHECK_ARG(nit <= 8, "udm_qknorm_rope_fwd: hidden size too large");
-  const int nch = nit <= 1 ? 1 : (nit == 2 ? 2 : (nit == 3 ? 3 : (nit == 4 ? 4 : 8)));
-  const size_t lds = gq ? (size_t)4 * d * sizeof(float) : 0;
-  if (d == 2048) {   // two rows per block iteration, 1024 blocks (in the step: 1.08-1.10 ms against 1.22-1.24 for one row per iteration; 3 rows 1.18, 4 rows 1.41)
-    const long groups = (M + 1) / 2;
-    const int g = (int)(groups < 1024 ? groups : 1024);
-    hipLaunchKernelGGL((qknorm_rope_fwd_brow_rows_kernel<2>), dim3(g), dim3(256), 0, stream, a);
-    UDM_CHECK_LAUNCH("udm_qknorm_rope_fwd");
-    return 0;
-  }
-  if (d >= 2048 && d <= 4096) {
-    const int g = (int)(M < 2048 ? M : 2048);
-    if (d <= 2048) hipLaunchKernelGGL((qknorm_rope_fwd_brow_kernel<1>), dim3(g), dim3(256), lds, stream, a);
-    else hipLaunchKernelGGL((qknorm_rope_fwd_brow_kernel<2>), dim3(g), dim3(256), lds, stream, a);
-    UDM_CHECK_LAUNCH("udm_qknorm_rope_fwd");
-    return 0;
-  }
-  const int grid = min(grid_rows(M), 1024);
-  switch (nch) {
-    case 1: hipLaunchKernelGGL((qknorm_rope_fwd_kernel<1>), dim3(grid), dim3(256), lds, stream, a); break;
-    case 2: hipLaunchKernelGGL((qknorm_rope_fwd_kernel<2>), dim3(grid), dim3(256), lds, stream, a); break;
-    case 3: hipLaunchKernelGGL((qknorm_rope_fwd_kernel<3>), dim3(grid), dim3(256), lds, stream, a); break;
-    case 4: hipLaunchKernelGGL((qknorm_rope_fwd_kernel<4>), dim3(grid), dim3(256), lds, stream, a); break;
-    default: hipLaunchKernelGGL((qknorm_rope_fwd_kernel<8>), dim3(grid), dim3(256), lds, stream, a); break;
-  }
+  const RowPlan plan = row_plan_qk_fwd(M, d, gq != nullptr);
+  UDM_CHECK_ARG(plan.ok, "udm_qknorm_rope_fwd: hidden size too large");
+  if (plan.form == BLOCK_ROW_2ROWS) launch_rows(qknorm_rope_fwd_brow_rows_kernel<2>, plan, stream, a);
+  else if (plan.form == BLOCK_ROW) launch_rows(qknorm_rope_fwd_brow_kernel<2>, plan, stream, a);
+  else (void)with_inst<1, 2, 3, 4>(plan.inst, [&](auto n) { launch_rows(qknorm_rope_fwd_kernel<decltype(n)::value>, plan, stream, a); });
   UDM_CHECK_LAUNCH("udm_qknorm_rope_fwd");
   return 0;
 }
@@ -2091,48 +1984,16 @@ extern "C" int udm_qknorm_rope_bwd(const void* dqkr, const void* qkv, void* dqkv
   UDM_CHECK_ARG(dqkr && qkv && dqkv && cos_t && sin_t, "udm_qknorm_rope_bwd: null pointer");
   UDM_CHECK_ARG(M > 0 && d > 0 && D > 0 && d % D == 0 && D % 8 == 0, "udm_qknorm_rope_bwd: bad shape");
   UDM_CHECK_ARG(!gq || (gk && stats && dgq && dbq && dgk && dbk), "udm_qknorm_rope_bwd: qk-norm needs gk, stats and the four gradient vectors");
-  QkBwdArgs a{(const bf16_t*)dqkr, (const bf16_t*)qkv, (bf16_t*)dqkv, gq, gk, stats, cos_t, sin_t, dgq, dbq, dgk, dbk, nullptr, (int)M, (int)d, (int)L, (int)D,
-              rope_per_sample, q_scale};
   UDM_CHECK_ARG(D % 16 == 0 && d % 16 == 0, "udm_qknorm_rope_bwd: head_dim and hidden size must be multiples of 16");
-  const int nit = (int)((2 * (d / 16) + 63) / 64);
-  UDM_CHECK_ARG(nit <= 8, "udm_qknorm_rope_bwd: hidden size too large");
-  const int nch = nit <= 1 ? 1 : (nit == 2 ? 2 : (nit == 3 ? 3 : (nit == 4 ? 4 : 8)));
-  const size_t lds = gq ? ((size_t)2 * d + 4096) * sizeof(float) : 0;
-  if (d >= 2048 && d <= 4096) {
-    int g = (int)(M < 1024 ? M : 1024);   // (swept 256 .. 2048 in the step: 2.92 / 1.91 / 1.69 / 1.60 / 1.88 / 1.82 / 1.87 ms per step at 256 / 512 / 768 / 1024 / 1280 / 1536 / 2048)
-    UDM_CHECK_ARG(!gq || (dbq == dgq + d && dgk == dgq + 2 * d && dbk == dgq + 3 * d) || !ws, "udm_qknorm_rope_bwd: the workspace form needs dgq|dbq|dgk|dbk contiguous");
-    if (gq && ws && ws_elems >= (int64_t)g * 4 * d) a.ws = ws;
-    else if (gq) g = g < 256 ? g : 256;
-    const size_t l2 = gq ? (size_t)2 * d * sizeof(float) : 0;
-    if (d <= 2048) hipLaunchKernelGGL((qknorm_rope_bwd_brow_kernel<1>), dim3(g), dim3(256), l2, stream, a);
-    else hipLaunchKernelGGL((qknorm_rope_bwd_brow_kernel<2>), dim3(g), dim3(256), l2, stream, a);
-    UDM_CHECK_LAUNCH("udm_qknorm_rope_bwd");
-    if (a.ws) {
-      hipLaunchKernelGGL(colreduce_kernel, dim3((unsigned)((4 * d + 63) / 64), 16), dim3(256), 0, stream, (const float*)ws, dgq, g, (int)(4 * d));
-      UDM_CHECK_LAUNCH("udm_qknorm_rope_bwd(colreduce)");
-    }
-    return 0;
-  }
-  // narrow rows (wave per row): with a workspace the column sums go through it and the grid can be wide enough to hide HBM latency (a same-address
-  // atomic per block and column limited it to 256 blocks: 117 us at d = 768, M = 24576); without one, the short atomic chains stay
-  int grid = min(grid_rows(M), 256);
-  if (gq && ws && dbq == dgq + d && dgk == dgq + 2 * d && dbk == dgq + 3 * d) {
-    const int wide = min(grid_rows(M), 1024);
-    if (ws_elems >= (int64_t)wide * 4 * d && wide >= 64) { grid = wide; a.ws = ws; }
-  }
-  switch (nch) {
-    case 1: hipLaunchKernelGGL((qknorm_rope_bwd_kernel<1>), dim3(grid), dim3(256), lds, stream, a); break;
-    case 2: hipLaunchKernelGGL((qknorm_rope_bwd_kernel<2>), dim3(grid), dim3(256), lds, stream, a); break;
-    case 3: hipLaunchKernelGGL((qknorm_rope_bwd_kernel<3>), dim3(grid), dim3(256), lds, stream, a); break;
-    case 4: hipLaunchKernelGGL((qknorm_rope_bwd_kernel<4>), dim3(grid), dim3(256), lds, stream, a); break;
-    default: hipLaunchKernelGGL((qknorm_rope_bwd_kernel<8>), dim3(grid), dim3(256), lds, stream, a); break;
-  }
-  UDM_CHECK_LAUNCH("udm_qknorm_rope_bwd");
-  if (a.ws) {
-    hipLaunchKernelGGL(colreduce_kernel, dim3((unsigned)((4 * d + 63) / 64), 16), dim3(256), 0, stream, (const float*)ws, dgq, grid, (int)(4 * d));
-    UDM_CHECK_LAUNCH("udm_qknorm_rope_bwd(colreduce)");
-  }
-  return 0;
+  const bool contiguous = gq && dbq == dgq + d && dgk == dgq + 2 * d && dbk == dgq + 3 * d;
+  const RowPlan plan = row_plan_qk_bwd(M, d, gq != nullptr, contiguous, ws ? ws_elems : 0);
+  UDM_CHECK_ARG(plan.ok, "udm_qknorm_rope_bwd: hidden size too large");
+  UDM_CHECK_ARG(plan.form != BLOCK_ROW || !gq || contiguous || !ws, "udm_qknorm_rope_bwd: the workspace form needs dgq|dbq|dgk|dbk contiguous");
+  QkBwdArgs a{(const bf16_t*)dqkr, (const bf16_t*)qkv, (bf16_t*)dqkv, gq, gk, stats, cos_t, sin_t, dgq, dbq, dgk, dbk, plan.use_ws ? ws : nullptr, (int)M, (int)d,
+              (int)L, (int)D, rope_per_sample, q_scale};
+  if (plan.form == BLOCK_ROW) (void)with_inst<1, 2>(plan.inst, [&](auto n) { launch_rows(qknorm_rope_bwd_brow_kernel<decltype(n)::value>, plan, stream, a); });
+  else (void)with_inst<1, 2, 3, 4>(plan.inst, [&](auto n) { launch_rows(qknorm_rope_bwd_kernel<decltype(n)::value>, plan, stream, a); });
+  return reduce_rows("udm_qknorm_rope_bwd", "udm_qknorm_rope_bwd(colreduce)", plan, stream, ws, dgq);
 }
 
 // ---------------------------------------------------------------------------------------------

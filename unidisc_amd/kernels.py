@@ -599,6 +599,26 @@ def cast_bf16_f32(x, y, scale=1.0):
 
 
 # ------------------------------------------------------------------------------------------------ norms
+# The workspace each backward wrapper below offers its entry point, in floats, for a call of M rows of width d: the one place these sizes are stated.  The C side
+# (csrc/rowops_plan.h) decides from the size offered whether the column sums go through the workspace; every entry names the plan constant it mirrors, and
+# tests/test_rowops_plan.py asserts that each ask covers the `ws_need` of the plan chosen under it.  0: no workspace is offered (the atomics form).
+_ADA_GRID_ROWS = 768     # FUSED_ADA_GRID: partial-sum rows of udm_norm_residual_bwd_ada's workspace (grid = B * max(1, min(768 / B, L)))
+ROWOPS_WS = {
+    "norm_bwd": lambda M, d: 1024 * d if M >= 2048 else 0,         # NORM_BWD_GRID_NARROW rows; the M >= 2048 gate is this wrapper's own: fewer rows stay on atomics
+    "residual_bwd": lambda M, d: 1536 * d,                         # RESID_BWD_GRID_BROW rows, the widest of its grids (offered with a sandwich norm only: dw_b is its one column sum)
+    # three planes of min(M, FUSED_BWD_GRID_WROW = 1024) or min(M, FUSED_BWD_GRID_BROW = 768) rows: up to 512 rows of slack per plane above M = 1024, kept as
+    # allocated so far
+    "norm_residual_bwd": lambda M, d: min(M, 1536) * 3 * d,
+    "norm_residual_bwd_ada": lambda M, d: _ADA_GRID_ROWS * 6 * d,  # six planes of FUSED_ADA_GRID rows
+    "qknorm_rope_bwd": lambda M, d: 4096 * d,                      # QK_BWD_GRID_WROW_WS = QK_BWD_GRID_BROW = 1024 rows of 4 d (offered with the four gradients in one allocation only)
+}
+
+
+def norm_residual_bwd_fused_ok(d):
+    """the widths udm_norm_residual_bwd is built for (row_plan_norm_residual_bwd's `ok`); norm_residual_bwd runs the two separate kernels elsewhere"""
+    return d in (2048, 4096) or (d < 2048 and d % 8 == 0 and d >= 64)
+
+
 def _mod_ptrs(mod, idx, d):
     """adaLN slices: `mod` is the bf16 (or fp32 gradient) [Bp, n*d] adaLN tensor, idx picks d-wide column chunks."""
     if mod is None:
@@ -627,7 +647,8 @@ def norm_bwd(dy, x, rstd, mean, w, norm_type, L, dx, dw, *, accumulate=True, mod
     M, d = x.shape
     (shift, scale), ms = _mod_ptrs(mod, mod_idx, d)
     (dshift, dscale), _ = _mod_ptrs(dmod, mod_idx, d)
-    ws = _scratch(1024 * d, x.device) if M >= 2048 else None
+    n = ROWOPS_WS["norm_bwd"](M, d)
+    ws = _scratch(n, x.device) if n else None
     _lib.call("udm_norm_bwd", _p(dy), _p(x), _p(rstd), _p(mean), _p(w), shift, scale, ms, _p(modality) if mod is not None else None,
               _p(any_img) if mod is not None else None, _p(dx), _p(dw), dshift, dscale, M, d, L, norm_type, 1 if accumulate else 0,
               _p(ws), ws.numel() if ws is not None else 0, _s())
@@ -678,7 +699,7 @@ def residual_bwd(dx, branch, L, *, w_b=None, rstd=None, mean=None, norm_type=NOR
     use = gate_idx is not None and mod is not None
     (gate,), ms = _mod_ptrs(mod if use else None, (gate_idx,), d)
     (dgate,), _ = _mod_ptrs(dmod if use else None, (gate_idx,), d)
-    ws = _scratch(1536 * d, dx.device) if w_b is not None else None
+    ws = _scratch(ROWOPS_WS["residual_bwd"](M, d), dx.device) if w_b is not None else None
     _lib.call("udm_residual_bwd", _p(dx), _p(branch), _p(dbranch), _p(w_b), _p(rstd), _p(mean), gate, ms, _p(modality), _p(dw_b), dgate, M, d, L,
               norm_type, float(p_drop), int(seed), _p(ws), ws.numel() if ws is not None else 0, _s())
     return dbranch
@@ -690,9 +711,9 @@ def norm_residual_bwd(dy, x, rstd, mean, w, norm_type, L, dx, dw, branch, *, acc
     dbias += column sums of d branch when given).  One fused pass per row at d = 2048 / 4096 (block per row) and at d < 2048 (wave per row), the separate
     kernels otherwise."""
     M, d = x.shape
-    if (d in (2048, 4096) or (d < 2048 and d % 8 == 0 and d >= 64)) and x.is_cuda:
+    if norm_residual_bwd_fused_ok(d) and x.is_cuda:
         dbranch = torch.empty((M, d), dtype=BF16, device=x.device)
-        ws = _scratch(min(M, 1536) * 3 * d, x.device)
+        ws = _scratch(ROWOPS_WS["norm_residual_bwd"](M, d), x.device)
         _lib.call("udm_norm_residual_bwd", _p(dy), _p(x), _p(rstd), _p(mean), _p(w), _p(dx), _p(dw), 1 if accumulate else 0, _p(branch), _p(dbranch), _p(w_b),
                   _p(rstd_b), _p(mean_b), _p(dw_b), _p(dbias), M, d, norm_type, float(p_drop), int(seed), _p(ws), ws.numel(), _s())
         return dbranch
@@ -701,9 +722,6 @@ def norm_residual_bwd(dy, x, rstd, mean, w, norm_type, L, dx, dw, branch, *, acc
     if dbias is not None:
         colsum(out, dbias)
     return out
-
-
-_ADA_GRID_ROWS = 768     # partial-sum rows of udm_norm_residual_bwd_ada's workspace (rowops.hip: grid = B * max(1, min(768 / B, L)))
 
 
 def norm_residual_bwd_ada_ok(M, d, L):
@@ -728,7 +746,7 @@ def norm_residual_bwd_ada(dy, x, rstd, mean, w, norm_type, L, dx, dw, branch, *,
         if m_ is not None and (dm_ is None or dm_.stride(0) != m_.stride(0)):
             raise ValueError("norm_residual_bwd_ada: an adaLN tensor and its gradient must share their row stride")
     dbranch = torch.empty((M, d), dtype=BF16, device=x.device)
-    ws = _scratch(_ADA_GRID_ROWS * 6 * d, x.device)
+    ws = _scratch(ROWOPS_WS["norm_residual_bwd_ada"](M, d), x.device)
     _lib.call("udm_norm_residual_bwd_ada", _p(dy), _p(x), _p(rstd), _p(mean), _p(w), _p(dx), _p(dw), 1 if accumulate else 0, _p(branch), _p(dbranch), _p(w_b), _p(rstd_b),
               _p(mean_b), _p(dw_b), _p(dbias), shift, scale, dshift, dscale, gate, dgate, ms_n or ms_r, _p(modality) if mod_n is not None else None,
               _p(any_img) if mod_n is not None else None, _p(modality_r), M, d, L, norm_type, float(p_drop), int(seed), _p(ws), ws.numel(), _s())
@@ -762,7 +780,7 @@ def qknorm_rope_bwd(dqkr, qkv, dqkv, cos, sin, L, D, *, gq=None, gk=None, stats=
     d = d3 // 3
     per_sample = 1 if cos.dim() == 3 else 0
     contig = gq is not None and dbq.data_ptr() == dgq.data_ptr() + 4 * d and dgk.data_ptr() == dgq.data_ptr() + 8 * d and dbk.data_ptr() == dgq.data_ptr() + 12 * d
-    ws = _scratch(4096 * d, qkv.device) if contig else None
+    ws = _scratch(ROWOPS_WS["qknorm_rope_bwd"](M, d), qkv.device) if contig else None
     _lib.call("udm_qknorm_rope_bwd", _p(dqkr), _p(qkv), _p(dqkv), _p(gq), _p(gk), _p(stats), _p(cos), _p(sin), per_sample, _p(dgq), _p(dbq), _p(dgk),
               _p(dbk), M, d, L, D, float(q_scale), _p(ws), ws.numel() if ws is not None else 0, _s())
 
