@@ -260,7 +260,14 @@ int udm_subs_logprobs(const void* logits, int64_t ld, const int64_t* xt, const i
 
 /* ---- loss arithmetic behind the per-token log-probabilities: Diffusion.compute_loss model.py:1010-1160 (schedule weights applied per row, masked mean or the
  * modality-weighted text / image sum with the optional text-loss cap); nlls = -log_p w_std on attended tokens, coef = d loss / d log_p,
- * scalars = {loss, txt_loss, img_loss, txt_frac, img_frac, valid_frac, txt_count, img_count}.  attention_mask: bool [B, L]; modality_mask: bool [B, L, 2] or NULL */
+ * scalars = {loss, txt_loss, img_loss, txt_frac, img_frac, valid_frac, txt_count, img_count}.  attention_mask: bool [B, L]; modality_mask: bool [B, L, 2] or NULL
+ * Conventions: an empty modality contributes 0 to the loss and passes no gradient, 0 / 0 gives loss 0 (the reference's nan_to_num; its autograd returns NaN
+ * gradients there, this entry point the finite gradient of the other term); txt_frac / img_frac are NaN when no attended token has a modality.
+ * Behind the mask: unless full_mask, the term of an unattended position is never added - log_p may hold anything there, NaN included, and nlls (+0 there), the
+ * scalars and coef are bit-identical to the call with finite values in its place (the reference's tensor statements multiply by the mask and carry such a NaN
+ * into the loss).  coef at an unattended position is -w_loss[b] * 0: -0 for a positive weight, NaN for a non-finite one.
+ * One workgroup, a fixed summation order, no atomics: two calls on the same inputs are bit-identical.  With non-negative terms the sums carry at most
+ * ceil(B L / 1024) + 23 fp32 roundings (tests/datapath_ref.py derives the bounds of every output from it). */
 int udm_diffusion_loss(const float* log_p, const float* w_loss, const float* w_std, const void* attention_mask, const void* modality_mask, float* nlls, float* coef,
                        float* scalars, int64_t B, int64_t L, int weighted, int full_mask, float text_w, float img_w, float ratio, hipStream_t stream);
 
@@ -322,10 +329,20 @@ int udm_assemble_joint_tokens(const int32_t* txt, const uint8_t* txt_mask, const
 /* ---- interleaved / packed rows: the per-position layout work of a packed batch as kernels (static shapes, no host reads)
  * udm_interleaved_rope: models/dit.py:1421-1444 with add_img_data_to_blocks / add_txt_data_to_blocks (:122-191).  modality / sid int64 [B, L]; img_cos / img_sin the 2-D
  *   tables of the supported image block sizes concatenated in the order of `sizes` (a HOST array of nsizes <= 8 ints), [sum sizes, half] fp32; txt_cos / txt_sin
- *   [txt_rows, half].  Writes cos, sin fp32 [B, L, half] and count_idx int64 [B, L] (row of img_count_embedding to add, -1: none).  scratch: B * 5 * L ints.
+ *   [txt_rows, half].  Writes cos, sin fp32 [B, L, half] and count_idx int64 [B, L] (row of img_count_embedding to add, -1: none).
+ *   scratch: int32 [B, 5, L], exactly - per row the planes run start | run end | j | start of the run of one sample id | list of image-run starts; planes 0, 1, 3
+ *   are written at every position, plane 2 at the image-run starts only, plane 4 in its first (number of image runs) entries; nothing else is touched.
  * udm_interleaved_block_lottery: model.py:483-522 after its draws - candidate block i of the batch (row-major order) reads r[i] (r fp32 [n_r]; ranks >= n_r never hit).
  *   Writes accum bool bytes [B, L] (positions of the blocks masked as a whole), rows_hit bool bytes [B], n_cand int64 [1] (number of candidate blocks).
- *   scratch: B * 4 * L ints, row_cands: B ints.
+ *   scratch: int32 [B, 4, L], exactly - per row the planes block start | next block's start | list of candidate starts | hit flag; planes 0 and 1 are written at
+ *   every position, plane 2 in its first (candidates of the row) entries, plane 3 at candidate starts only.  row_cands: int32 [B], all written.  n_cand is written
+ *   once, by the last row's workgroup.  r may be NULL when n_r == 0.
+ * Preconditions of both (what `PackingCollate` produces, unidisc_amd/token_data.py: the samples of a row are numbered 0, 1, 2 .., unused positions get -1):
+ *   -1 is the only negative sample id, and every id is below L.  The kernels compare ids exactly and would also take other values, but the tensor-statement
+ *   forms they are tested against (`DIT._rotary_interleaved_torch`, the statement path of `Diffusion._interleaved_block_lottery`) group all negative ids together
+ *   and build group keys row * (L + 1) + id that collide across rows for an id above L: outside the precondition the two forms may differ.
+ *   Image runs are maximal stretches of modality != 0 whatever the sample id (every non-zero value counts as image; `update_batch` clamps the collate's -1 on
+ *   padding to 0 before these calls); blocks of the lottery are runs of constant (modality, id).
  * udm_rowgroup_sum_f32: out[g, :] += sum of the rows r of x [M, d] with group[r] == g (0 <= g < G <= 32; other rows are skipped): the image-count embedding's gradient. */
 int udm_interleaved_rope(const int64_t* modality, const int64_t* sid, const float* img_cos, const float* img_sin, const int32_t* sizes, int64_t nsizes, const float* txt_cos,
                          const float* txt_sin, int64_t txt_rows, int64_t B, int64_t L, int64_t half, float* cos, float* sin, int64_t* count_idx, int32_t* scratch,
@@ -334,7 +351,9 @@ int udm_interleaved_block_lottery(const int64_t* modality, const int64_t* sid, c
                                   uint8_t* rows_hit, int64_t* n_cand, int32_t* scratch, int32_t* row_cands, hipStream_t stream);
 int udm_rowgroup_sum_f32(const float* x, const int64_t* group, float* out, int64_t M, int64_t d, int64_t G, hipStream_t stream);
 /* q_xt model.py:424-587 for multimodal (non-interleaved) batches after its random draws: move = r_move < move_chance[b], whole-modality masking (a row drawn for both
- * modalities masks neither), xt = move ? mask_id : x; outputs bool [B, L] move_indices and bool [B] rows (text masked, image masked, either).  r_txt / r_img NULL: no draw. */
+ * modalities masks neither), xt = move ? mask_id : x; outputs bool [B, L] move_indices and bool [B] rows (text masked, image masked, either).  r_txt / r_img NULL: no draw
+ * for that modality (either may be given alone); with both NULL the modality mask and the three row outputs may be NULL and are not touched.  Both comparisons are
+ * strict: a draw equal to its threshold does not mask. */
 int udm_qxt_absorbing(const int64_t* x, const float* r_move, const float* move_chance, const float* r_txt, const float* r_img, float thr_txt, float thr_img,
                       const void* modality_mask, int64_t B, int64_t L, int64_t mask_id, int64_t* xt, void* move_indices, void* row_txt, void* row_img, void* row_ignore,
                       hipStream_t stream);

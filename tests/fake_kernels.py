@@ -296,7 +296,8 @@ def attention_doc_ranges(sample_ids):
             if ids.numel():
                 hit = ((sample_ids[b] >= ids.min()) & (sample_ids[b] <= ids.max())).nonzero().flatten()
                 r[b, t, 0], r[b, t, 1] = int(hit[0]), int(hit[-1]) + 1
-                r[b, t, 2], r[b, t, 3] = (int(ids.min()) if ids.numel() == tile.numel() else -1), int(ids.max())
+                small = int(ids.max()) < 1 << 30          # ids that do not fit an int32 interval are never reported (the kernel: "never uniform")
+                r[b, t, 2], r[b, t, 3] = (int(ids.min()) if small and ids.numel() == tile.numel() else -1), (int(ids.max()) if small else -2)
                 r[b, t, 4] = int(r[b, t, 2] >= 0 and r[b, t, 2] == r[b, t, 3] and hit.numel() == int(hit[-1]) + 1 - int(hit[0]))
     return r
 
