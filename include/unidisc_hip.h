@@ -238,6 +238,21 @@ int udm_attention_bwd_dropout(const void* q, const void* k, const void* v, const
 int udm_attention_fwd_kv(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t D, int64_t q_stride,
                          int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t q_batch, int64_t k_batch, int64_t v_batch, int64_t o_batch, int64_t flags,
                          hipStream_t stream);
+/* The same attention with the keys split over workgroups - for small batches, where ceil(Lq / 128) * B * H workgroups leave most CUs idle (32 on 256 CUs at
+ * B = 1, H = 16, Lq = 256).  The arguments of udm_attention_fwd_kv plus, in front of flags: ws (fp32 scratch, 16-byte aligned, or NULL), ws_elems (its size in
+ * floats) and splits: 0 = the plan decides (attn_plan_fwd_kv_split, csrc/attention_plan.h: one split while the unsplit grid fills a quarter of the device's
+ * workgroup slots), >= 1 forces a count.  The count is lowered so that every split owns at least one 64-key tile, to at most 32, and to what ws holds
+ * (S * B * H * Lq * (D + 2) floats for S > 1); ws = NULL gives one split.  One split launches the kernel of udm_attention_fwd_kv: bit-identical results.
+ * S > 1: the grid is ceil(Lq / 128) * B * H * S; each workgroup walks a contiguous, balanced range of key tiles (9 tiles in 4 splits: 3, 2, 2, 2; the last
+ * range carries the Lk tail) and writes per query row (m, l, unnormalised O[D]) in fp32 to ws; a second launch forms M = max_s m_s and
+ * O = sum_s 2^(m_s - M) O_s / sum_s 2^(m_s - M) l_s in the fixed order s = 0 .. S - 1 with one rounding to bf16 (no atomics: bit-identical from launch to
+ * launch).  Same flags, argument errors and addressing guarantee; in addition nothing outside the first S * B * H * Lq * (D + 2) floats of ws is written.
+ * udm_attention_kv_split_plan: the split count a call with `splits` (0 = the plan's choice on the current device) runs with an unlimited workspace, and the
+ * floats of workspace it needs (0 for one split); either output pointer may be NULL. */
+int udm_attention_fwd_kv_split(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t D,
+                               int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t q_batch, int64_t k_batch, int64_t v_batch,
+                               int64_t o_batch, float* ws, int64_t ws_elems, int64_t splits, int64_t flags, hipStream_t stream);
+int udm_attention_kv_split_plan(int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t D, int64_t splits, int64_t* splits_out, int64_t* ws_elems_out);
 
 /* ---- embeddings: EmbeddingLayer models/dit.py:1036-1043 (+modality embedding :1402-1411) ------------- */
 /* ids outside [0, V): the forward CLAMPS them (a negative id reads row 0, an id >= V row V - 1); the backward DROPS them from dE and still counts their rows

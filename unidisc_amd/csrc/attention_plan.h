@@ -149,3 +149,60 @@ inline AttnKvPlan attn_plan_fwd_kv(const AttnKvProblem& p) {
   plan.lds_bytes = (uint32_t)(4 * 64 * p.D * 2);
   return plan;
 }
+
+// ---- the key-split form (attention_kv.hip, udm_attention_fwd_kv_split): the same body, S workgroups per (128-query block, b, h), each over a contiguous range
+// of 64-key tiles; fp32 partials (m, l, unnormalised O) per query row in a workspace, a second launch combines them in the fixed order s = 0 .. S - 1.
+// The consumer is the conditioning K / V cache at batch 1 or 2 (DESIGN.md "Conditioning K/V cache"): 256 queries against 1280 keys are 32 workgroups unsplit.
+constexpr int ATTN_KV_MAX_SPLITS = 32;
+struct AttnKvSplitPlan {
+  AttnKvPlan base;          // the unsplit plan of the same problem (q_tiles, kv_tiles, lds_bytes); S = 1 launches exactly it
+  uint32_t splits = 1;      // S
+  uint32_t grid = 0;        // q_tiles * B * H * S workgroups
+  long ws_elems = 0;        // floats the workspace must hold for S splits: S B H Lq (D + 2), 0 for S = 1
+  bool grid_ok = false;
+};
+// floats of workspace S splits need: per (split, b, h, query row) the D unnormalised outputs, then m and l.  Layout: all O rows ([S][B][H][Lq][D]), then all
+// (m, l) pairs ([S][B][H][Lq][2]) - 16-byte rows for the kernels' four-float stores.
+inline long attn_kv_split_ws_elems(const AttnKvProblem& p, long S) { return S <= 1 ? 0 : S * p.B * p.H * p.Lq * (long)(p.D + 2); }
+// tiles [begin, end) of split s: balanced, the first kv_tiles % S splits take one more (9 tiles in 4 splits: 3, 2, 2, 2); the last range carries the Lk tail
+inline void attn_kv_split_range(long kv_tiles, long S, long s, long& begin, long& end) {
+  const long base = kv_tiles / S, rem = kv_tiles % S;
+  begin = s * base + (s < rem ? s : rem);
+  end = begin + base + (s < rem ? 1 : 0);
+}
+// a requested split count lowered to what can run: every split owns at least one key tile, at most ATTN_KV_MAX_SPLITS, and what `ws_elems` floats hold
+// (have_ws = false: the NULL workspace, one split)
+inline long attn_kv_split_clamp(const AttnKvProblem& p, long S, bool have_ws, long ws_elems) {
+  const long T = (p.Lk + 63) / 64, per = p.B * p.H * p.Lq * (long)(p.D + 2);
+  if (S > T) S = T;
+  if (S > ATTN_KV_MAX_SPLITS) S = ATTN_KV_MAX_SPLITS;
+  if (!have_ws) S = 1;
+  else if (per > 0 && S > ws_elems / per) S = ws_elems / per;
+  return S < 1 ? 1 : S;
+}
+inline AttnKvSplitPlan attn_kv_split_with(const AttnKvProblem& p, long S) {
+  AttnKvSplitPlan plan;
+  plan.base = attn_plan_fwd_kv(p);
+  const long grid = (long)plan.base.grid * S;
+  plan.grid_ok = plan.base.grid_ok && grid < (1L << 31);
+  plan.splits = (uint32_t)S;
+  plan.grid = plan.grid_ok ? (uint32_t)grid : 0;
+  plan.ws_elems = attn_kv_split_ws_elems(p, S);
+  return plan;
+}
+// The plan's own choice (splits = 0).  One split while the unsplit grid fills at least a QUARTER of the device's workgroup slots (ATTN_KV_WGS per CU): the second
+// launch and the fp32 round trip of the partials then cost more than the idle CUs win.  Otherwise the smallest power of two that brings the grid to HALF the
+// slots - one workgroup per CU at head dim <= 128 - halved until every split keeps at least two key tiles (and at most ATTN_KV_MAX_SPLITS).
+// Both fractions are measured (RESULTS.md "Conditioning K/V cache", 256 CUs, H 16, D 128, Lk 1280): the first form of this rule - split below half of the slots,
+// up to all of them - chose S = 4 at Lq 1024, B 1 (128 workgroups, a quarter of the slots), 4 % slower than unsplit, and S = 8 at Lq 256, B 2, where S = 4 is
+// 17 % faster than S = 8.  At Lq 256, B 1 both forms give S = 8 (0.69 of the unsplit time).
+inline AttnKvSplitPlan attn_plan_fwd_kv_split(const AttnKvProblem& p, int dev_cus) {
+  const AttnKvPlan base = attn_plan_fwd_kv(p);
+  const long slots = (long)dev_cus * ATTN_KV_WGS(p.D), T = base.kv_tiles;
+  long S = 1;
+  if (base.grid_ok && 4L * base.grid < slots) {
+    while (2L * base.grid * S < slots && S < ATTN_KV_MAX_SPLITS) S *= 2;
+    while (S > 1 && T / S < 2) S /= 2;
+  }
+  return attn_kv_split_with(p, S);
+}

@@ -587,6 +587,8 @@ class Diffusion:
         masked] (the reference's non-split form, :1787-1803), head on the same positions of both halves.  Returns the cache tuple
         (logits_cond [R, Vp], rows [R], n, logits_uncond [R, Vp], per-row weights [n]) or None when the guidance weight is zero everywhere."""
         ev = cfg_get(self.config, "eval", None)
+        if getattr(self, "_cond", None) is not None:   # eval.conditioning_cache: every forward of the run goes through the conditioning K / V cache
+            return self._cond_masked_logits(x, t, sigma, x0_unmask)
         if cfg_get(ev, "cfg", None) is None or x0_unmask is None or not bool(x0_unmask.any()):
             return None
         w = self.get_cfg_weight(t)
@@ -611,6 +613,82 @@ class Diffusion:
         w_b = w.to(torch.float32).reshape(-1)
         w_rows = (w_b.index_select(0, b_of) if w_b.numel() == B else w_b.expand(B).index_select(0, b_of)).contiguous()
         return logits[:n], rows[:n], n, logits_u[:n], w_rows
+
+    # ---- `eval.conditioning_cache` (extension key): conditional sampling with one modality fully given.  Under the ModalityMask that blinds the given
+    # modality's queries to the other one, its K / V in every block depend on its own tokens alone - constant for the whole run (and all-[MASK], so constant
+    # too, in the unconditional half of guided sampling).  Step 0 runs the full sequence and fills the backbone's conditioning cache
+    # (DIT.set_conditioning_cache); every later forward runs on the generated slice and attends to [cached ; fresh] keys.  Nothing is ever stale.
+    def _conditioning_setup(self, x0, x0_unmask, modality, sample_ids, caching, B, L):
+        name = "unidisc_amd.Diffusion.sample: eval.conditioning_cache"
+        ev = cfg_get(self.config, "eval", None)
+        if caching:
+            raise NotImplementedError(f"{name} with eval.attention_caching - two different caches, set one")
+        if self.time_conditioning:
+            raise NotImplementedError(f"{name} with time_conditioning - the cached conditioning keys would depend on sigma")
+        if sample_ids is not None:
+            raise NotImplementedError(f"{name} with sample_ids - built for unpacked batches")
+        Lt = int(cfg_get(cfg_get(self.config, "model"), "txt_length"))
+        txt_given = x0_unmask is not None and 0 < Lt < L and bool(x0_unmask[:, :Lt].all())
+        img_given = x0_unmask is not None and 0 < Lt < L and bool(x0_unmask[:, Lt:].all())
+        if txt_given == img_given:
+            raise NotImplementedError(f"{name} needs x0 / x0_unmask with exactly one of the static slices [:txt_length] / [txt_length:] fully given in every row "
+                                      f"({'both are' if txt_given else 'neither is'})")
+        if modality is not None and not (bool((modality[:, :Lt] == 0).all()) and bool((modality[:, Lt:] != 0).all())):
+            raise NotImplementedError(f"{name} needs the text in the static slice [:txt_length] of every sample")
+        guided = cfg_get(ev, "cfg", None) is not None
+        self.backbone.set_conditioning_cache(B, L, self.device, given="text" if txt_given else "image", guided=guided)
+        mod_rows = modality   # what the SUBS vocabulary restriction reads per row: the static slices, written out, once x is a slice
+        if mod_rows is None and self._restrict():
+            mod_rows = torch.zeros((B, L), dtype=torch.int64, device=self.device)
+            mod_rows[:, self.static_img_sl] = 1
+        return dict(sl=slice(Lt, L) if txt_given else slice(0, Lt), guided=guided, split=bool(cfg_get(ev, "split_cfg_batches", False)), built=False, sliced=False,
+                    modality=modality, mod_rows=mod_rows, B=B, L=L)
+
+    def _cond_masked_logits(self, x, t, sigma, x0_unmask):
+        """the cache tuple of `_guided_masked_logits` (5 entries with guidance weights > 0 somewhere, else (logits, rows, n)) from a conditioning-cache forward:
+        "build" on the full x while the cache is empty - with guidance always on both halves, whatever the weights, since both halves' keys are needed later -
+        and "read" on the generated slice afterwards"""
+        st, bb = self._cond, self.backbone
+        what = "read" if st["built"] else "build"
+        mod = None if st["built"] else st["modality"]
+        B, L = x.shape
+        w = self.get_cfg_weight(t) if (st["guided"] and t is not None) else None
+        use_w = w is not None and bool((w > 0).any())
+        if not st["guided"] or (st["built"] and not use_w):
+            out = bb.forward_masked_logits(x, sigma, modality=mod, conditioning_cache=what)
+            st["built"] = True
+            return out
+        x_uncond = x.clone()
+        x_uncond[x0_unmask] = self.mask_index
+        if st["split"]:   # two passes of B rows, each on its half of the cache
+            logits, rows, n = bb.forward_masked_logits(x, sigma, modality=mod, plan_ids=x, conditioning_cache=what, cache_row0=0)
+            logits_u, _, n_u = bb.forward_masked_logits(x_uncond, sigma, modality=mod, plan_ids=x, conditioning_cache=what, cache_row0=B)
+            assert n_u == n
+        else:
+            cat2 = (lambda v: None if v is None else torch.cat([v, v], 0))
+            both, rows, n2 = bb.forward_masked_logits(torch.cat([x, x_uncond], 0), cat2(sigma), modality=cat2(mod), plan_ids=torch.cat([x, x], 0),
+                                                      conditioning_cache=what)
+            n = n2 // 2
+            logits, logits_u = both, both[n:]
+        st["built"] = True
+        if not use_w:
+            return logits[:n], rows[:n], n
+        b_of = torch.div(rows[:n], L, rounding_mode="floor")
+        w_b = w.to(torch.float32).reshape(-1)
+        w_rows = (w_b.index_select(0, b_of) if w_b.numel() == B else w_b.expand(B).index_select(0, b_of)).contiguous()
+        return logits[:n], rows[:n], n, logits_u[:n], w_rows
+
+    @staticmethod
+    def _cache_to_slice(cache, L, sl):
+        """the logits cache over [B, L] -> its rows inside positions sl, re-indexed for [B, len(sl)] (guided caches keep their second half and weights)"""
+        if cache is None:
+            return None
+        logits, rows, n = cache[:3]
+        r = rows[:n]
+        keep = ((r % L) >= sl.start) & ((r % L) < sl.stop)
+        r2 = r[keep]
+        out = (logits[:n][keep], torch.div(r2, L, rounding_mode="floor") * (sl.stop - sl.start) + r2 % L - sl.start, int(keep.sum()))
+        return out if len(cache) == 3 else out + (cache[3][:n][keep], cache[4][:n][keep])
 
     @torch.no_grad()
     def _ddpm_caching_update(self, x, t, dt, p_x0=None, x0=None, x0_unmask=None, modality=None, sample_ids=None, u=None, seed=None, **kwargs):
@@ -966,6 +1044,8 @@ class Diffusion:
         (x0 / x0_unmask conditioning kept fixed), timesteps = linspace(1, eps, steps + 1), one fused update per step with the logits
         cache reused while nothing changes, final arg-max of the log-probs (`noise_removal`).  Returns token ids [B, L]
         (and the number of backbone evaluations).  `noise`: optional list of uniforms [B, L, V] per step (replay of a recorded run)."""
+        if self.parameterization == "ar" and bool(cfg_get(cfg_get(self.config, "eval", None), "conditioning_cache", False)):
+            raise NotImplementedError("unidisc_amd.Diffusion.sample: eval.conditioning_cache with parameterization=ar - the AR sampler has its own causal KV cache")
         if self.parameterization == "ar":   # model_eval.py:2736-2822: one step per token
             if self.device.type != "cuda":
                 raise NotImplementedError("unidisc_amd.Diffusion: the AR sampler runs on the GPU only (KV-cached decoding in HIP kernels; there is no CPU path)")
@@ -1030,8 +1110,28 @@ class Diffusion:
                 self.backbone.set_flex_attention_cache(B, L, self.device, None)
         sliced, saved = False, None
         read_cache = caching and read_cache
+        # eval.conditioning_cache (extension key, default false): step 0 on the full x fills the conditioning K / V cache, every later step and the
+        # noise-removal forward run on the generated slice (x, x0, x0_unmask, modality and the logits cache sliced; written back at the end)
+        self._cond = None
+        if ev is not None and bool(cfg_get(ev, "conditioning_cache", False)):
+            self._cond = self._conditioning_setup(x0, x0_unmask, modality, sample_ids, caching, B, L)
+        cond, cond_full = self._cond, None
+
+        def cond_slice():   # once the cache is built: from here on the sampler's state is the generated slice
+            nonlocal x, x0, x0_unmask, modality, cache, cond_full
+            sl = cond["sl"]
+            cond_full = (x.clone(), x0, x0_unmask, modality)
+            cache = self._cache_to_slice(cache, L, sl)
+            x, x0, x0_unmask = x[:, sl].contiguous(), x0[:, sl].contiguous(), x0_unmask[:, sl].contiguous()
+            modality = None if cond["mod_rows"] is None else cond["mod_rows"][:, sl].contiguous()
+            cond["sliced"] = True
+
         for i in range(num_steps):
             t = timesteps[i] * torch.ones(B, 1, device=self.device)
+            if cond is not None:
+                if cond["built"] and not cond["sliced"]:
+                    cond_slice()
+                self.sample_step_modes.append("slice" if cond["sliced"] else "build")
             block_mask = None
             mc_kw = {}
             if caching:
@@ -1084,18 +1184,30 @@ class Diffusion:
             x, modality = x_full, mod_full
         if caching:
             self.backbone.reset_kv_cache()
+        if cond is not None and cond["built"] and not cond["sliced"]:
+            cond_slice()
         if noise_removal:  # x = forward(x, sigma(t_last)).argmax(-1): unmasked positions keep their token, masked ones take the best valid id
             t = timesteps[-1] * torch.ones(B, device=self.device)
             sigma_t, _ = self.noise(t)
-            logits, rows, n = self.backbone.forward_masked_logits(x, self._process_sigma(sigma_t), modality=modality, sample_ids=sample_ids)
+            if cond is not None:   # (unguided, like the line below: the conditional half of the cache alone)
+                logits, rows, n = self._cond_masked_logits(x, None, self._process_sigma(sigma_t), x0_unmask)[:3]
+            else:
+                logits, rows, n = self.backbone.forward_masked_logits(x, self._process_sigma(sigma_t), modality=modality, sample_ids=sample_ids)
             nfe += 1
             if n > 0:
                 tok = K.ddpm_sample_rows(logits[:n], self.vocab_size, self.text_vocab_size, self.mask_index,
-                                         modality=self._row_modality(rows[:n], B, L, modality), restrict=self._restrict(), greedy=True)
+                                         modality=self._row_modality(rows[:n], B, x.shape[1], modality), restrict=self._restrict(), greedy=True)
                 x = x.clone()
                 x.view(-1).index_copy_(0, rows[:n], tok)
             if x0 is not None:
                 x = torch.where(x0_unmask, x0, x)
+        if cond is not None:
+            if cond["sliced"]:   # the full tensors take the generated slice back
+                x_full, x0, x0_unmask, modality = cond_full
+                x_full[:, cond["sl"]] = x
+                x = x_full
+            self._cond = None
+            self.backbone.reset_kv_cache()
         return (x, nfe) if return_nfe else x
 
     # ---- model.py:797-1173, SUBS / continuous-time branch

@@ -244,6 +244,7 @@ class DIT(nn.Module, _HubMixin):
                                       "baseline): a bidirectional block's keys change with every new token")
         self._kv = None
         self._mc = None
+        self._cc = None
         # model.full_attention=false (models/dit.py:1118, the AR baseline of configs/experiments/ar.yaml): every block attends causally (sdpa is_causal=True,
         # :768 / :826 / :843) - the attention kernels' UDM_ATTN_CAUSAL form.  The reference never combines it with another mask: an attention_mask beside
         # is_causal is an SDPA error, and the packed / flex-mask paths sit inside `parameterization != "ar"`.
@@ -376,6 +377,7 @@ class DIT(nn.Module, _HubMixin):
     def reset_kv_cache(self, batch_size=None, seq_len=None, dtype=None, device=None, set_to_none=False, modality=None):
         self.use_flex_attention_cache = False
         self._mc = None   # the modality K / V cache of set_flex_attention_cache(read_cache=True)
+        self._cc = None   # the conditioning K / V cache of set_conditioning_cache
         if set_to_none:
             self._kv = None
             return
@@ -531,6 +533,42 @@ class DIT(nn.Module, _HubMixin):
         mc.K = [torch.zeros((B, L, self.hidden_size), dtype=BF16, device=dev) for _ in self.blocks]
         mc.V = [torch.zeros((B, L, self.hidden_size), dtype=BF16, device=dev) for _ in self.blocks]
         self._mc = mc
+
+    def set_conditioning_cache(self, batch_size, seq_len, device=None, given="text", guided=False):
+        """Conditional sampling (extension, eval.conditioning_cache): one modality of every sample - `given`, "text" = positions [:txt_length] or "image" = the rest
+        - is fixed for the whole run.  Under the ModalityMask that blinds the given modality's queries to the other modality (txt_drop = 1 / img_drop = 1) its
+        hidden states, and so its K / V in every block, are a function of its own tokens alone: constant over the run, and constant ([MASK] everywhere) in the
+        unconditional half of guided sampling.  Allocates per block bf16 K / V [R, seq_len, d] (R = 2 batch_size with `guided`: rows [0, B) the conditional half,
+        [B, 2 B) the unconditional one) and the split workspace of udm_attention_fwd_kv_split; forward_masked_logits(conditioning_cache="build") fills them with
+        one full-length forward, every conditioning_cache="read" forward then runs on the generated slice alone.  Nothing goes stale: what is cached never
+        changes.  reset_kv_cache() frees it."""
+        self._cc = None
+        name = "unidisc_amd.DIT.set_conditioning_cache"
+        if given not in ("text", "image"):
+            raise ValueError(f"{name}: given={given!r} (\"text\" or \"image\")")
+        if self.time_conditioning:
+            raise NotImplementedError(f"{name}: with time_conditioning the cached conditioning keys would depend on sigma")
+        if self.causal or self.require_sample_ids:
+            raise NotImplementedError(f"{name}: built for bidirectional backbones on unpacked batches")
+        sl = self.static_txt_sl
+        if self.txt_length <= 0 or self.img_length <= 0 or (sl is not None and ((sl.start or 0) != 0 or sl.stop != self.txt_length or sl.step not in (None, 1))):
+            raise NotImplementedError(f"{name}: the text must be the static slice [:txt_length] of the sequence "
+                                      f"(static_txt_sl = {sl}, txt_length = {self.txt_length}, img_length = {self.img_length})")
+        B, L = int(batch_size), int(seq_len)
+        if L != self.total_length:
+            raise ValueError(f"{name}: seq_len {L} is not model.length = {self.total_length}")
+        dev = torch.device(device) if device is not None else self.vocab_embed.embedding.device
+        Lt = int(self.txt_length)
+        R = 2 * B if guided else B
+        cc = types.SimpleNamespace(B=B, R=R, L=L, Lt=Lt, given=given, guided=bool(guided), built=set(), sliced={}, cos=None, sin=None, mod=None)
+        cc.sl = slice(Lt, L) if given == "text" else slice(0, Lt)      # the generated slice: what a read step runs on, and the cache slots it rewrites
+        cc.Lq = cc.sl.stop - cc.sl.start
+        cc.K = [torch.zeros((R, L, self.hidden_size), dtype=BF16, device=dev) for _ in self.blocks]
+        cc.V = [torch.zeros((R, L, self.hidden_size), dtype=BF16, device=dev) for _ in self.blocks]
+        # one workspace for the pass over all R rows and for the two passes of B rows (eval.split_cfg_batches), whose plan may split further
+        need = max(K.attention_kv_split_plan(rows, cc.Lq, L, self.n_heads, self.head_dim)[1] for rows in {R, B})
+        cc.ws = torch.empty(need, dtype=F32, device=dev) if need > 0 else None
+        self._cc = cc
 
     # -------------------------------------------------------------------------------------------- parameters / shadows
     IMG_BLOCKS = ((256, 1), (1024, 2), (2304, 3), (4096, 4))   # (tokens of an image block, Lumina linear factor), models/dit.py:1210
@@ -721,7 +759,8 @@ class DIT(nn.Module, _HubMixin):
         return _DitFn.apply(self, "logp", inputs, *params)
 
     @torch.no_grad()
-    def forward_masked_logits(self, xt, sigma=None, modality=None, sample_ids=None, plan_ids=None, block_mask=None, modality_cache=None):
+    def forward_masked_logits(self, xt, sigma=None, modality=None, sample_ids=None, plan_ids=None, block_mask=None, modality_cache=None, conditioning_cache=None,
+                              cache_row0=0):
         """Sampler path: (logits [R, Vp] bf16 of the [MASK] positions of `xt` first, then padding rows; their flat row indices [R];
         the number of [MASK] rows).  Unmasked positions keep their token under SUBS (model.py:646-656), so they need no logits.
         `plan_ids` (same shape as xt): take the row selection from the [MASK] positions of this tensor instead of xt's (guided sampling runs
@@ -730,7 +769,17 @@ class DIT(nn.Module, _HubMixin):
         ModalityMask) that also leaves every block's post-rope k and its v of all L positions in the cache; "read" - xt is the text slice [B, txt_length]: the
         backbone runs on those rows alone, with the modality ids and rotary rows of the full-length forward, writes their k / v into cache slots [0, txt_length)
         and attends to [fresh text keys ; cached image keys] (udm_attention_fwd_kv).  Under the build step's mask the image rows never see a text key, so their
-        K / V depend on the image tokens alone: a "read" step equals the text rows of the masked full-length forward on [xt ; image tokens of the build step]."""
+        K / V depend on the image tokens alone: a "read" step equals the text rows of the masked full-length forward on [xt ; image tokens of the build step].
+        `conditioning_cache` (set_conditioning_cache first; conditional sampling, see there): "build" - a full-length forward under the ModalityMask that blinds
+        the GIVEN modality's queries to the other one (built here), leaving every block's post-rope k and its v in cache rows [cache_row0, cache_row0 + rows of
+        xt); "read" - xt is the generated slice: the backbone runs on those rows alone with the modality ids and rotary rows of the build step's tables, writes
+        their k / v into the slice's cache slots and attends to all L slots (udm_attention_fwd_kv_split).  A read step equals the generated rows of that masked
+        full-length forward on [given ; xt].  `plan_ids` is accepted (the two halves of guided sampling need the same positions); xt holds either all cache rows
+        ([x ; x_uncond]) or, with cache_row0 = 0 / B, one half (eval.split_cfg_batches: two passes, each on its half of the cache)."""
+        if conditioning_cache is not None:
+            if modality_cache is not None:
+                raise ValueError("unidisc_amd.DIT.forward_masked_logits: modality_cache and conditioning_cache are two different caches - pass one")
+            return self._conditioning_forward(xt, sigma, modality, sample_ids, plan_ids, block_mask, conditioning_cache, int(cache_row0))
         inputs = dict(indices=xt, sigma=sigma, modality=modality, sample_ids=sample_ids, x0=None, save=False, plan_ids=plan_ids,
                       block_mask=block_mask if isinstance(block_mask, ModalityMask) else None)
         mc = self._mc
@@ -761,6 +810,56 @@ class DIT(nn.Module, _HubMixin):
                 inputs["modality"] = mc.mod[:, :Lt].contiguous()
             inputs["rope"] = (mc.cos[..., :Lt, :].contiguous(), mc.sin[..., :Lt, :].contiguous())
             inputs["kv_read"] = dict(K=mc.K, V=mc.V, slot0=0, Lk=mc.L)
+        out, _ = self._engine_forward(inputs, "rows", save=False)
+        return out
+
+    def _conditioning_forward(self, xt, sigma, modality, sample_ids, plan_ids, block_mask, what, row0):
+        name = f"unidisc_amd.DIT.forward_masked_logits(conditioning_cache={what!r})"
+        cc = self._cc
+        if what not in ("build", "read"):
+            raise ValueError(f"{name}: \"build\", \"read\" or None")
+        if cc is None:
+            raise RuntimeError(f"{name}: no conditioning cache - call set_conditioning_cache(B, L, device, given=..., guided=...) first")
+        if sample_ids is not None or block_mask is not None or sigma is not None and self.time_conditioning:
+            raise NotImplementedError(f"{name}: no packed sample ids, no caller's block mask (the build step makes its own), no time conditioning")
+        rows, Lx = xt.shape
+        if Lx != (cc.L if what == "build" else cc.Lq) or row0 < 0 or row0 + rows > cc.R or (rows != cc.R and (rows != cc.B or row0 % cc.B != 0)):
+            raise ValueError(f"{name}: xt {tuple(xt.shape)} at cache row {row0}; the cache serves {cc.R} rows of length {cc.L}, in passes of {cc.R} or {cc.B} rows, "
+                             f"with a generated slice of {cc.Lq} positions")
+        dev = xt.device
+        inputs = dict(indices=xt, sigma=sigma, modality=modality, sample_ids=None, x0=None, save=False, plan_ids=plan_ids, block_mask=None)
+        span = range(row0, row0 + rows)
+        if what == "build":
+            on = torch.ones(rows, dtype=torch.bool, device=dev)
+            inputs["block_mask"] = ModalityMask(on if cc.given == "text" else ~on, on if cc.given == "image" else ~on, cc.Lt)
+            inputs["kv_sink"] = [(k[row0:row0 + rows], v[row0:row0 + rows]) for k, v in zip(cc.K, cc.V)]
+            out, S = self._engine_forward(inputs, "rows", save=False)
+            cos, sin = S["cos"], S["sin"]                # [L, D/2], or per sample [rows, L, D/2]
+            if cos.dim() == 3:                           # per-sample tables: kept per cache row
+                if cc.cos is None or cc.cos.dim() != 3:
+                    cc.cos, cc.sin = cos.new_zeros((cc.R,) + tuple(cos.shape[1:])), sin.new_zeros((cc.R,) + tuple(sin.shape[1:]))
+                cc.cos[row0:row0 + rows], cc.sin[row0:row0 + rows] = cos, sin
+            else:
+                cc.cos, cc.sin = cos, sin
+            mod = modality.to(torch.int64) if modality is not None else (self._static_modality(rows, cc.L, dev) if self.modality_embed is not None else None)
+            if mod is not None:
+                if cc.mod is None:
+                    cc.mod = torch.zeros((cc.R, cc.L), dtype=torch.int64, device=dev)
+                cc.mod[row0:row0 + rows] = mod
+            cc.built.update(span)
+            cc.sliced.clear()
+            return out
+        if not set(span) <= cc.built:
+            raise RuntimeError(f"{name}: the cache holds no conditioning keys for rows [{row0}, {row0 + rows}) yet (no \"build\" step ran on them)")
+        sl = cc.sl
+        if (row0, rows) not in cc.sliced:   # row p takes exactly the modality id and the rotary row of the full-length forward (cut once: they never change)
+            pick = (lambda t: t[row0:row0 + rows, sl].contiguous()) if cc.cos.dim() == 3 else (lambda t: t[sl].contiguous())
+            cc.sliced[(row0, rows)] = (None if cc.mod is None else cc.mod[row0:row0 + rows, sl].contiguous(), pick(cc.cos), pick(cc.sin))
+        mod_sl, cos_sl, sin_sl = cc.sliced[(row0, rows)]
+        if mod_sl is not None:
+            inputs["modality"] = mod_sl
+        inputs["rope"] = (cos_sl, sin_sl)
+        inputs["kv_read"] = dict(K=[k[row0:row0 + rows] for k in cc.K], V=[v[row0:row0 + rows] for v in cc.V], slot0=sl.start, Lk=cc.L, split=True, ws=cc.ws)
         out, _ = self._engine_forward(inputs, "rows", save=False)
         return out
 
@@ -1026,7 +1125,10 @@ class DIT(nn.Module, _HubMixin):
                 s0 = kv_read["slot0"]
                 kv_read["K"][i][:, s0:s0 + L].copy_(qkr.view(B, L, 2 * d)[:, :, d:])
                 kv_read["V"][i][:, s0:s0 + L].copy_(qkv.view(B, L, 3 * d)[:, :, 2 * d:])
-                o, lse = K.attention_fwd_kv(qkr[:, :d], kv_read["K"][i], kv_read["V"][i], B, L, kv_read["Lk"], H, D, q_prescaled=True), None
+                if kv_read.get("split"):   # the conditioning cache: small batches, the keys split over workgroups where the plan says so
+                    o, lse = K.attention_fwd_kv_split(qkr[:, :d], kv_read["K"][i], kv_read["V"][i], B, L, kv_read["Lk"], H, D, q_prescaled=True, ws=kv_read["ws"]), None
+                else:
+                    o, lse = K.attention_fwd_kv(qkr[:, :d], kv_read["K"][i], kv_read["V"][i], B, L, kv_read["Lk"], H, D, q_prescaled=True), None
             else:
                 o, lse = K.attention_fwd(qkr, qkv, B, L, H, D, sid, S["doc_ranges"], q_prescaled=True, **self._attn_mask_kw, **S["attn_drop_kw"](i))
             rows_c = last_rows

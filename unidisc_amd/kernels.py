@@ -855,6 +855,41 @@ def attention_fwd_kv(q, k_cache, v_cache, B, Lq, Lk, H, D, q_prescaled=False, ou
     return (out, lse) if want_lse else out
 
 
+def attention_kv_split_plan(B, Lq, Lk, H, D, splits=0):
+    """(S, workspace floats) a K.attention_fwd_kv_split call of this shape runs with: splits = 0 asks the plan (csrc/attention_plan.h, for the current device),
+    splits >= 1 forces a count; either is lowered to the key tiles and to 32."""
+    import ctypes
+    s, n = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.call("udm_attention_kv_split_plan", B, H, Lq, Lk, D, int(splits), ctypes.byref(s), ctypes.byref(n))
+    return int(s.value), int(n.value)
+
+
+def attention_kv_split_ws(B, Lq, Lk, H, D, device, splits=0):
+    """fp32 split scratch of udm_attention_fwd_kv_split: (D + 2) floats per (split, sample, head, query row) for the split count of
+    attention_kv_split_plan; None when that is one split (the call then needs no workspace)."""
+    _, n = attention_kv_split_plan(B, Lq, Lk, H, D, splits)
+    return torch.empty(n, dtype=F32, device=device) if n > 0 else None
+
+
+def attention_fwd_kv_split(q, k_cache, v_cache, B, Lq, Lk, H, D, q_prescaled=False, out=None, want_lse=False, ws=None, splits=0):
+    """K.attention_fwd_kv with the keys split over workgroups (udm_attention_fwd_kv_split): for small batches, whose unsplit grid leaves CUs idle.
+    ws: the fp32 scratch of attention_kv_split_ws (None: one split, the unsplit kernel); splits: 0 = the plan decides, >= 1 forces a count (lowered to the
+    key tiles, to 32 and to what ws holds)."""
+    d = H * D
+    Bc, Lmax, dc = k_cache.shape
+    if Bc < B or dc != d or Lk > Lmax or tuple(v_cache.shape) != tuple(k_cache.shape) or k_cache.stride(2) != 1 or v_cache.stride(2) != 1 or q.stride(1) != 1:
+        raise ValueError(f"attention_fwd_kv_split: cache {tuple(k_cache.shape)} / {tuple(v_cache.shape)} does not serve B={B}, Lk={Lk}, H D={d}")
+    if ws is not None and (ws.dtype != F32 or not ws.is_contiguous()):
+        raise ValueError("attention_fwd_kv_split: ws must be a contiguous fp32 tensor (attention_kv_split_ws)")
+    if out is None:
+        out = torch.empty((B * Lq, d), dtype=BF16, device=q.device)
+    lse = torch.empty((B, H, Lq), dtype=F32, device=q.device) if want_lse else None
+    _lib.call("udm_attention_fwd_kv_split", _p(q), _p(k_cache), _p(v_cache), _p(out), _p(lse), B, H, Lq, Lk, D, q.stride(0), k_cache.stride(1), v_cache.stride(1),
+              out.stride(0), Lq * q.stride(0), k_cache.stride(0), v_cache.stride(0), Lq * out.stride(0), _p(ws), ws.numel() if ws is not None else 0, int(splits),
+              _attn_flags(q_prescaled, False), _s())
+    return (out, lse) if want_lse else out
+
+
 def attention_bwd(qkr, qkv, o, do, lse, dqkr, dqkv, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False, causal=False, dropout_p=0.0, seed=0):
     """Writes dq|dk (wrt the stored rotated q, k) into dqkr [M,2d] and dv into dqkv[:, 2d:3d].  dropout_p, seed: those of the forward."""
     d = H * D
