@@ -254,6 +254,7 @@ NT_STAGGER = [(333, 260, 128), (700, 1001, 192)]
 NT_PERSIST = [(4352, 4096, 128), (4352, 4096, 192)]
 NT_PERSIST_320 = (5440, 4096, 128)
 NT_QUAD = [(M, N, K) for M in (192, 256, 320) for N in (256, 512) for K in (128, 192, 448)]
+NT_QUAD_ASM = [(M, N, 256) for M in (256, 320) for N in (256, 512)]    # 4 K tiles: the smallest count the generated asm K loop takes (fm = 4, 5)
 NT_QUAD_RAGGED = (5000, 2048, 128)
 NT_QUAD_RAGGED_320 = (8200, 2048, 128)                                # (the tile chooser picks 320-row tiles for this one)
 NN = [(192, 256, 128), (320, 256, 256), (768, 256, 1024), (5000, 2048, 128)]
@@ -271,7 +272,7 @@ SMALL_BATCH = [(5, 100, 32), (8, 12288, 128)]                         # (B, out,
 
 def all_mnk():
     """every (M, N, K) product the GPU suite draws"""
-    s = list(NT_SMALL) + list(NT_STAGGER) + list(NT_PERSIST) + [NT_PERSIST_320] + list(NT_QUAD) + [NT_QUAD_RAGGED, NT_QUAD_RAGGED_320] + list(NN)
+    s = list(NT_SMALL) + list(NT_STAGGER) + list(NT_PERSIST) + [NT_PERSIST_320] + list(NT_QUAD) + list(NT_QUAD_ASM) + [NT_QUAD_RAGGED, NT_QUAD_RAGGED_320] + list(NN)
     s += [(M, N, Kc) for Kc, M, N in TN + TN_QUAD + TN_SPLITK]
     s += [(TN_PAIR[0], TN_PAIR[2], TN_PAIR[3]), (TN_PAIR[1], TN_PAIR[2], TN_PAIR[3])] + [(M, N, TN_MULTI[1]) for M, N in TN_MULTI[0]]
     s += list(NT_SPLITK) + [NT_SPLITK_SLICE[:3]] + [(M, N, K) for M in SKINNY_M for N, K in SKINNY_NK]

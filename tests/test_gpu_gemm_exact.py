@@ -177,7 +177,7 @@ def nt_case(K, rep, M, N, Kd, variant, *, narrow=False):
 @pytest.mark.parametrize("variant", VARIANTS)
 @pytest.mark.parametrize("M,N,Kd", R.NT_SMALL)
 def test_nt_small_kernel(K, M, N, Kd, variant):
-    """128 x 128 register-staged kernel: every shape here has M < 192, or N < 192, or K % 64 != 0, or K < 128 (choose_tile returns 0).  K tails of 8
+    """128 x 128 register-staged kernel: every shape here has M < 192, or N < 192, or K % 64 != 0, or K < 128 (gemm_choose_tile of csrc/gemm_plan.h returns 0).  K tails of 8
     (K = 72, 2056, 8: K % 64 == 8) with NaN right behind K; M, N ragged against the 128-wide tile ((129, 129): one row / column in the second tile)."""
     rep = Report("nt 128x128", (M, N, Kd))
     nt_case(K, rep, M, N, Kd, variant)
@@ -196,7 +196,7 @@ def test_nt_small_kernel_narrow_ldc(K, variant):
 @pytest.mark.parametrize("M,N,Kd", R.NT_STAGGER)
 def test_nt_stagger_kernels(K, tile, M, N, Kd):
     """LDS-DMA stagger kernels forced per tile family (gemm_set_tile; 0 = the 128 x 128 kernel on a shape it would not get by itself): K % 64 == 0 and
-    K >= 128, so choose_tile obeys the forced tile; ragged M and N in the last tile row / column; two and three K tiles; fewer than 256 tiles: one block per tile."""
+    K >= 128, so gemm_choose_tile obeys the forced tile; ragged M and N in the last tile row / column; two and three K tiles; fewer than 256 tiles: one block per tile."""
     rep = Report(f"nt stagger tile {tile}", (M, N, Kd))
     K.gemm_set_tile(tile)
     try:
@@ -211,7 +211,7 @@ def test_nt_stagger_kernels(K, tile, M, N, Kd):
 @pytest.mark.parametrize("tile,M,N,Kd", [(256,) + s for s in R.NT_PERSIST] + [(320,) + R.NT_PERSIST_320])
 def test_nt_persistent_wide(K, tile, M, N, Kd, persist):
     """Persistent wide form: 17 x 16 = 272 whole tiles (> 256), M % tile == 0, N % 256 == 0, K / 64 >= 2, ldc % 8 == 0, ldaux % 8 == 0
-    (persistent_wide_ok), even and odd K-tile counts.  The tile is forced: choose_tile by itself prefers one ragged round of 320-row tiles at M = 4352.
+    (gemm_persistent_wide_ok), even and odd K-tile counts.  The tile is forced: gemm_choose_tile by itself prefers one ragged round of 320-row tiles at M = 4352.
     persist = 0: the same shapes with one block per tile (gemm_set_persist)."""
     rep = Report(f"nt tile {tile} " + ("persistent" if persist else "one block per tile"), (M, N, Kd))
     K.gemm_set_tile(tile)
@@ -228,13 +228,15 @@ def test_nt_persistent_wide(K, tile, M, N, Kd, persist):
 @pytest.mark.parametrize("asm", [1, 0])
 @pytest.mark.parametrize("M,N", [(M, N) for M in (192, 256, 320) for N in (256, 512)])
 def test_nt_quad_one_wave_per_simd(K, M, N, asm):
-    """One-wave-per-SIMD kernel under gemm_set_quad(2): M = 192 / 256 / 320 is exactly one tile row of fm = 3 / 4 / 5 (udm_quad_nt_ok: N % 256 == 0,
-    K % 64 == 0, K >= 128; 320 is no multiple of 192 or 256, 256 none of 192), K tiles 2 / 3 / 7; generated asm K loop on and off."""
+    """One-wave-per-SIMD kernel under gemm_set_quad(2): M = 192 / 256 / 320 is exactly one tile row of fm = 3 / 4 / 5 (gemm_quad_whole_fm: N % 256 == 0,
+    K % 64 == 0, K >= 128; 320 is no multiple of 192 or 256, 256 none of 192), K tiles 2 / 3 / 7 - which all run the C++ K loop whatever `asm` says: the
+    generated asm loop is taken for at least 4 K tiles and an even count, on the 256- and 320-row tiles.  K = 256 (R.NT_QUAD_ASM: 4 K tiles, the smallest count
+    it takes) is where asm = 1 and asm = 0 differ (tests/test_gemm_plan.py lists the plan of every case here)."""
     rep = Report(f"nt quad asm={asm}", (M, N))
     K.gemm_set_quad(2)
     K.debug_set("gemm_quad_asm", asm)
     try:
-        for Kd in (128, 192, 448):
+        for Kd in (128, 192, 448) + tuple(k for m, n, k in R.NT_QUAD_ASM if (m, n) == (M, N)):
             rep.shape = f"{M}x{N}x{Kd}"
             for variant in ("none_bf16", "bias_bf16", "none_f32"):
                 nt_case(K, rep, M, N, Kd, variant)
@@ -246,9 +248,9 @@ def test_nt_quad_one_wave_per_simd(K, M, N, asm):
 
 @pytest.mark.parametrize("M,N,Kd", [R.NT_QUAD_RAGGED, R.NT_QUAD_RAGGED_320])
 def test_nt_quad_ragged_last_tile_row(K, M, N, Kd):
-    """Ragged 320-row tiles (fm = -5): udm_gemm_nt_bf16 takes them when choose_tile picks 320 for one round of 128..256 tiles with M % 320 != 0.
+    """Ragged 320-row tiles (fm = -5): udm_gemm_nt_bf16 takes them when gemm_choose_tile picks 320 for one round of 128..256 tiles with M % 320 != 0.
     (8200, 2048, 128): 26 x 8 = 208 tiles in one round where 192- / 256-row tiles need two -> the ragged form; the rows behind M are guard rows.
-    (5000, 2048, 128): choose_tile prefers one round of 192-row tiles (27 x 8 = 216), so NT runs the ragged 8-wave kernel there; gemm_nn (test_nn) is where
+    (5000, 2048, 128): gemm_choose_tile prefers one round of 192-row tiles (27 x 8 = 216), so NT runs the ragged 8-wave kernel there; gemm_nn (test_nn) is where
     this shape takes fm = -5."""
     rep = Report("nt ragged 320-row tiles", (M, N, Kd))
     K.gemm_set_quad(2)
@@ -311,7 +313,7 @@ def test_tn(K, Kc, M, N, beta):
 @pytest.mark.parametrize("beta", [0, 1])
 @pytest.mark.parametrize("Kc,M,N", R.TN_QUAD)
 def test_tn_quad(K, Kc, M, N, beta):
-    """gemm_tn on the one-wave-per-SIMD K-major kernel under gemm_set_quad(2): M = 192 -> fm = 3, M = 256 -> fm = 4 (udm_quad_tn_ok has no 320-row tile)"""
+    """gemm_tn on the one-wave-per-SIMD K-major kernel under gemm_set_quad(2): M = 192 -> fm = 3, M = 256 -> fm = 4 (gemm_quad_whole_fm with fm_max = 4: the K-major form has no 320-row tile)"""
     rep = Report("tn quad", (Kc, M, N))
     K.gemm_set_quad(2)
     try:

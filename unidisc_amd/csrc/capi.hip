@@ -26,6 +26,7 @@ extern "C" int udm_abi_version(void) { return UDM_ABI_VERSION; }
 extern "C" __attribute__((visibility("hidden"))) int udm_gemm_set_tile(int tile);      // gemm.hip: force the tile family (-1 auto, 0 = 128x128 kernel, 192 / 256 / 320 = BM x 256 kernel)
 extern "C" __attribute__((visibility("hidden"))) int udm_gemm_set_quad(int mode);      // gemm.hip: one-wave-per-SIMD kernels 0 = off, 1 = auto (default; env UDM_GEMM_QUAD), 2 = wherever the shape fits
 extern "C" __attribute__((visibility("hidden"))) int udm_gemm_set_persist(int enable); // gemm.hip: 0 = one block per output tile (default 1: persistent blocks for multi-round NT shapes)
+extern "C" __attribute__((visibility("hidden"))) int udm_gemm_set_quad_asm(int mode); // gemm.hip: the generated asm K loop of the one-wave-per-SIMD NT kernels
 extern "C" __attribute__((visibility("hidden"))) int udm_attention_debug_set(const char* key, int64_t value);   // attention.hip: every "attention_*" key (1 = not one of them)
 
 namespace { int g_exp = [] { const char* e = getenv("UDM_EXP"); return e ? atoi(e) : 0; }(); }
@@ -39,7 +40,7 @@ extern "C" int udm_debug_set(const char* key, int64_t value) {
   if (is("gemm_quad")) return udm_gemm_set_quad((int)value);
   if (is("gemm_persist")) return udm_gemm_set_persist((int)value);
   if (is("gemm_quad_timeline")) { g_quad_timeline = reinterpret_cast<unsigned*>(value); return 0; }
-  if (is("gemm_quad_asm")) { g_quad_asm = (int)value; return 0; }   // 0 = the C++ K loop of gemm_quad.hip everywhere, 1 = the generated asm loop where it exists, -1 = env
+  if (is("gemm_quad_asm")) return udm_gemm_set_quad_asm((int)value);   // 0 = the C++ K loop of gemm_quad.hip everywhere, 1 = the generated asm loop where it exists, -1 = env
   if (udm_attention_debug_set(key, value) == 0) return 0;
   udm_set_error("udm_debug_set: unknown key '%s'", key);
   return 2;

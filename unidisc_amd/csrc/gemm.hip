@@ -11,7 +11,6 @@
 // through LDS so the epilogue (bias / GELU / GELU' / accumulate) runs on coalesced 16-byte rows.
 // Tile order is XCD-aware (8 private L2s) with a grouped-M sweep.
 #include "common.h"
-#include <algorithm>
 #include "gemm_quad.h"
 #include "../../include/unidisc_hip.h"
 
@@ -805,46 +804,35 @@ __global__ __launch_bounds__(512) void gemm_nt_stagger_kernel(GemmArgs p) {
 
 #undef ROT_A
 #undef ROT_B
-int g_gemm_persist = 1;   // diagnostics (UDM_GEMM_PERSIST=0): 0 = one block per output tile everywhere
-// Data-parallel runs: the persistent blocks of a multi-round NT GEMM occupy every CU for the whole launch, and RCCL's channel kernels (the
-// gradient all-reduce overlapped with backward) then only get CUs between launches.  UDM_GEMM_CUS = n (or udm_gemm_set_cus) caps the
-// persistent grid at n blocks (a multiple of 8: one block per CU, XCD round-robin), leaving 256 - n CUs to the collective.  0 = all 256.
-int g_gemm_cus = 0;
-int gemm_cus_available() {   // (also reached from gemm_quad.hip through udm_gemm_cus_available below)
-  static const bool env_once = [] {
-    if (const char* e = getenv("UDM_GEMM_CUS")) { const int n = atoi(e); if (n >= 8 && n <= 256) g_gemm_cus = n / 8 * 8; }
-    return true;
-  }();
-  (void)env_once;
-  return g_gemm_cus ? g_gemm_cus : 256;
+// THE process-wide switches of the GEMM plans (gemm_plan.h: GemmEnv).  The environment is read here, once, and nowhere else; the setters at the end of this file
+// write into gemm_env().  UDM_GEMM_CUS: the persistent blocks of a multi-round NT GEMM occupy every CU for the whole launch, and RCCL's channel kernels (the
+// gradient all-reduce overlapped with backward) then only get CUs between launches; a cap of n (a multiple of 8: one block per CU, XCD round-robin) leaves
+// 256 - n CUs to the collective.
+GemmEnv gemm_env_from_environment() {
+  const auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+  GemmEnv e;
+  const int cus = num("UDM_GEMM_CUS", 0);
+  if (cus >= 8 && cus <= 256) e.cus = cus / 8 * 8;
+  e.quad = num("UDM_GEMM_QUAD", 1);
+  e.persist = num("UDM_GEMM_PERSIST", 1);
+  e.ragged = num("UDM_QUAD_RAGGED", 1);        // diagnostics: 0 = whole quad tiles only
+  e.quad_asm = num("UDM_QUAD_ASM", 1);
+  e.group_m = num("UDM_GEMM_GROUP_M", 0);
+  return e;
 }
+const GemmEnv& gemm_env_default() { static const GemmEnv e = gemm_env_from_environment(); return e; }
+GemmEnv& gemm_env() { static GemmEnv e = gemm_env_default(); return e; }
 
-int g_gemm_persist_fwd() {   // the persistent-form switch with its environment default applied (UDM_GEMM_PERSIST, read once)
-  static const bool env_once = [] {
-    if (const char* e = getenv("UDM_GEMM_PERSIST")) g_gemm_persist = atoi(e);
-    return true;
-  }();
-  (void)env_once;
-  return g_gemm_persist;
-}
-// Does this launch take the persistent wide form (256 blocks walking whole tiles, 16-byte epilogue accesses)?
-template <int BMX, int EPI, bool OUT_F32>
-bool persistent_wide_ok(const GemmArgs& a) {
-  if (BMX < 256) return false;
-  const bool aux_ok = EPI < UDM_EPI_BIAS_GELU || a.ldaux % 8 == 0;
-  return g_gemm_persist_fwd() && a.splitk <= 1 && (long)((a.M + BMX - 1) / BMX) * ((a.N + 255) / 256) > 256 && a.M % BMX == 0 && a.N % 256 == 0 && a.K / BK >= 2 &&
-         (!UDM_EPI_WIDE || ((OUT_F32 ? a.ldc % 4 == 0 : a.ldc % 8 == 0) && aux_ok));
-}
-
+// the 8-wave kernel a plan names: GEMM_STAGGER (one block per tile and slice) or GEMM_PERSIST (plan.grid blocks walking whole tiles; NT, 256- / 320-row tiles)
 template <int BMX, int EPI, bool OUT_F32, bool TN = false>
-int launch_big_t(const GemmArgs& a0, hipStream_t stream) {
+int launch_big_t(const GemmArgs& a0, const GemmPlan& p, hipStream_t stream) {
   GemmArgs a = a0;
-  a.tiles_m = (a.M + BMX - 1) / BMX;
-  a.tiles_n = (a.N + 255) / 256;
-  static const int env_gm = [] { const char* e = getenv("UDM_GEMM_GROUP_M"); return e ? atoi(e) : 0; }();
-  a.group_m = env_gm;
+  a.tiles_m = p.tiles_m;
+  a.tiles_n = p.tiles_n;
+  a.group_m = p.group_m;
+  a.splitk = p.splitk;
   a.exp = udm_exp_flags();
-  const size_t lds = (size_t)2 * (BMX + 256) * BK * 2;
+  const size_t lds = p.lds_bytes;
   auto kern = gemm_nt_stagger_kernel<BMX, EPI, OUT_F32, TN>;
   static bool attr_set = false;
   if (!attr_set) {
@@ -852,76 +840,61 @@ int launch_big_t(const GemmArgs& a0, hipStream_t stream) {
     attr_set = true;
   }
   if constexpr (!TN && BMX >= 256) {
-    // more than one round of whole tiles: 256 persistent blocks walk them (see PERSIST above)
-    (void)gemm_cus_available();   // (applies UDM_GEMM_CUS once)
-    if (persistent_wide_ok<BMX, EPI, OUT_F32>(a)) {
+    if (p.family == GEMM_PERSIST) {   // more than one round of whole tiles (see PERSIST above)
       auto kp = gemm_nt_stagger_kernel<BMX, EPI, OUT_F32, false, 1, true>;
       static bool attr_p = false;
       if (!attr_p) {
         (void)hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_p = true;
       }
-      hipLaunchKernelGGL(kp, dim3(g_gemm_cus ? g_gemm_cus : 256), dim3(512), lds, stream, a);
+      hipLaunchKernelGGL(kp, dim3(p.grid), dim3(512), lds, stream, a);
       UDM_CHECK_LAUNCH("udm_gemm_nt_bf16(big, persistent)");
       return 0;
     }
   }
-  hipLaunchKernelGGL(kern, dim3(a.tiles_m * a.tiles_n * (a.splitk > 1 ? a.splitk : 1)), dim3(512), lds, stream, a);
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(512), lds, stream, a);
   UDM_CHECK_LAUNCH("udm_gemm_nt_bf16(big)");
   return 0;
 }
 template <int BMX>
-int launch_big(const GemmArgs& a, int epi, int out_f32, hipStream_t stream) {
+int launch_big(const GemmArgs& a, const GemmPlan& p, int epi, int out_f32, hipStream_t stream) {
   switch (epi) {
-    case UDM_EPI_NONE: return out_f32 ? launch_big_t<BMX, UDM_EPI_NONE, true>(a, stream) : launch_big_t<BMX, UDM_EPI_NONE, false>(a, stream);
-    case UDM_EPI_BIAS: return out_f32 ? launch_big_t<BMX, UDM_EPI_BIAS, true>(a, stream) : launch_big_t<BMX, UDM_EPI_BIAS, false>(a, stream);
-    case UDM_EPI_BIAS_GELU: return launch_big_t<BMX, UDM_EPI_BIAS_GELU, false>(a, stream);
-    default: return out_f32 ? launch_big_t<BMX, UDM_EPI_DGELU, true>(a, stream) : launch_big_t<BMX, UDM_EPI_DGELU, false>(a, stream);
+    case UDM_EPI_NONE: return out_f32 ? launch_big_t<BMX, UDM_EPI_NONE, true>(a, p, stream) : launch_big_t<BMX, UDM_EPI_NONE, false>(a, p, stream);
+    case UDM_EPI_BIAS: return out_f32 ? launch_big_t<BMX, UDM_EPI_BIAS, true>(a, p, stream) : launch_big_t<BMX, UDM_EPI_BIAS, false>(a, p, stream);
+    case UDM_EPI_BIAS_GELU: return launch_big_t<BMX, UDM_EPI_BIAS_GELU, false>(a, p, stream);
+    default: return out_f32 ? launch_big_t<BMX, UDM_EPI_DGELU, true>(a, p, stream) : launch_big_t<BMX, UDM_EPI_DGELU, false>(a, p, stream);
   }
-}
-
-// Pick the tile whose tile count wastes the least of the 256-CU rounds.  Returns 0 for the 128x128 kernel.
-int g_force_tile = -1;  // diagnostics (udm_gemm_set_tile): -1 auto, 0 small kernel, 192/256/320
-int choose_tile(long M, long N, long K, long lda, long ldb) {
-  if (K % 64 != 0 || K < 128) return 0;  // the LDS-DMA path has no K-tail handling: such shapes take the register-staged kernel
-  if (g_force_tile >= 0) return g_force_tile;
-  if (M < 192 || N < 192) return 0;
-  const double eff[4] = {0.74, 0.93, 1.0, 1.0};  // measured relative throughput of {128x128, 192, 256, 320} x 256 tiles at full occupancy
-  const int bms[4] = {128, 192, 256, 320};
-  double best = 1e30;
-  int pick = 0;
-  for (int c = 0; c < 4; ++c) {
-    const long tm = (M + bms[c] - 1) / bms[c];
-    const long tn = c == 0 ? (N + 127) / 128 : (N + 255) / 256;
-    const long slots = c == 0 ? 512 : 256;  // co-resident blocks on the chip
-    const long rounds = (tm * tn + slots - 1) / slots;
-    double t = rounds * (double)bms[c] * (c == 0 ? 128 : 256) * (c == 0 ? 2.0 : 1.0) / eff[c];  // time ~ rounds x tile area (2 blocks/CU share a CU)
-    // short contractions (UniDisc-S: K = 768, 12 K tiles per output tile): prologue and epilogue are a large part of a tile, and only the persistent
-    // form (256- / 320-row tiles, whole tiles, more than one round) overlaps the next tile's first loads with them.  Measured at M = 24576
-    // (scripts/bench_gemm_s.py): N = 3072 + GELU 162 us persistent 256 vs 178 (192) / 194 (320, ragged); + GELU' 166 vs 187 / 228; N = 2304 plain 111 vs 120 / 114.
-    const bool persistent = c >= 2 && M % bms[c] == 0 && N % 256 == 0 && tm * tn > 256;
-    if (K <= 1024 && !persistent) t *= 1.15;
-    // ... and at any K the persistent form (next tile's first loads under the epilogue, wide epilogue) is worth ~10 % of a launch: M = 9216 (config E), K = 2048,
-    // N = 8192 + GELU: 293 us as 5 rounds of persistent 256-row tiles against 313 us as 6 rounds of 192-row tiles (GELU' + column sums 290 vs 316); N = 6144 plain:
-    // 207 us (4 rounds of 256) against 217 (3 rounds of ragged 320) - scripts/bench_gemm_epi.py with M / N / TILE from the environment
-    static const int env_pb = [] { const char* e = getenv("UDM_GEMM_PERSIST_BONUS"); return e ? atoi(e) : 1; }();   // diagnostics: 0 = the round-2 cost model
-    if (persistent && env_pb) t *= 0.90;
-    if (t < best || (t == best && c > 0)) { best = t; pick = c == 0 ? 0 : bms[c]; }  // ties go to the larger tile (fewer operand re-reads)
-  }
-  return pick;
 }
 
 template <int EPI>
-int launch_gemm(const GemmArgs& a, int out_f32, hipStream_t stream) {
-  dim3 grid(a.tiles_m * a.tiles_n), block(NTHREADS);
-  const size_t lds = 4 * TILE_BYTES;
+int launch_gemm(const GemmArgs& a0, const GemmPlan& p, int out_f32, hipStream_t stream) {
+  GemmArgs a = a0;
+  a.tiles_m = p.tiles_m;
+  a.tiles_n = p.tiles_n;
   if (out_f32)
-    hipLaunchKernelGGL((gemm_nt_kernel<EPI, true>), grid, block, lds, stream, a);
+    hipLaunchKernelGGL((gemm_nt_kernel<EPI, true>), dim3(p.grid), dim3(NTHREADS), p.lds_bytes, stream, a);
   else
-    hipLaunchKernelGGL((gemm_nt_kernel<EPI, false>), grid, block, lds, stream, a);
+    hipLaunchKernelGGL((gemm_nt_kernel<EPI, false>), dim3(p.grid), dim3(NTHREADS), p.lds_bytes, stream, a);
   UDM_CHECK_LAUNCH("udm_gemm_nt_bf16");
   return 0;
 }
+
+GemmArgs gemm_args(const void* A, const void* B, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, float beta) {
+  GemmArgs a;
+  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = C; a.bias = nullptr; a.aux = nullptr;
+  a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldaux = 0;
+  a.M = (int)M; a.N = (int)N; a.K = (int)K; a.beta = beta;
+  a.splitk = 1;
+  a.slice_stride = 0;
+  return a;
+}
+QuadArgs quad_args(const void* A, const void* B, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, float beta) {
+  QuadArgs q{};
+  q.A = (const bf16_t*)A; q.B = (const bf16_t*)B; q.C = C; q.lda = lda; q.ldb = ldb; q.ldc = ldc;
+  q.M = (int)M; q.N = (int)N; q.K = (int)K; q.beta = beta; q.splitk = 1;
+  return q;
+}
+bool is_quad(const GemmPlan& p) { return p.family == GEMM_QUAD || p.family == GEMM_QUAD_RAGGED; }
 }  // namespace
 
 extern "C" int udm_gemm_nt_bf16(const void* A, const void* B, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
@@ -933,66 +906,29 @@ extern "C" int udm_gemm_nt_bf16(const void* A, const void* B, void* C, int64_t M
   UDM_CHECK_ARG(((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && ((uintptr_t)C % 16 == 0), "udm_gemm_nt_bf16: operands must be 16-byte aligned");
   UDM_CHECK_ARG(beta == 0.f || out_f32, "udm_gemm_nt_bf16: beta accumulate needs fp32 output");
   UDM_CHECK_ARG(M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "udm_gemm_nt_bf16: dimension too large");
-  GemmArgs a;
-  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = C; a.bias = bias; a.aux = (bf16_t*)aux;
-  a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldaux = ldaux;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.tiles_m = (int)((M + BM - 1) / BM); a.tiles_n = (int)((N + BN - 1) / BN);
-  a.beta = beta;
-  a.splitk = 1;
-  a.slice_stride = 0;
+  UDM_CHECK_ARG(epilogue >= 0 && epilogue <= 3, "udm_gemm_nt_bf16: unknown epilogue %d", epilogue);
   if (epilogue == UDM_EPI_BIAS || epilogue == UDM_EPI_BIAS_GELU) UDM_CHECK_ARG(bias, "udm_gemm_nt_bf16: bias epilogue without bias");
   if (epilogue == UDM_EPI_BIAS_GELU) UDM_CHECK_ARG(aux && !out_f32, "udm_gemm_nt_bf16: EPI_BIAS_GELU needs aux and bf16 output");
   if (epilogue == UDM_EPI_DGELU) UDM_CHECK_ARG(aux, "udm_gemm_nt_bf16: EPI_DGELU needs aux (the saved GELU derivative)");
-  UDM_CHECK_ARG(epilogue >= 0 && epilogue <= 3, "udm_gemm_nt_bf16: unknown epilogue %d", epilogue);
-  {  // whole tiles: the one-wave-per-SIMD kernel (gemm_quad.hip) where its tile count fills rounds of the chip at least as well
-    int fm = 0;
-    if (g_force_tile < 0 && (beta == 0.f) && udm_quad_nt_ok(M, N, K, &fm)) {
-      const long qt = (M / (64 * fm)) * (N / 256);
-      const int t8 = choose_tile(M, N, K, lda, ldb);
-      const long t8n = t8 ? ((M + t8 - 1) / t8) * ((N + 255) / 256) : 0;
-      const double q_cost = (double)((qt + 255) / 256) * 64 * fm, o_cost = t8 ? (double)((t8n + 255) / 256) * t8 : 1e30;
-      // measured (scripts/bench_gemm_quad.py, 1.4 B shapes, random operands): the quad kernel wins 1-3 % on single-round shapes with a plain or
-      // bias epilogue and loses 3 % where the GELU / GELU' epilogue runs (one wave per SIMD has nothing to overlap its VALU with);
-      // multi-round shapes stay with the persistent 8-wave blocks
-      if (udm_quad_mode() == 2 || (qt >= 128 && qt <= 256 && q_cost <= o_cost && epilogue <= UDM_EPI_BIAS)) {
-        QuadArgs q{};
-        q.A = a.A; q.B = a.B; q.C = C; q.bias = bias; q.aux = (bf16_t*)aux; q.lda = lda; q.ldb = ldb; q.ldc = ldc; q.ldaux = ldaux;
-        q.M = a.M; q.N = a.N; q.K = a.K; q.beta = 0.f; q.splitk = 1;
-        if (ldc % 4 == 0 && (epilogue < UDM_EPI_BIAS_GELU || ldaux % 4 == 0) && !(out_f32 && epilogue != UDM_EPI_NONE))
-          return udm_quad_launch_nt(q, fm, epilogue, out_f32, stream);
-      }
-    }
+  const GemmPlan p = gemm_plan_nt(M, N, K, ldc, ldaux, epilogue, out_f32 != 0, beta != 0.f, gemm_env(), UDM_EPI_WIDE);
+  if (is_quad(p)) {
+    QuadArgs q = quad_args(A, B, C, M, N, K, lda, ldb, ldc, 0.f);
+    q.bias = bias; q.aux = (bf16_t*)aux; q.ldaux = ldaux;
+    return udm_quad_launch(q, p, QUAD_NT, epilogue, out_f32, stream);
   }
-  {  // one round of 320-row tiles with a ragged last tile row (config E: M = 9216, N = 2048): the one-wave-per-SIMD kernel's ragged form instead of the 8-wave one
-    int fm = 0;
-    const long rt = ((M + 319) / 320) * ((N + 255) / 256);
-    if (g_force_tile < 0 && beta == 0.f && !out_f32 && epilogue <= UDM_EPI_BIAS && M % 320 != 0 && N % 256 == 0 && rt >= 128 && rt <= 256 && ldc % 4 == 0 &&
-        choose_tile(M, N, K, lda, ldb) == 320 && udm_quad_nn_ok(M, N, K, &fm) && fm == -5) {
-      QuadArgs q{};
-      q.A = a.A; q.B = a.B; q.C = C; q.bias = bias; q.lda = lda; q.ldb = ldb; q.ldc = ldc;
-      q.M = a.M; q.N = a.N; q.K = a.K; q.beta = 0.f; q.splitk = 1;
-      return udm_quad_launch_nt(q, -5, epilogue, 0, stream);
-    }
-  }
-  switch (choose_tile(M, N, K, lda, ldb)) {
-    case 192: return launch_big<192>(a, epilogue, out_f32, stream);
-    case 256: return launch_big<256>(a, epilogue, out_f32, stream);
-    case 320: return launch_big<320>(a, epilogue, out_f32, stream);
+  GemmArgs a = gemm_args(A, B, C, M, N, K, lda, ldb, ldc, beta);
+  a.bias = bias; a.aux = (bf16_t*)aux; a.ldaux = ldaux;
+  switch (p.family == GEMM_SMALL ? 0 : p.tile_rows) {
+    case 192: return launch_big<192>(a, p, epilogue, out_f32, stream);
+    case 256: return launch_big<256>(a, p, epilogue, out_f32, stream);
+    case 320: return launch_big<320>(a, p, epilogue, out_f32, stream);
     default: break;
   }
   switch (epilogue) {
-    case UDM_EPI_NONE: return launch_gemm<UDM_EPI_NONE>(a, out_f32, stream);
-    case UDM_EPI_BIAS:
-      UDM_CHECK_ARG(bias, "udm_gemm_nt_bf16: EPI_BIAS without bias");
-      return launch_gemm<UDM_EPI_BIAS>(a, out_f32, stream);
-    case UDM_EPI_BIAS_GELU:
-      UDM_CHECK_ARG(bias && aux && !out_f32, "udm_gemm_nt_bf16: EPI_BIAS_GELU needs bias, aux and bf16 output");
-      return launch_gemm<UDM_EPI_BIAS_GELU>(a, out_f32, stream);
-    case UDM_EPI_DGELU:
-      UDM_CHECK_ARG(aux, "udm_gemm_nt_bf16: EPI_DGELU needs aux (the saved GELU derivative)");
-      return launch_gemm<UDM_EPI_DGELU>(a, out_f32, stream);
-    default: udm_set_error("udm_gemm_nt_bf16: unknown epilogue %d", epilogue); return 2;
+    case UDM_EPI_NONE: return launch_gemm<UDM_EPI_NONE>(a, p, out_f32, stream);
+    case UDM_EPI_BIAS: return launch_gemm<UDM_EPI_BIAS>(a, p, out_f32, stream);
+    case UDM_EPI_BIAS_GELU: return launch_gemm<UDM_EPI_BIAS_GELU>(a, p, out_f32, stream);
+    default: return launch_gemm<UDM_EPI_DGELU>(a, p, out_f32, stream);
   }
 }
 
@@ -1003,35 +939,13 @@ extern "C" int udm_gemm_tn_bf16(const void* A, const void* B, void* C, int64_t M
   UDM_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 64 == 0, "udm_gemm_tn_bf16: K must be a positive multiple of 64 (got M=%ld N=%ld K=%ld)", (long)M, (long)N, (long)K);
   UDM_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0 && lda >= M && ldb >= N && lda >= 8 && ldb >= 8, "udm_gemm_tn_bf16: lda/ldb must be multiples of 8 and cover the rows");
   UDM_CHECK_ARG(((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && ((uintptr_t)C % 16 == 0), "udm_gemm_tn_bf16: operands must be 16-byte aligned");
-  GemmArgs a;
-  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = C; a.bias = nullptr; a.aux = nullptr;
-  a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldaux = 0;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K; a.beta = beta;
-  a.splitk = 1;
-  a.slice_stride = 0;
-  {  // whole tiles that fill the chip: the one-wave-per-SIMD kernel (gemm_quad.hip)
-    int fm = 0;
-    if (g_force_tile < 0 && udm_quad_tn_ok(M, N, K, &fm) && ((M / (64 * fm)) * (N / 256) >= 128 || udm_quad_mode() == 2)) {
-      QuadArgs q{};
-      q.A = a.A; q.B = a.B; q.C = C; q.lda = lda; q.ldb = ldb; q.ldc = ldc; q.M = a.M; q.N = a.N; q.K = a.K; q.beta = beta; q.splitk = 1;
-      return udm_quad_launch_tn(q, fm, stream);
-    }
-  }
-  int tile = choose_tile(M, N, K, lda, ldb);
-  if (tile == 0) tile = M <= 192 ? 192 : 256;  // the K-major path has no small-tile kernel; the large one handles any M, N by clamping
-  if (beta == 1.0f) {  // accumulate form: few output tiles over a long K (e.g. the 2048x2048 out-proj wgrad, K = B*L) -> split K, atomically add
-    const long tiles = ((M + tile - 1) / tile) * ((N + 255) / 256);
-    const long nkt = K / 64;
-    int sk = 1;
-    // Measured on MI355X (2048x2048 output, K = 10240): 4-way split + fp32 atomics is SLOWER (0.31 ms) than one slice per tile on a
-    // quarter of the CUs (0.24 ms) — 16.8 M L2 atomics cost more than the idle CUs.  Only split when the output is tiny.
-    while (tiles * sk * 2 <= 32 && nkt / (sk * 2) >= 16 && sk < 8) sk *= 2;
-    a.splitk = sk;
-  }
-  switch (tile) {
-    case 192: return launch_big_t<192, UDM_EPI_NONE, true, true>(a, stream);
-    case 320: return launch_big_t<320, UDM_EPI_NONE, true, true>(a, stream);
-    default: return launch_big_t<256, UDM_EPI_NONE, true, true>(a, stream);
+  const GemmPlan p = gemm_plan_tn(M, N, K, beta, gemm_env());
+  if (is_quad(p)) return udm_quad_launch(quad_args(A, B, C, M, N, K, lda, ldb, ldc, beta), p, QUAD_TN, UDM_EPI_NONE, 1, stream);
+  const GemmArgs a = gemm_args(A, B, C, M, N, K, lda, ldb, ldc, beta);
+  switch (p.tile_rows) {
+    case 192: return launch_big_t<192, UDM_EPI_NONE, true, true>(a, p, stream);
+    case 320: return launch_big_t<320, UDM_EPI_NONE, true, true>(a, p, stream);
+    default: return launch_big_t<256, UDM_EPI_NONE, true, true>(a, p, stream);
   }
 }
 
@@ -1074,26 +988,14 @@ extern "C" int udm_gemm_nt_splitk_bf16(const void* A, const void* B, void* C, in
                                        float* ws, int64_t ws_elems, hipStream_t stream) {
   UDM_CHECK_ARG(A && B && C, "udm_gemm_nt_splitk_bf16: null operand");
   UDM_CHECK_ARG(M > 0 && N > 0 && K > 0, "udm_gemm_nt_splitk_bf16: empty problem");
-  const long tiles = ((M + 319) / 320) * ((N + 255) / 256);
-  const long nkt = K / 64;
-  long skl = gemm_cus_available() / tiles;
-  if (skl > nkt / 8) skl = nkt / 8;
-  if (skl > 32) skl = 32;
-  const int sk = skl < 2 ? 1 : (int)skl;
-  if (sk == 1 || K % 64 != 0 || !ws || ws_elems < (int64_t)sk * M * N || N % 4 != 0 || ldc % 4 != 0 || M < 320 || N < 256)
-    return udm_gemm_nt_bf16(A, B, C, M, N, K, lda, ldb, ldc, 0, UDM_EPI_NONE, nullptr, nullptr, 0, 0.f, stream);
+  const GemmPlan p = gemm_plan_nt_splitk(M, N, K, ldc, ws ? ws_elems : 0, gemm_env());
+  if (p.fallback) return udm_gemm_nt_bf16(A, B, C, M, N, K, lda, ldb, ldc, 0, UDM_EPI_NONE, nullptr, nullptr, 0, 0.f, stream);
   UDM_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0, "udm_gemm_nt_splitk_bf16: lda/ldb must be multiples of 8");
   UDM_CHECK_ARG(((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && ((uintptr_t)C % 8 == 0) && ((uintptr_t)ws % 16 == 0), "udm_gemm_nt_splitk_bf16: operand alignment");
-  GemmArgs a;
-  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = ws; a.bias = nullptr; a.aux = nullptr;
-  a.lda = lda; a.ldb = ldb; a.ldc = N; a.ldaux = 0;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K; a.beta = 0.f;
-  a.splitk = sk;
+  GemmArgs a = gemm_args(A, B, ws, M, N, K, lda, ldb, N, 0.f);
   a.slice_stride = (long)M * N;
-  if (int rc = launch_big_t<320, UDM_EPI_NONE, true, false>(a, stream)) return rc;
-  const long n4 = (long)M * N / 4;
-  const int grid = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-  hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3(grid), dim3(256), 0, stream, (const float*)ws, (bf16_t*)C, (long)M, (int)N, (long)ldc, sk, (long)M * N);
+  if (int rc = launch_big_t<320, UDM_EPI_NONE, true, false>(a, p, stream)) return rc;
+  hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3(p.reduce_grid), dim3(256), 0, stream, (const float*)ws, (bf16_t*)C, (long)M, (int)N, (long)ldc, p.splitk, (long)M * N);
   UDM_CHECK_LAUNCH("udm_gemm_nt_splitk_bf16(reduce)");
   return 0;
 }
@@ -1106,42 +1008,27 @@ extern "C" int udm_gemm_tn_splitk_bf16(const void* A, const void* B, void* C, in
                                        float beta, float* ws, int64_t ws_elems, hipStream_t stream) {
   UDM_CHECK_ARG(A && B && C, "udm_gemm_tn_splitk_bf16: null operand");
   UDM_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 64 == 0, "udm_gemm_tn_splitk_bf16: K must be a positive multiple of 64 (got M=%ld N=%ld K=%ld)", (long)M, (long)N, (long)K);
-  int fm = 0;
-  bool quad = g_force_tile < 0 && udm_quad_tn_ok(M, N, K, &fm);   // whole 256- or 192-row tiles of the one-wave-per-SIMD kernel
-  if (quad && M % 256 == 0) fm = 4;   // (256-row tiles wherever they are whole: fewer partial-tile bytes per flop; UniDisc-S 23.84 vs 23.97 ms with the round-count pick)
-  const long tiles = quad ? (M / (64 * fm)) * (N / 256) : ((M + 255) / 256) * ((N + 255) / 256);
-  const long nkt = K / 64;
-  // as many slices as fill the CUs once (256, or the cap of udm_gemm_set_cus; any count: slices may be uneven), each at least 8 K tiles deep, at most 32
-  long skl = gemm_cus_available() / tiles;
-  if (skl > nkt / 8) skl = nkt / 8;
-  if (skl > 32) skl = 32;
-  const int sk = skl < 2 ? 1 : (int)skl;
-  if (sk == 1 || !ws || ws_elems < (int64_t)sk * M * N || ldc != N || (M * N) % 4 != 0)
-    return udm_gemm_tn_bf16(A, B, C, M, N, K, lda, ldb, ldc, beta, stream);
+  const GemmPlan p = gemm_plan_tn_splitk(M, N, K, ldc, ws ? ws_elems : 0, gemm_env());
+  if (p.fallback) return udm_gemm_tn_bf16(A, B, C, M, N, K, lda, ldb, ldc, beta, stream);
   UDM_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0 && lda >= M && ldb >= N, "udm_gemm_tn_splitk_bf16: lda/ldb must be multiples of 8 and cover the rows");
   UDM_CHECK_ARG(((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && ((uintptr_t)C % 16 == 0) && ((uintptr_t)ws % 16 == 0), "udm_gemm_tn_splitk_bf16: operands must be 16-byte aligned");
-  GemmArgs a;
-  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = ws; a.bias = nullptr; a.aux = nullptr;
-  a.lda = lda; a.ldb = ldb; a.ldc = N; a.ldaux = 0;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K; a.beta = 0.f;
-  a.splitk = sk;
-  a.slice_stride = (long)M * N;
-  if (quad) {   // same slices, one-wave-per-SIMD tiles
-    QuadArgs q{};
-    q.A = a.A; q.B = a.B; q.C = ws; q.lda = lda; q.ldb = ldb; q.ldc = N; q.M = a.M; q.N = a.N; q.K = a.K; q.beta = 0.f; q.splitk = sk;
+  if (is_quad(p)) {   // same slices, one-wave-per-SIMD tiles
+    QuadArgs q = quad_args(A, B, ws, M, N, K, lda, ldb, N, 0.f);
     q.slice_stride = (long)M * N;
-    if (int rc = udm_quad_launch_tn(q, fm, stream)) return rc;
-  } else if (int rc = launch_big_t<256, UDM_EPI_NONE, true, true>(a, stream)) return rc;
-  const long n4 = (long)M * N / 4;
-  const int grid = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid), dim3(256), 0, stream, (const float*)ws, (float*)C, n4, sk, (long)M * N, beta);
+    if (int rc = udm_quad_launch(q, p, QUAD_TN, UDM_EPI_NONE, 1, stream)) return rc;
+  } else {
+    GemmArgs a = gemm_args(A, B, ws, M, N, K, lda, ldb, N, 0.f);
+    a.slice_stride = (long)M * N;
+    if (int rc = launch_big_t<256, UDM_EPI_NONE, true, true>(a, p, stream)) return rc;
+  }
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(p.reduce_grid), dim3(256), 0, stream, (const float*)ws, (float*)C, (long)M * N / 4, p.splitk, (long)M * N, beta);
   UDM_CHECK_LAUNCH("udm_gemm_tn_splitk_bf16(reduce)");
   return 0;
 }
 
 extern "C" __attribute__((visibility("hidden"))) int udm_gemm_set_tile(int tile) {
   UDM_CHECK_ARG(tile == -1 || tile == 0 || tile == 192 || tile == 256 || tile == 320, "udm_gemm_set_tile: tile must be -1 (auto), 0, 192, 256 or 320");
-  g_force_tile = tile;
+  gemm_env().force_tile = tile;
   return 0;
 }
 
@@ -1178,20 +1065,14 @@ extern "C" int udm_cast_transpose_multi_f32_bf16(const void* jobs, int64_t njobs
 
 // C[M, N] bf16 = A[M, K] B[K, N] (A row-major with K contiguous, B row-major with N contiguous): the dgrad dX = dY W read from the forward's own
 // bf16 shadow of W [out, in], so that no transposed shadow has to be produced by the per-step weight cast.  Whole tiles, or 320-row tiles with a ragged last tile row (udm_gemm_nn_ok).
-extern "C" int udm_gemm_nn_ok(int64_t M, int64_t N, int64_t K) {
-  int fm = 0;
-  return (M > 0 && udm_quad_nn_ok(M, N, K, &fm)) ? 1 : 0;
-}
+extern "C" int udm_gemm_nn_ok(int64_t M, int64_t N, int64_t K) { return gemm_plan_nn(M, N, K, gemm_env()).ok ? 1 : 0; }
 extern "C" int udm_gemm_nn_bf16(const void* A, const void* B, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, hipStream_t stream) {
   UDM_CHECK_ARG(A && B && C, "udm_gemm_nn_bf16: null pointer");
-  int fm = 0;
-  UDM_CHECK_ARG(M > 0 && udm_quad_nn_ok(M, N, K, &fm), "udm_gemm_nn_bf16: shape %ld x %ld x %ld does not fit the NN kernel (N %% 256, K %% 64, M %% 192/256/320 or enough 320-row tiles to fill the chip; see udm_gemm_nn_ok)",
+  const GemmPlan p = gemm_plan_nn(M, N, K, gemm_env());
+  UDM_CHECK_ARG(p.ok, "udm_gemm_nn_bf16: shape %ld x %ld x %ld does not fit the NN kernel (N %% 256, K %% 64, M %% 192/256/320 or enough 320-row tiles to fill the chip; see udm_gemm_nn_ok)",
                 (long)M, (long)N, (long)K);
   UDM_CHECK_ARG(lda >= K && ldb >= N && ldc >= N && lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0, "udm_gemm_nn_bf16: bad leading dimensions");
-  QuadArgs q{};
-  q.A = (const bf16_t*)A; q.B = (const bf16_t*)B; q.C = C; q.lda = lda; q.ldb = ldb; q.ldc = ldc;
-  q.M = (int)M; q.N = (int)N; q.K = (int)K; q.beta = 0.f; q.splitk = 1;
-  return udm_quad_launch_nn(q, fm, stream);
+  return udm_quad_launch(quad_args(A, B, C, M, N, K, lda, ldb, ldc, 0.f), p, QUAD_NN, UDM_EPI_NONE, 0, stream);
 }
 
 // udm_gemm_nn_bf16 for FEW output tiles: the K range cut into slices so that tiles x slices fill the available CUs once, fp32 partial tiles in `ws`
@@ -1200,24 +1081,15 @@ extern "C" int udm_gemm_nn_bf16(const void* A, const void* B, void* C, int64_t M
 extern "C" int udm_gemm_nn_splitk_bf16(const void* A, const void* B, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
                                        float* ws, int64_t ws_elems, hipStream_t stream) {
   UDM_CHECK_ARG(A && B && C, "udm_gemm_nn_splitk_bf16: null pointer");
-  int fm = 0;
-  UDM_CHECK_ARG(M > 0 && udm_quad_nn_ok(M, N, K, &fm), "udm_gemm_nn_splitk_bf16: shape %ld x %ld x %ld does not fit the NN kernel (see udm_gemm_nn_ok)", (long)M, (long)N, (long)K);
-  const long tiles = fm > 0 ? (M / (64 * fm)) * (N / 256) : 0;
-  const long nkt = K / 64;
-  long skl = tiles ? gemm_cus_available() / tiles : 1;
-  if (skl > nkt / 4) skl = nkt / 4;
-  if (skl > 32) skl = 32;
-  const int sk = skl < 2 ? 1 : (int)skl;
-  if (fm <= 0 || sk == 1 || !ws || ws_elems < (int64_t)sk * M * N || ldc % 4 != 0) return udm_gemm_nn_bf16(A, B, C, M, N, K, lda, ldb, ldc, stream);
+  const GemmPlan p = gemm_plan_nn_splitk(M, N, K, ldc, ws ? ws_elems : 0, gemm_env());
+  UDM_CHECK_ARG(p.ok, "udm_gemm_nn_splitk_bf16: shape %ld x %ld x %ld does not fit the NN kernel (see udm_gemm_nn_ok)", (long)M, (long)N, (long)K);
+  if (p.fallback) return udm_gemm_nn_bf16(A, B, C, M, N, K, lda, ldb, ldc, stream);
   UDM_CHECK_ARG(lda >= K && ldb >= N && ldc >= N && lda % 8 == 0 && ldb % 8 == 0, "udm_gemm_nn_splitk_bf16: bad leading dimensions");
   UDM_CHECK_ARG(((uintptr_t)ws % 16 == 0) && ((uintptr_t)C % 8 == 0), "udm_gemm_nn_splitk_bf16: operand alignment");
-  QuadArgs q{};
-  q.A = (const bf16_t*)A; q.B = (const bf16_t*)B; q.C = ws; q.lda = lda; q.ldb = ldb; q.ldc = N;
-  q.M = (int)M; q.N = (int)N; q.K = (int)K; q.beta = 0.f; q.splitk = sk; q.slice_stride = (long)M * N;
-  if (int rc = udm_quad_launch_nn_f32(q, fm, stream)) return rc;
-  const long n4 = (long)M * N / 4;
-  const int grid = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-  hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3(grid), dim3(256), 0, stream, (const float*)ws, (bf16_t*)C, (long)M, (int)N, (long)ldc, sk, (long)M * N);
+  QuadArgs q = quad_args(A, B, ws, M, N, K, lda, ldb, N, 0.f);
+  q.slice_stride = (long)M * N;
+  if (int rc = udm_quad_launch(q, p, QUAD_NN, UDM_EPI_NONE, 1, stream)) return rc;
+  hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3(p.reduce_grid), dim3(256), 0, stream, (const float*)ws, (bf16_t*)C, (long)M, (int)N, (long)ldc, p.splitk, (long)M * N);
   UDM_CHECK_LAUNCH("udm_gemm_nn_splitk_bf16(reduce)");
   return 0;
 }
@@ -1233,31 +1105,23 @@ extern "C" int udm_gemm_tn_pair_bf16(const void* A0, const void* B0, void* C0, i
                                      const void* B1, void* C1, int64_t M1, int64_t lda1, int64_t ldb1, int64_t ldc1, int64_t N, int64_t K, float beta,
                                      float* ws, int64_t ws_elems, hipStream_t stream) {
   UDM_CHECK_ARG(A0 && B0 && C0 && A1 && B1 && C1, "udm_gemm_tn_pair_bf16: null operand");
-  if (!udm_quad_mode() || M0 <= 0 || M1 <= 0 || M0 % 256 || M1 % 256 || N <= 0 || N % 256 || K < 128 || K % 64) return 3;
   if (lda0 % 8 || ldb0 % 8 || lda1 % 8 || ldb1 % 8 || ldc0 % 4 || ldc1 % 4 || lda0 < M0 || lda1 < M1 || ldb0 < N || ldb1 < N) return 3;
   if (((uintptr_t)A0 | (uintptr_t)B0 | (uintptr_t)C0 | (uintptr_t)A1 | (uintptr_t)B1 | (uintptr_t)C1) % 16) return 3;
-  QuadArgs q{};
-  q.A = (const bf16_t*)A0; q.B = (const bf16_t*)B0; q.C = C0; q.lda = lda0; q.ldb = ldb0; q.ldc = ldc0;
+  const GemmPlan p = gemm_plan_tn_pair(M0, M1, N, K, ldc0 == N && ldc1 == N && ((uintptr_t)ws % 16) == 0, ws ? ws_elems : 0, gemm_env());
+  if (!p.ok) return 3;
+  // the tile rows of BOTH problems in one grid: rows [0, M0) are problem one, the rest problem two
+  QuadArgs q = quad_args(A0, B0, C0, M0 + M1, N, K, lda0, ldb0, ldc0, beta);
   q.A2 = (const bf16_t*)A1; q.B2 = (const bf16_t*)B1; q.C2 = C1; q.lda2 = lda1; q.ldb2 = ldb1; q.ldc2 = ldc1;
-  q.M = (int)M0; q.N = (int)N; q.K = (int)K; q.beta = beta; q.splitk = 1;
-  const long tiles = ((M0 + M1) / 256) * (N / 256), nkt = K / 64;
-  long skl = 256 / tiles;
-  if (skl > nkt / 8) skl = nkt / 8;
-  if (skl > 32) skl = 32;
-  const int sk = skl < 2 ? 1 : (int)skl;
+  q.tiles_m_split = (int)(M0 / 256);
+  if (p.splitk == 1) return udm_quad_launch(q, p, QUAD_TN, UDM_EPI_NONE, 1, stream);
+  // slice s of problem one at ws + s * area, of problem two at ws + M0 * N + s * area (both with leading dimension N)
   const long area = (long)(M0 + M1) * N;
-  if (sk > 1 && ws && ws_elems >= (int64_t)sk * area && ldc0 == N && ldc1 == N && ((uintptr_t)ws % 16) == 0) {
-    // slice s of problem one at ws + s * area, of problem two at ws + M0 * N + s * area (both with leading dimension N)
-    q.C = ws; q.C2 = ws + (long)M0 * N; q.ldc = N; q.ldc2 = N; q.beta = 0.f; q.splitk = sk; q.slice_stride = area;
-    if (int rc = udm_quad_launch_tn_pair(q, M1, stream)) return rc;
-    const long n40 = (long)M0 * N / 4, n41 = (long)M1 * N / 4;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<long>((n40 + 255) / 256, 2048)), dim3(256), 0, stream, (const float*)ws, (float*)C0, n40, sk, area, beta);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<long>((n41 + 255) / 256, 2048)), dim3(256), 0, stream, (const float*)(ws + (long)M0 * N), (float*)C1, n41, sk,
-                       area, beta);
-    UDM_CHECK_LAUNCH("udm_gemm_tn_pair_bf16(reduce)");
-    return 0;
-  }
-  return udm_quad_launch_tn_pair(q, M1, stream);
+  q.C = ws; q.C2 = ws + (long)M0 * N; q.ldc = N; q.ldc2 = N; q.beta = 0.f; q.slice_stride = area;
+  if (int rc = udm_quad_launch(q, p, QUAD_TN, UDM_EPI_NONE, 1, stream)) return rc;
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(p.reduce_grid), dim3(256), 0, stream, (const float*)ws, (float*)C0, (long)M0 * N / 4, p.splitk, area, beta);
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(p.reduce_grid2), dim3(256), 0, stream, (const float*)(ws + (long)M0 * N), (float*)C1, (long)M1 * N / 4, p.splitk, area, beta);
+  UDM_CHECK_LAUNCH("udm_gemm_tn_pair_bf16(reduce)");
+  return 0;
 }
 
 namespace {
@@ -1289,53 +1153,55 @@ __global__ __launch_bounds__(256) void splitk_reduce_multi_kernel(const float* _
 extern "C" int udm_gemm_tn_multi_bf16(int nprob, const void* const* A, const void* const* B, void* const* C, const int64_t* M, const int64_t* N, const int64_t* lda,
                                       const int64_t* ldb, int64_t K, float beta, float* ws, int64_t ws_elems, hipStream_t stream) {
   UDM_CHECK_ARG(A && B && C && M && N && lda && ldb && nprob >= 1 && nprob <= 4, "udm_gemm_tn_multi_bf16: one to four problems");
-  if (!udm_quad_mode() || K < 128 || K % 64 || !ws || ((uintptr_t)ws % 16)) return 3;
+  if (!ws || ((uintptr_t)ws % 16)) return 3;
+  const GemmPlan p = gemm_plan_tn_multi(nprob, M, N, K, ws_elems, gemm_env());
+  if (!p.ok) return 3;
+  const long area = p.ws_need / p.splitk;
   QuadArgs q{};
-  long tiles = 0, area = 0;
+  long tiles = 0, at = 0;
+  ReduceSegs sg{};
   for (int i = 0; i < nprob; ++i) {
-    if (!A[i] || !B[i] || !C[i] || M[i] <= 0 || N[i] <= 0 || M[i] % 256 || N[i] % 256 || lda[i] % 8 || ldb[i] % 8 || lda[i] < M[i] || ldb[i] < N[i]) return 3;
+    if (!A[i] || !B[i] || !C[i] || lda[i] % 8 || ldb[i] % 8 || lda[i] < M[i] || ldb[i] < N[i]) return 3;
     if (((uintptr_t)A[i] | (uintptr_t)B[i] | (uintptr_t)C[i]) % 16) return 3;
     q.m_tile_start[i] = (int)tiles;
     q.m_tiles_n[i] = (int)(N[i] / 256);
     q.mA[i] = (const bf16_t*)A[i]; q.mB[i] = (const bf16_t*)B[i];
-    q.mC[i] = ws + area; q.mlda[i] = lda[i]; q.mldb[i] = ldb[i]; q.mldc[i] = N[i];   // every slice writes its partial tile; slice s at + s * total area
+    q.mC[i] = ws + at; q.mlda[i] = lda[i]; q.mldb[i] = ldb[i]; q.mldc[i] = N[i];   // every slice writes its partial tile; slice s at + s * total area
+    sg.start4[i] = at / 4; sg.out[i] = (float*)C[i];
     tiles += (M[i] / 256) * (N[i] / 256);
-    area += M[i] * N[i];
+    at += M[i] * N[i];
   }
   q.m_tile_start[nprob] = (int)tiles;
-  q.nprob = nprob;
-  const long nkt = K / 64;
-  long skl = gemm_cus_available() / tiles;
-  if (skl > nkt / 8) skl = nkt / 8;
-  if (skl > 32) skl = 32;
-  if (tiles > 128 || skl < 2 || ws_elems < skl * area) return 3;
-  q.A = q.mA[0]; q.B = q.mB[0]; q.C = q.mC[0]; q.lda = q.mlda[0]; q.ldb = q.mldb[0]; q.ldc = q.mldc[0];
-  q.K = (int)K; q.beta = 0.f; q.splitk = (int)skl; q.slice_stride = area;
-  if (int rc = udm_quad_launch_tn_multi(q, stream)) return rc;
-  ReduceSegs sg{};
-  sg.n = nprob;
-  long at = 0;
-  for (int i = 0; i < nprob; ++i) { sg.start4[i] = at / 4; sg.out[i] = (float*)C[i]; at += M[i] * N[i]; }
   sg.start4[nprob] = at / 4;
-  hipLaunchKernelGGL(splitk_reduce_multi_kernel, dim3((unsigned)std::min<long>((at / 4 + 255) / 256, 2048)), dim3(256), 0, stream, (const float*)ws, sg, (int)skl, area, beta);
+  q.nprob = sg.n = nprob;
+  q.A = q.mA[0]; q.B = q.mB[0]; q.C = q.mC[0]; q.lda = q.mlda[0]; q.ldb = q.mldb[0]; q.ldc = q.mldc[0];
+  q.M = (int)tiles * 256; q.N = 256;   // (all tiles of all problems: the grid of the plan)
+  q.K = (int)K; q.beta = 0.f; q.slice_stride = area;
+  if (int rc = udm_quad_launch(q, p, QUAD_TN, UDM_EPI_NONE, 1, stream)) return rc;
+  hipLaunchKernelGGL(splitk_reduce_multi_kernel, dim3(p.reduce_grid), dim3(256), 0, stream, (const float*)ws, sg, p.splitk, area, beta);
   UDM_CHECK_LAUNCH("udm_gemm_tn_multi_bf16(reduce)");
   return 0;
 }
 
-int udm_gemm_cus_available() { return gemm_cus_available(); }
+int udm_gemm_cus_available() { return gemm_env().cus; }
 extern "C" int udm_gemm_set_cus(int cus) {   // 0 = all CUs; otherwise the persistent NT grid (a multiple of 8 in [8, 256])
   UDM_CHECK_ARG(cus == 0 || (cus >= 8 && cus <= 256 && cus % 8 == 0), "udm_gemm_set_cus: 0 or a multiple of 8 in [8, 256]");
-  g_gemm_cus = cus;
+  gemm_env().cus = cus ? cus : 256;
   return 0;
 }
 
 extern "C" __attribute__((visibility("hidden"))) int udm_gemm_set_quad(int mode) {   // diagnostics / tests: 0 = 8-wave kernels only, 1 = auto (default), 2 = quad wherever the shape fits
   UDM_CHECK_ARG(mode >= 0 && mode <= 2, "udm_gemm_set_quad: mode must be 0, 1 or 2");
-  g_quad_mode = mode;
+  gemm_env().quad = mode;
   return 0;
 }
 
 extern "C" __attribute__((visibility("hidden"))) int udm_gemm_set_persist(int enable) {   // diagnostics / tests: 0 = one block per output tile everywhere
-  g_gemm_persist = enable ? 1 : 0;
+  gemm_env().persist = enable ? 1 : 0;
+  return 0;
+}
+
+extern "C" __attribute__((visibility("hidden"))) int udm_gemm_set_quad_asm(int mode) {   // udm_debug_set "gemm_quad_asm": 0 = the C++ K loop everywhere, 1 / 2 = the generated loop, -1 = as the environment has it
+  gemm_env().quad_asm = mode < 0 ? gemm_env_default().quad_asm : mode;
   return 0;
 }

@@ -1,6 +1,7 @@
 // Internal interface between gemm.hip (dispatch, C ABI) and gemm_quad.hip (one-wave-per-SIMD kernels).  Not part of the C ABI.
 #pragma once
 #include "common.h"
+#include "gemm_plan.h"
 
 struct QuadArgs {
   const bf16_t* A;
@@ -36,22 +37,9 @@ struct QuadArgs {
   unsigned* timeline = nullptr;   // diagnostic build of the asm K loop (make UDM_QUADLOOP=timeline)
 };
 
-extern int g_quad_mode;
-extern int g_quad_asm;
 extern unsigned* g_quad_timeline;
-int udm_gemm_cus_available();   // 256, or the cap of udm_gemm_set_cus / UDM_GEMM_CUS: rounds are counted against it
-int udm_quad_mode();   // 0 off, 1 auto (shapes that fill the chip), 2 force wherever the shape fits
-// TN (wgrad) form: does a quad tile fit (whole tiles, K % 64 == 0)?  *fm receives the tile height / 64 (3, 4 or 5).
-bool udm_quad_tn_ok(long M, long N, long K, int* fm);
-int udm_quad_launch_tn(const QuadArgs& a, int fm, hipStream_t stream);
-// two wgrads C = A^T B, C2 = A2^T B2 with the same N and K in one launch of 256 x 256 tiles (a.M / a.tiles_m_split describe problem one, M2 rows problem two)
-int udm_quad_launch_tn_pair(const QuadArgs& a, long M2, hipStream_t stream);
-// up to four wgrads over the same K in one launch of 256 x 256 tiles (a.nprob, a.m*: filled by the caller; a.splitk slices per tile)
-int udm_quad_launch_tn_multi(const QuadArgs& a, hipStream_t stream);
-// NT (forward / dgrad) form
-bool udm_quad_nt_ok(long M, long N, long K, int* fm);
-int udm_quad_launch_nt(const QuadArgs& a, int fm, int epilogue, int out_f32, hipStream_t stream);
-// NN (dgrad from the forward's W shadow) form: C[M, N] bf16 = A[M, K] B[K, N], plain epilogue.  *fm = 3 / 4 / 5 (whole tiles) or -5 (320-row tiles, ragged last tile row)
-bool udm_quad_nn_ok(long M, long N, long K, int* fm);
-int udm_quad_launch_nn(const QuadArgs& a, int fm, hipStream_t stream);
-int udm_quad_launch_nn_f32(const QuadArgs& a, int fm, hipStream_t stream);   // whole tiles (fm = 3 / 4 / 5), fp32 output, a.splitk slices
+int udm_gemm_cus_available();   // GemmEnv::cus of gemm.hip: 256, or the cap of udm_gemm_set_cus / UDM_GEMM_CUS (attention.hip plans against it too)
+// launch the one-wave-per-SIMD kernel a plan of gemm_plan.h names (GEMM_QUAD / GEMM_QUAD_RAGGED: fm, grid, LDS, slices, asm K loop) in the given operand form.
+// NT takes every epilogue (fp32 output: none); TN is fp32 without an epilogue; NN is plain, bf16 or (out_f32: the partial tiles of a K split) fp32.
+enum { QUAD_NT = 0, QUAD_TN = 1, QUAD_NN = 2 };
+int udm_quad_launch(const QuadArgs& a, const GemmPlan& p, int form, int epilogue, int out_f32, hipStream_t stream);

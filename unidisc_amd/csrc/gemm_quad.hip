@@ -426,24 +426,19 @@ __global__ __launch_bounds__(256, 1) void gemm_quad_kernel(QuadArgs p0) {
 }
 
 template <int FM, int MODE, int EPI, bool OUT_F32, bool RAGGED = false>
-int launch_quad_t(const QuadArgs& a0, hipStream_t stream) {
+int launch_quad_t(const QuadArgs& a0, const GemmPlan& p, hipStream_t stream) {
   QuadArgs a = a0;
-  constexpr int BM = 64 * FM;
-  a.tiles_m = RAGGED ? (a.M + BM - 1) / BM : a.M / BM;
-  a.tiles_n = a.N / 256;
-  static const int env_gm = [] { const char* e = getenv("UDM_GEMM_GROUP_M"); return e ? atoi(e) : 0; }();
-  a.group_m = env_gm;
-  const size_t lds = (size_t)2 * (BM + 256) * BK * 2;
+  a.tiles_m = p.tiles_m;
+  a.tiles_n = p.tiles_n;
+  a.group_m = p.group_m;
+  a.splitk = p.splitk;
   constexpr int GAP = 2;
   auto kern = gemm_quad_kernel<FM, MODE, EPI, OUT_F32, GAP, 0, RAGGED>;
   if constexpr (MODE == 0 && !RAGGED && (FM == 4 || FM == 5)) {
-    static const int env_asm = [] { const char* e = getenv("UDM_QUAD_ASM"); return e ? atoi(e) : 1; }();
-    const int nk = a.K / BK;
-    const int mode = g_quad_asm < 0 ? env_asm : g_quad_asm;      // 1 = the 32x32x16 statement, 2 = the 16x16x32 statement
-    if (mode && a.splitk <= 1 && nk >= 4 && nk % 2 == 0) {
+    if (p.asm_loop) {   // 1 = the 32x32x16 statement, 2 = the 16x16x32 statement (a build without it runs the first)
       kern = gemm_quad_kernel<FM, MODE, EPI, OUT_F32, GAP, 0, RAGGED, 1>;
 #ifdef UDM_QUADLOOP16_NT5_ASM
-      if (mode == 2) kern = gemm_quad_kernel<FM, MODE, EPI, OUT_F32, GAP, 0, RAGGED, 2>;
+      if (p.asm_loop == 2) kern = gemm_quad_kernel<FM, MODE, EPI, OUT_F32, GAP, 0, RAGGED, 2>;
 #endif
     }
   }
@@ -455,145 +450,54 @@ int launch_quad_t(const QuadArgs& a0, hipStream_t stream) {
   a.timeline = g_quad_timeline;
   static const void* attr_set = nullptr;
   if (attr_set != (const void*)kern) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
     attr_set = (const void*)kern;
   }
-  hipLaunchKernelGGL(kern, dim3(a.tiles_m * a.tiles_n * (a.splitk > 1 ? a.splitk : 1)), dim3(256), lds, stream, a);
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds_bytes, stream, a);
   UDM_CHECK_LAUNCH("udm_gemm (quad)");
   return 0;
+}
+
+template <int FM>
+int launch_quad_nt_fm(const QuadArgs& a, const GemmPlan& p, int epilogue, int out_f32, hipStream_t stream) {
+  if (out_f32) {
+    if (epilogue != UDM_EPI_NONE) { udm_set_error("udm_quad_launch: fp32 output only without an epilogue"); return 2; }
+    return launch_quad_t<FM, false, UDM_EPI_NONE, true>(a, p, stream);
+  }
+  switch (epilogue) {
+    case UDM_EPI_NONE: return launch_quad_t<FM, false, UDM_EPI_NONE, false>(a, p, stream);
+    case UDM_EPI_BIAS: return launch_quad_t<FM, false, UDM_EPI_BIAS, false>(a, p, stream);
+    case UDM_EPI_BIAS_GELU: return launch_quad_t<FM, false, UDM_EPI_BIAS_GELU, false>(a, p, stream);
+    default: return launch_quad_t<FM, false, UDM_EPI_DGELU, false>(a, p, stream);
+  }
 }
 }  // namespace
 
 unsigned* g_quad_timeline = nullptr;   // diagnostic builds only (udm_debug_set "gemm_quad_timeline")
-int g_quad_asm = -1;    // A/B switch (udm_debug_set "gemm_quad_asm"): -1 = env UDM_QUAD_ASM (default on), 0 = the C++ K loop everywhere
-int g_quad_mode = -1;   // -1: read UDM_GEMM_QUAD (default 1); 0 = off, 1 = where it fills the chip, 2 = wherever the shape fits (tests)
-int udm_quad_mode() {
-  if (g_quad_mode < 0) {
-    const char* e = getenv("UDM_GEMM_QUAD");
-    g_quad_mode = e ? atoi(e) : 1;
-  }
-  return g_quad_mode;
-}
 
-bool udm_quad_tn_ok(long M, long N, long K, int* fm) {
-  if (!udm_quad_mode() || K % 64 != 0 || K < 128 || N % 256 != 0) return false;
-  // the tile height that fills whole rounds of the CUs (256, or what udm_gemm_set_cus leaves) best (ties: the larger wave tile)
-  const long G = udm_gemm_cus_available();
-  const int cands[2] = {4, 3};   // (FM = 5 spills in the TN form: 2 x 9 fragment halves beside 320 accumulators)
-  double best = 1e30;
-  int pick = 0;
-  for (int c = 0; c < 2; ++c) {
-    const int bm = 64 * cands[c];
-    if (M % bm != 0) continue;
-    const long tiles = (M / bm) * (N / 256);
-    const long rounds = (tiles + G - 1) / G;
-    const double t = (double)rounds * bm;
-    if (t < best) { best = t; pick = cands[c]; }
+int udm_quad_launch(const QuadArgs& a, const GemmPlan& p, int form, int epilogue, int out_f32, hipStream_t stream) {
+  const int fm = p.fm();
+  if (form == QUAD_TN) {   // fp32 output, 192- and 256-row tiles (the pair and the multi form: 256)
+    if (fm == 3) return launch_quad_t<3, true, UDM_EPI_NONE, true>(a, p, stream);
+    if (fm == 4) return launch_quad_t<4, true, UDM_EPI_NONE, true>(a, p, stream);
+  } else if (form == QUAD_NT) {
+    if (fm == -5) {   // 320-row tiles, ragged last tile row: plain / bias epilogue, bf16 output
+      if (out_f32 || epilogue > UDM_EPI_BIAS) { udm_set_error("udm_quad_launch: the ragged form has the plain and the bias epilogue only"); return 2; }
+      return epilogue == UDM_EPI_BIAS ? launch_quad_t<5, false, UDM_EPI_BIAS, false, true>(a, p, stream) : launch_quad_t<5, false, UDM_EPI_NONE, false, true>(a, p, stream);
+    }
+    if (fm == 3) return launch_quad_nt_fm<3>(a, p, epilogue, out_f32, stream);
+    if (fm == 4) return launch_quad_nt_fm<4>(a, p, epilogue, out_f32, stream);
+    if (fm == 5) return launch_quad_nt_fm<5>(a, p, epilogue, out_f32, stream);
+  } else if (out_f32) {   // NN, fp32 partial tiles of a K split: whole tiles
+    if (fm == 3) return launch_quad_t<3, 2, UDM_EPI_NONE, true>(a, p, stream);
+    if (fm == 4) return launch_quad_t<4, 2, UDM_EPI_NONE, true>(a, p, stream);
+    if (fm == 5) return launch_quad_t<5, 2, UDM_EPI_NONE, true>(a, p, stream);
+  } else {                // NN, bf16
+    if (fm == -5) return launch_quad_t<5, 2, UDM_EPI_NONE, false, true>(a, p, stream);
+    if (fm == 3) return launch_quad_t<3, 2, UDM_EPI_NONE, false>(a, p, stream);
+    if (fm == 4) return launch_quad_t<4, 2, UDM_EPI_NONE, false>(a, p, stream);
+    if (fm == 5) return launch_quad_t<5, 2, UDM_EPI_NONE, false>(a, p, stream);
   }
-  if (!pick) return false;
-  *fm = pick;
-  return true;
-}
-
-int udm_quad_launch_tn_pair(const QuadArgs& a0, long M2, hipStream_t stream) {
-  QuadArgs a = a0;
-  a.tiles_m_split = a.M / 256;
-  a.M = a.M + (int)M2;        // launch_quad_t derives the tile rows of BOTH problems from M
-  return launch_quad_t<4, true, UDM_EPI_NONE, true>(a, stream);
-}
-
-int udm_quad_launch_tn_multi(const QuadArgs& a0, hipStream_t stream) {
-  QuadArgs a = a0;
-  a.M = a.m_tile_start[a.nprob] * 256;   // launch_quad_t derives the grid from M / 256 x N / 256: all tiles of all problems
-  a.N = 256;
-  a.tiles_m_split = 0;
-  return launch_quad_t<4, true, UDM_EPI_NONE, true>(a, stream);
-}
-
-int udm_quad_launch_tn(const QuadArgs& a, int fm, hipStream_t stream) {
-  switch (fm) {
-    case 3: return launch_quad_t<3, true, UDM_EPI_NONE, true>(a, stream);
-    case 4: return launch_quad_t<4, true, UDM_EPI_NONE, true>(a, stream);
-    default: udm_set_error("udm_quad_launch_tn: bad tile"); return 2;
-  }
-}
-
-bool udm_quad_nt_ok(long M, long N, long K, int* fm) {
-  if (!udm_quad_mode() || K % 64 != 0 || K < 128 || N % 256 != 0) return false;
-  const long G = udm_gemm_cus_available();
-  const int cands[3] = {5, 4, 3};
-  double best = 1e30;
-  int pick = 0;
-  for (int c = 0; c < 3; ++c) {
-    const int bm = 64 * cands[c];
-    if (M % bm != 0) continue;
-    const long tiles = (M / bm) * (N / 256);
-    const long rounds = (tiles + G - 1) / G;
-    const double t = (double)rounds * bm;
-    if (t < best) { best = t; pick = cands[c]; }
-  }
-  if (!pick) return false;
-  *fm = pick;
-  return true;
-}
-
-template <int FM>
-static int launch_quad_nt_fm(const QuadArgs& a, int epilogue, int out_f32, hipStream_t stream) {
-  if (out_f32) {
-    if (epilogue != UDM_EPI_NONE) { udm_set_error("udm_quad_launch_nt: fp32 output only without an epilogue"); return 2; }
-    return launch_quad_t<FM, false, UDM_EPI_NONE, true>(a, stream);
-  }
-  switch (epilogue) {
-    case UDM_EPI_NONE: return launch_quad_t<FM, false, UDM_EPI_NONE, false>(a, stream);
-    case UDM_EPI_BIAS: return launch_quad_t<FM, false, UDM_EPI_BIAS, false>(a, stream);
-    case UDM_EPI_BIAS_GELU: return launch_quad_t<FM, false, UDM_EPI_BIAS_GELU, false>(a, stream);
-    default: return launch_quad_t<FM, false, UDM_EPI_DGELU, false>(a, stream);
-  }
-}
-
-int udm_quad_launch_nt(const QuadArgs& a, int fm, int epilogue, int out_f32, hipStream_t stream) {
-  if (fm == -5) {   // 320-row tiles, ragged last tile row: plain / bias epilogue, bf16 output
-    if (out_f32 || epilogue > UDM_EPI_BIAS) { udm_set_error("udm_quad_launch_nt: the ragged form has the plain and the bias epilogue only"); return 2; }
-    return epilogue == UDM_EPI_BIAS ? launch_quad_t<5, false, UDM_EPI_BIAS, false, true>(a, stream) : launch_quad_t<5, false, UDM_EPI_NONE, false, true>(a, stream);
-  }
-  switch (fm) {
-    case 3: return launch_quad_nt_fm<3>(a, epilogue, out_f32, stream);
-    case 4: return launch_quad_nt_fm<4>(a, epilogue, out_f32, stream);
-    case 5: return launch_quad_nt_fm<5>(a, epilogue, out_f32, stream);
-    default: udm_set_error("udm_quad_launch_nt: bad tile"); return 2;
-  }
-}
-
-// NN (dgrad) form: C[M, N] bf16 = A[M, K] B[K, N]; whole tiles, plain epilogue
-// fm = 3 / 4 / 5: whole tiles of that height; fm = -5: 320-row tiles with a ragged last tile row, where that is fewer rounds x rows than any whole-tile height
-bool udm_quad_nn_ok(long M, long N, long K, int* fm) {
-  int whole = 0;
-  const bool ok = udm_quad_nt_ok(M, N, K, &whole);
-  const long G = udm_gemm_cus_available();
-  double best = ok ? (double)(((M / (64 * whole)) * (N / 256) + G - 1) / G) * 64 * whole : 1e30;
-  static const int env_ragged = [] { const char* e = getenv("UDM_QUAD_RAGGED"); return e ? atoi(e) : 1; }();   // diagnostics: 0 = whole tiles only
-  if (env_ragged && udm_quad_mode() && K % 64 == 0 && K >= 128 && N % 256 == 0 && M > 320 && M % 320 != 0) {
-    const long tiles = ((M + 319) / 320) * (N / 256);
-    const double t = (double)((tiles + G - 1) / G) * 320 * 1.03;
-    if (tiles >= 128 && t < best) { *fm = -5; return true; }
-  }
-  if (ok) *fm = whole;
-  return ok;
-}
-int udm_quad_launch_nn_f32(const QuadArgs& a, int fm, hipStream_t stream) {   // fp32 output (split-K partial tiles)
-  switch (fm) {
-    case 3: return launch_quad_t<3, 2, UDM_EPI_NONE, true>(a, stream);
-    case 4: return launch_quad_t<4, 2, UDM_EPI_NONE, true>(a, stream);
-    case 5: return launch_quad_t<5, 2, UDM_EPI_NONE, true>(a, stream);
-    default: udm_set_error("udm_quad_launch_nn_f32: bad tile"); return 2;
-  }
-}
-int udm_quad_launch_nn(const QuadArgs& a, int fm, hipStream_t stream) {
-  switch (fm) {
-    case -5: return launch_quad_t<5, 2, UDM_EPI_NONE, false, true>(a, stream);
-    case 3: return launch_quad_t<3, 2, UDM_EPI_NONE, false>(a, stream);
-    case 4: return launch_quad_t<4, 2, UDM_EPI_NONE, false>(a, stream);
-    case 5: return launch_quad_t<5, 2, UDM_EPI_NONE, false>(a, stream);
-    default: udm_set_error("udm_quad_launch_nn: bad tile"); return 2;
-  }
+  udm_set_error("udm_quad_launch: no kernel for form %d, fm %d", form, fm);
+  return 2;
 }

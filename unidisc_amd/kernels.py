@@ -102,6 +102,28 @@ def norm_eps(norm_type: str) -> float:
 
 
 # ------------------------------------------------------------------------------------------------ GEMM
+def _splitk_slices(tiles, K, depth=8, cus=256):
+    """gemm_splitk_slices of csrc/gemm_plan.h: as many K slices as fill `cus` CUs once, each at least `depth` K tiles deep, at most 32; 1 = no split"""
+    s = min(cus // tiles if tiles > 0 else 1, (K // 64) // depth, 32)
+    return s if s >= 2 else 1
+
+
+def _ws_floats(slices, area):
+    return slices * area if slices > 1 else 0
+
+
+# Floats of split-K workspace each wrapper asks of `_scratch` (0: it offers none), after the slice rule of the entry point's plan (csrc/gemm_plan.h;
+# tests/test_gemm_plan.py holds the two together).  The asks count slices against all 256 CUs and 256-row tiles: with CUs held (gemm_set_cus) or 192-row tiles the
+# plan takes fewer slices and the ask is an upper bound; only gemm_tn_multi, whose entry point refuses a workspace that is too small, counts what is available.
+GEMM_WS = {
+    "gemm_nn_splitk": lambda M, N, K: 32 * M * N if M * N <= (1 << 22) else 0,   # (at most 32 slices; big problems do not split)
+    "gemm_tn_splitk": lambda M, N, K: _ws_floats(_splitk_slices(((M + 255) // 256) * ((N + 255) // 256), K), M * N),
+    "gemm_nt_splitk": lambda M, N, K: _ws_floats(_splitk_slices(((M + 319) // 320) * ((N + 255) // 256), K), M * N),
+    "gemm_tn_pair": lambda M0, M1, N, K: _ws_floats(_splitk_slices(((M0 + M1) // 256) * (N // 256), K), (M0 + M1) * N),
+    "gemm_tn_multi": lambda shapes, K: _ws_floats(_splitk_slices(sum((M // 256) * (N // 256) for M, N in shapes), K, cus=_CUS[0] or 256), sum(M * N for M, N in shapes)),
+}
+
+
 def gemm_nt(a, b, out=None, *, out_dtype=BF16, M=None, N=None, K=None, lda=None, ldb=None, ldc=None, epilogue=EPI_NONE, bias=None, aux=None,
             ldaux=None, beta=0.0):
     """out[M,N] (+)= a[M,K] @ b[N,K]^T.  a, b bf16 2-D (row stride = stride(0)); out bf16 or fp32."""
@@ -154,7 +176,8 @@ def gemm_nn_splitk(a, b, out, *, N=None):
     _chk(a, BF16, "gemm_nn_splitk a"), _chk(b, BF16, "gemm_nn_splitk b")
     M, Kd = a.shape
     N = b.shape[1] if N is None else N
-    ws = _scratch(32 * M * N, a.device) if M * N <= (1 << 22) else None   # (at most 32 slices; big problems do not split)
+    n = GEMM_WS["gemm_nn_splitk"](M, N, Kd)
+    ws = _scratch(n, a.device) if n else None
     _lib.call("udm_gemm_nn_splitk_bf16", _p(a), _p(b), _p(out), M, N, Kd, a.stride(0), b.stride(0), out.stride(0), _p(ws), ws.numel() if ws is not None else 0, _s())
     return out
 
@@ -197,9 +220,8 @@ def gemm_tn_pair(a0, b0, out0, a1, b1, out1, *, beta=0.0):
     M1 = out1.shape[0]
     if a1.shape[0] != K or b0.shape[0] != K or b1.shape[0] != K or out1.shape[1] != N or not gemm_tn_pair_ok(M0, M1, N, K):
         raise ValueError("gemm_tn_pair: the two problems need the same N and K, with M0, M1, N multiples of 256 and K of 64")
-    tiles = ((M0 + M1) // 256) * (N // 256)
-    sk = max(1, min(256 // tiles, (K // 64) // 8, 32))   # the rule of udm_gemm_tn_pair_bf16 (sizes the workspace): few tiles over a long K are split in K
-    ws = _scratch(sk * (M0 + M1) * N, a0.device) if sk > 1 else None
+    n = GEMM_WS["gemm_tn_pair"](M0, M1, N, K)   # few tiles over a long K are split in K
+    ws = _scratch(n, a0.device) if n else None
     try:   # (through _lib.call like every launch: the bench's per-entry-point timer hooks it)
         _lib.call("udm_gemm_tn_pair_bf16", _p(a0), _p(b0), _p(out0), M0, a0.stride(0), b0.stride(0), out0.stride(0), _p(a1), _p(b1), _p(out1), M1, a1.stride(0),
                   b1.stride(0), out1.stride(0), N, K, float(beta), _p(ws), ws.numel() if ws is not None else 0, _s())
@@ -218,19 +240,16 @@ def gemm_tn_multi(problems, *, beta=0.0):
     if not (1 <= n <= 4):
         return False
     K = problems[0][0].shape[0]
-    tiles = 0
     for a, b, out in problems:
         _chk(a, BF16, "gemm_tn_multi a"), _chk(b, BF16, "gemm_tn_multi b"), _chk(out, F32, "gemm_tn_multi out")
         M, N = out.shape
         if a.shape[0] != K or b.shape[0] != K or M % 256 or N % 256 or out.stride(0) != N or a.stride(1) != 1 or b.stride(1) != 1:
             return False
-        tiles += (M // 256) * (N // 256)
-    cus = _CUS[0] or 256
-    sk = min(cus // max(tiles, 1), (K // 64) // 8, 32)
-    if tiles > 128 or sk < 2 or K % 64:
+    shapes = [tuple(o.shape) for _, _, o in problems]
+    n_ws = GEMM_WS["gemm_tn_multi"](shapes, K)
+    if sum((M // 256) * (N // 256) for M, N in shapes) > 128 or not n_ws or K % 64:
         return False
-    area = sum(o.numel() for _, _, o in problems)
-    ws = _scratch(sk * area, problems[0][0].device)
+    ws = _scratch(n_ws, problems[0][0].device)
     P, I64 = ctypes.c_void_p * n, ctypes.c_int64 * n
     try:
         _lib.call("udm_gemm_tn_multi_bf16", n, P(*[a.data_ptr() for a, _, _ in problems]), P(*[b.data_ptr() for _, b, _ in problems]),
@@ -247,9 +266,8 @@ def gemm_tn_splitk(a, b, out, *, M=None, N=None, beta=0.0):
     K = a.shape[0]
     M = a.shape[1] if M is None else M
     N = b.shape[1] if N is None else N
-    tiles = ((M + 255) // 256) * ((N + 255) // 256)
-    sk = max(1, min(256 // tiles, (K // 64) // 8, 32))   # the rule of udm_gemm_tn_splitk_bf16 (sizes the workspace)
-    ws = _scratch(sk * M * N, a.device) if sk > 1 else None
+    n = GEMM_WS["gemm_tn_splitk"](M, N, K)
+    ws = _scratch(n, a.device) if n else None
     _lib.call("udm_gemm_tn_splitk_bf16", _p(a), _p(b), _p(out), M, N, K, a.stride(0), b.stride(0), out.stride(0), float(beta), _p(ws),
               ws.numel() if ws is not None else 0, _s())
     return out
@@ -262,9 +280,8 @@ def gemm_nt_splitk(a, b, out=None, *, N=None):
     N = b.shape[0] if N is None else N
     if out is None:
         out = torch.empty((M, N), dtype=BF16, device=a.device)
-    tiles = ((M + 319) // 320) * ((N + 255) // 256)
-    sk = max(1, min(256 // tiles, (Kd // 64) // 8, 32))   # the rule of udm_gemm_nt_splitk_bf16 (sizes the workspace)
-    ws = _scratch(sk * M * N, a.device) if sk > 1 else None
+    n = GEMM_WS["gemm_nt_splitk"](M, N, Kd)
+    ws = _scratch(n, a.device) if n else None
     _lib.call("udm_gemm_nt_splitk_bf16", _p(a), _p(b), _p(out), M, N, Kd, a.stride(0), b.stride(0), out.stride(0), _p(ws),
               ws.numel() if ws is not None else 0, _s())
     return out
