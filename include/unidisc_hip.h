@@ -453,6 +453,27 @@ int udm_ar_nucleus_rows(const void* logits, const void* logits_uncond, const flo
                         const int64_t* x0, const void* x0_unmask, int64_t pos, int64_t* next_ids, int64_t R, int64_t V, int64_t Vt, int64_t mask_id,
                         int restrict_modality, hipStream_t stream);
 
+/* ---- The second half of a maskgit / maskgit_nucleus / first_hitting sampler step in one launch (`_maskgit_update` model_eval.py:3046-3114,
+ * `_first_hitting_update` :3005-3043, the padding behind EOS :2390-2394 and the conditioning write-back :2399), one workgroup per sample, L <= 8192 (a longer
+ * row is an argument error), the row in registers (csrc/reveal_plan.h).
+ *   x [B, ldx] int64 in, x_out [B, ldo] int64 out (out of place).  rows [n] int64: flat indices b L + l of the step's [MASK] rows in ascending order, tok [n]
+ *   int64 their tokens, logp [n] fp32 their log-probabilities (confidence mode), as forward_masked_logits and the token kernels leave them; a [MASK] position
+ *   that `rows` does not name keeps [MASK] and has log p = -inf.  Malformed `rows` give wrong tokens, never an access outside the operands.
+ *   k_b = min(sched[b], number of [MASK] positions of row b) (sched int64 [B]; NULL: zeros); k_b <= 0 reveals nothing.
+ *   lottery = 0 (confidence): conf_l = logp_l + (r_temp noise_l) t_b on the [MASK] positions, three rounded fp32 operations in this order; thr = the k_b-th
+ *     largest; EVERY [MASK] position with conf >= thr takes its token (ties at the threshold are all revealed, more than k_b may be).
+ *   lottery = 1: exactly the k_b [MASK] positions with the largest noise_l, in the order (value descending, position ascending).
+ *   noise [B, ldn] fp32, or NULL: Philox4x32-10, key = seed, counter = b ceil(L / 4) + (l >> 2), word = l & 3, grid point u = ((word >> 8) + 0.5) 2^-24 (never 0
+ *     or 1); confidence mode: the Gumbel noise -log(-log u) of the exact grid point; lottery: u rounded to fp32 and capped at 1 - 2^-24.  out_noise [B, ldon]
+ *     (nullable) receives the noise of every position; a second call with it as `noise` gives the same x_out bit for bit.
+ *   eos_id >= 0: first = the smallest l of the whole row with x_new[l] == eos_id; every l > first with modality[b ldm + l] == 0 whose token is neither pad_id
+ *     nor mask_id becomes pad_id.  Then x_new = x0 where x0_unmask (bool, both [B, ld0]; nullable together).
+ *   n = 0 with sched NULL or zeros is the pad-only call: the EOS rule and the write-back alone.  Two launches give bit-identical outputs. */
+int udm_reveal_rows(const int64_t* x, int64_t ldx, int64_t* x_out, int64_t ldo, const int64_t* rows, const int64_t* tok, const float* logp, int64_t n,
+                    const int64_t* sched, const float* t, const float* noise, int64_t ldn, float* out_noise, int64_t ldon, uint64_t seed, float r_temp,
+                    int lottery, int64_t eos_id, int64_t pad_id, const int64_t* modality, int64_t ldm, const int64_t* x0, const void* x0_unmask, int64_t ld0,
+                    int64_t B, int64_t L, int64_t mask_id, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,7 @@ PROTOTYPES = {
     "udm_ar_sample_rows": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _U64, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I, _P],
     "udm_nucleus_sample_rows": [_P, _P, _P, _I64, _P, _P, _I64, _U64, _F, _F, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P],
     "udm_ar_nucleus_rows": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _U64, _I64, _F, _F, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I, _P],
+    "udm_reveal_rows": [_P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _I64, _U64, _F, _I, _I64, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _P],
 }
 EXTRA_SYMBOLS = ["udm_last_error", "udm_abi_version"]
 ABI_VERSION = 4   # the UDM_ABI_VERSION of include/unidisc_hip.h that PROTOTYPES was written for (bumped whenever a signature changes)

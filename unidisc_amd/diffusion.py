@@ -810,7 +810,7 @@ class Diffusion:
 
     @torch.no_grad()
     def _maskgit_update(self, x, t, dt, schedule=None, step=None, x0=None, x0_unmask=None, modality=None, sample_ids=None, pred=None, gumbel=None, seed=None,
-                        nucleus=None, **kwargs):
+                        nucleus=None, tail=None, **kwargs):
         """One `maskgit` step on the [MASK] rows only: token ~ p (or the replayed `pred`) and its log-probability from the fused row kernel
         (`udm_categorical_sample_rows`), confidence = log p + r_temp * gumbel * t, each sample keeps its num_unmask most confident predictions
         (threshold = k-th largest, as the reference).  `gumbel` [B, L]: explicit noise (replay); otherwise drawn on the device."""
@@ -819,7 +819,7 @@ class Diffusion:
         copy_flag = x != self.mask_index
         num_unmask = torch.minimum(schedule[:, step].to(torch.int64).to(x.device), (~copy_flag).sum(dim=-1))
         if bool(torch.all(num_unmask <= 0)):
-            return x, 0
+            return (x if not tail else K.reveal_rows(x, self.mask_index, **tail)), 0      # (early exit: the padding and the write-back still apply)
         r_temp = float(cfg_get(cfg_get(self.config, "eval", None), "maskgit_r_temp", 10))
         sigma_t, _ = self.noise(t_col.squeeze(-1))
         sig = self._process_sigma(sigma_t)
@@ -836,22 +836,67 @@ class Diffusion:
             tok, logp = K.nucleus_sample_rows(logits[:n], self.vocab_size, self.text_vocab_size, self.mask_index, inv_temperature=1.0,
                                               budget=nucleus[0] * nucleus[1], modality=self._row_modality(rows_n, B, L, modality), restrict=self._restrict(),
                                               seed=int(seed if seed is not None else torch.initial_seed()) + 2, logits_u=logits_u, w=w_rows)
-            return self._maskgit_reveal(x, copy_flag, num_unmask, rows_n, tok, logp, gumbel, seed, r_temp, t_col)
+            return self._maskgit_reveal(x, copy_flag, num_unmask, rows_n, tok, logp, gumbel, seed, r_temp, t_col, tail=tail)
         if given is None and nucleus is not None and n > 0:
             given = self._nucleus_draw(logits[:n], logits_u, w_rows, self._row_modality(rows_n, B, L, modality), nucleus[0], nucleus[1],
                                        int(seed if seed is not None else torch.initial_seed()))
         tok, logp = K.categorical_sample_rows(logits[:n], self.vocab_size, self.text_vocab_size, self.mask_index,
                                               modality=self._row_modality(rows_n, B, L, modality), restrict=self._restrict(), given=given,
                                               seed=int(seed if seed is not None else torch.initial_seed()), logits_u=logits_u, w=w_rows)
-        return self._maskgit_reveal(x, copy_flag, num_unmask, rows_n, tok, logp, gumbel, seed, r_temp, t_col)
+        return self._maskgit_reveal(x, copy_flag, num_unmask, rows_n, tok, logp, gumbel, seed, r_temp, t_col, tail=tail)
 
     def _fused_nucleus(self, logits):
         """eval.fused_nucleus (extension key, default false) and a case the fused top-p kernels take: logits on the GPU, a vocabulary they hold in registers"""
         return bool(cfg_get(cfg_get(self.config, "eval", None), "fused_nucleus", False)) and K.nucleus_supported(logits, self.vocab_size)
 
-    def _maskgit_reveal(self, x, copy_flag, num_unmask, rows_n, tok, logp, gumbel, seed, r_temp, t_col):
-        """the second half of a maskgit step: confidence = log p + r_temp * gumbel * t, each sample keeps its num_unmask most confident predictions"""
+    def _fused_reveal(self, x):
+        """eval.fused_reveal (extension key, default false) and a case `udm_reveal_rows` takes: the state on the GPU, a row the kernel holds in registers"""
+        return bool(cfg_get(cfg_get(self.config, "eval", None), "fused_reveal", False)) and K.reveal_supported(x)
+
+    def _eos_padding_ids(self, caching):
+        """(eos, pad) when `trainer.force_after_eos_padding` applies to this run, else None.  model_eval.py:2390: the rule is skipped under
+        eval.attention_caching and when the tokenizer's EOS is its BOS.  The ids come from the tokenizer, else from the extension keys eval.eos_token_id /
+        eval.pad_token_id (as `_pad_token_id`)."""
+        if not bool(cfg_get(cfg_get(self.config, "trainer", None), "force_after_eos_padding", False)) or caching:
+            return None
+        tk, ev = self.tokenizer, cfg_get(self.config, "eval", None)
+        eos, pad, bos = (getattr(tk, n, None) if tk is not None else None for n in ("eos_token_id", "pad_token_id", "bos_token_id"))
+        eos = cfg_get(ev, "eos_token_id", None) if eos is None else eos
+        pad = cfg_get(ev, "pad_token_id", None) if pad is None else pad
+        if eos is None or pad is None:
+            raise ValueError("unidisc_amd.Diffusion.sample: trainer.force_after_eos_padding needs the EOS and pad token ids: tokenizer.eos_token_id / "
+                             "tokenizer.pad_token_id, or the keys eval.eos_token_id / eval.pad_token_id; "
+                             f"{'neither is' if eos is None and pad is None else ('the EOS id is not' if eos is None else 'the pad id is not')} set")
+        if bos is not None and int(eos) == int(bos):
+            return None
+        return int(eos), int(pad)
+
+    def _pad_after_eos(self, x, eos_pad, modality):
+        """model_eval.py:2390-2394 after a sampler update: every text position strictly behind a row's first EOS (searched over the whole row) that holds a
+        token other than pad and [MASK] becomes pad.  Out of place, no host read (a row without EOS has its first EOS at L: nothing lies behind it)."""
+        eos, pad = eos_pad
+        L = x.shape[1]
+        pos = torch.arange(L, device=x.device)
+        first = torch.where(x == eos, pos, torch.full((), L, device=x.device)).amin(dim=-1, keepdim=True)
+        to_pad = (pos > first) & (modality == 0) & (x != pad) & (x != self.mask_index)
+        return torch.where(to_pad, torch.full((), pad, dtype=x.dtype, device=x.device), x)
+
+    def _eos_modality(self, x, modality):
+        """the modality map [B, L] the EOS rule reads: the given one, else the static slices written out"""
+        if modality is not None:
+            return modality.to(torch.int64).contiguous()
+        mod = torch.zeros(x.shape, dtype=torch.int64, device=x.device)
+        mod[:, self.static_img_sl] = 1
+        return mod
+
+    def _maskgit_reveal(self, x, copy_flag, num_unmask, rows_n, tok, logp, gumbel, seed, r_temp, t_col, tail=None):
+        """the second half of a maskgit step: confidence = log p + r_temp * gumbel * t, each sample keeps its num_unmask most confident predictions.
+        `tail`: eval.fused_reveal - one launch (`udm_reveal_rows`) that also pads behind the EOS and writes x0 back (the operands of sample()'s step tail)"""
         B, L = x.shape
+        if tail is not None:
+            return K.reveal_rows(x, self.mask_index, rows=rows_n, tok=tok, logp=logp, sched=num_unmask, t=t_col.reshape(-1).to(torch.float32).contiguous(),
+                                 noise=None if gumbel is None else gumbel.to(torch.float32).contiguous(),
+                                 seed=int(seed if seed is not None else torch.initial_seed()) + 1, r_temp=r_temp, **tail), 1
         if gumbel is None:
             g = torch.Generator(device=x.device).manual_seed(int(seed if seed is not None else torch.initial_seed()) + 1)
             u = torch.rand(B, L, device=x.device, generator=g).clamp_(1e-20, 1.0)
@@ -869,7 +914,7 @@ class Diffusion:
 
     @torch.no_grad()
     def _first_hitting_update(self, x, t, dt, schedule=None, step=None, x0=None, x0_unmask=None, modality=None, sample_ids=None, u=None, pos_u=None, seed=None,
-                              **kwargs):
+                              tail=None, **kwargs):
         """`_first_hitting_update` (model_eval.py:3005-3043) on the [MASK] rows: token = `_sample_categorical(p_x0)` through the fused row kernel (explicit
         uniforms `u` [B, L, V] replay the reference's draw, else Philox), then the num_unmask [MASK] positions with the largest lottery values
         `pos_u` [B, L] are revealed."""
@@ -883,7 +928,7 @@ class Diffusion:
             cache = self.backbone.forward_masked_logits(x, sig, modality=modality, sample_ids=sample_ids)
         num_unmask = torch.minimum(schedule[:, step].to(torch.int64).to(x.device), (~copy_flag).sum(dim=-1))
         if bool(torch.all(num_unmask <= 0)):
-            return x, 1
+            return (x if not tail else K.reveal_rows(x, self.mask_index, **tail)), 1
         logits, rows, n = cache[:3]
         logits_u, w_rows = (cache[3], cache[4]) if len(cache) == 5 else (None, None)
         rows_n = rows[:n]
@@ -891,6 +936,15 @@ class Diffusion:
         base = int(seed if seed is not None else torch.initial_seed())
         tok, _ = K.categorical_sample_rows(logits[:n], self.vocab_size, self.text_vocab_size, self.mask_index, modality=self._row_modality(rows_n, B, L, modality),
                                            restrict=self._restrict(), u=u_rows, seed=base, logits_u=logits_u, w=w_rows)
+        if tail is not None:   # eval.fused_reveal: the lottery, the padding behind the EOS and the x0 write-back in one launch (`udm_reveal_rows`)
+            return K.reveal_rows(x, self.mask_index, rows=rows_n, tok=tok, sched=num_unmask, noise=None if pos_u is None else pos_u.to(torch.float32).contiguous(),
+                                 seed=base + 1, lottery=True, **tail), 1
+        return self._first_hitting_reveal(x, copy_flag, num_unmask, rows_n, tok, pos_u, base), 1
+
+    @staticmethod
+    def _first_hitting_reveal(x, copy_flag, num_unmask, rows_n, tok, pos_u, base):
+        """the second half of a first_hitting step: the num_unmask [MASK] positions with the largest lottery values take their token"""
+        B, L = x.shape
         if pos_u is None:
             pos_u = torch.rand(B, L, device=x.device, generator=torch.Generator(device=x.device).manual_seed(base + 1))
         rv = torch.where(~copy_flag, pos_u.to(torch.float32), torch.full((), -1.0, device=x.device))
@@ -900,7 +954,7 @@ class Diffusion:
         result.scatter_(-1, indices, final)
         pred_full = x.clone()
         pred_full.view(-1).index_copy_(0, rows_n, tok)
-        return torch.where(result, pred_full, x), 1
+        return torch.where(result, pred_full, x)
 
     # ---- AR baseline sampler: `_ar_sampler` model_eval.py:2736-2822 on the backbone's KV cache (reset_kv_cache / forward(start_pos=...))
     def _ar_bos_id(self, bos_token_id=None):
@@ -1116,10 +1170,30 @@ class Diffusion:
         if ev is not None and bool(cfg_get(ev, "conditioning_cache", False)):
             self._cond = self._conditioning_setup(x0, x0_unmask, modality, sample_ids, caching, B, L)
         cond, cond_full = self._cond, None
+        # trainer.force_after_eos_padding (model_eval.py:2390-2394): after every update, padding behind each row's first EOS, then the x0 write-back.  With
+        # eval.fused_reveal (extension key, default false) the second half of a maskgit / first_hitting step, this padding and the write-back are one launch
+        # (`udm_reveal_rows`); ddpm_cache then pads and writes back through the same kernel.
+        eos_pad = self._eos_padding_ids(caching)
+        eos_mod = self._eos_modality(x, modality) if eos_pad is not None else None
+        if x0 is not None and self._fused_reveal(x):
+            x0, x0_unmask = x0.contiguous(), x0_unmask.contiguous()
+
+        def fused_tail():   # the operands of the step tail for `udm_reveal_rows`, or None on the tensor path
+            if not self._fused_reveal(x):
+                return None
+            ops = dict(eos_id=eos_pad[0], pad_id=eos_pad[1], modality=eos_mod) if eos_pad is not None else {}
+            return dict(ops, x0=x0, x0_unmask=x0_unmask) if x0 is not None else ops
+
+        def step_tail(x):
+            if eos_pad is not None:
+                x = self._pad_after_eos(x, eos_pad, eos_mod)
+            return torch.where(x0_unmask, x0, x) if x0 is not None else x
 
         def cond_slice():   # once the cache is built: from here on the sampler's state is the generated slice
-            nonlocal x, x0, x0_unmask, modality, cache, cond_full
+            nonlocal x, x0, x0_unmask, modality, cache, cond_full, eos_mod
             sl = cond["sl"]
+            if eos_mod is not None:
+                eos_mod = eos_mod[:, sl].contiguous()
             cond_full = (x.clone(), x0, x0_unmask, modality)
             cache = self._cache_to_slice(cache, L, sl)
             x, x0, x0_unmask = x[:, sl].contiguous(), x0[:, sl].contiguous(), x0_unmask[:, sl].contiguous()
@@ -1158,17 +1232,21 @@ class Diffusion:
             if predictor in ("maskgit", "maskgit_nucleus"):   # replay: list of (pred [B, L] or None, gumbel [B, L] or None) per step
                 pr, gm = replay[i] if replay is not None else (None, None)
                 upd = self._maskgit_update if predictor == "maskgit" else self._maskgit_nucleus_update
+                tail = fused_tail()
                 x, n = upd(x, t, dt, schedule=schedule, step=i, x0=x0, x0_unmask=x0_unmask, modality=modality, sample_ids=sample_ids,
-                           pred=pr, gumbel=gm, seed=base_seed + 7919 * i)
+                           pred=pr, gumbel=gm, seed=base_seed + 7919 * i, tail=tail)
                 nfe += n
-                if x0 is not None:
-                    x = torch.where(x0_unmask, x0, x)
+                if tail is None:
+                    x = step_tail(x)
                 continue
             if predictor == "first_hitting":   # replay: list of (u [B, L, V] or None, pos_u [B, L] or None) per step
                 uu, pu = replay[i] if replay is not None else (None, None)
+                tail = fused_tail()
                 x, n = self._first_hitting_update(x, t, dt, schedule=schedule, step=i, x0=x0, x0_unmask=x0_unmask, modality=modality, sample_ids=sample_ids,
-                                                  u=uu, pos_u=pu, seed=base_seed + 7919 * i)
+                                                  u=uu, pos_u=pu, seed=base_seed + 7919 * i, tail=tail)
                 nfe += n
+                if tail is None and eos_pad is not None:   # (without the padding the write-back is a no-op here: the update leaves every given position alone)
+                    x = step_tail(x)
                 continue
             cache, x_next, n = self._ddpm_caching_update(x, t, dt, p_x0=cache, x0=x0, x0_unmask=x0_unmask, modality=modality, sample_ids=sample_ids,
                                                          u=noise[i] if noise is not None else None, seed=base_seed + 7919 * i, block_mask=block_mask, **mc_kw)
@@ -1176,8 +1254,8 @@ class Diffusion:
             if self.time_conditioning or not torch.equal(x_next, x):
                 cache = None  # the reference's `if not allclose(x_next, x) or time_conditioning: p_x0_cache = None`
             x = x_next
-            if x0 is not None:
-                x = torch.where(x0_unmask, x0, x)
+            tail = fused_tail() if eos_pad is not None else None
+            x = step_tail(x) if tail is None else K.reveal_rows(x, self.mask_index, **tail)   # (the pad-only call)
         if sliced:   # model_eval.py:2425-2440
             x_full, mod_full, _ = saved
             x_full[:, :Lt] = x

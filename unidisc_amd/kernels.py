@@ -1190,3 +1190,50 @@ def ar_nucleus_rows(logits, x, pos, V, Vt, mask_id, *, inv_temperature, budget, 
               u.stride(0) if u is not None else 0, int(u_col0), int(seed), int(step), float(inv_temperature), float(budget), _p(x), x.stride(0), _p(x0),
               _p(x0_unmask), int(pos), _p(next_ids), R, V, Vt, mask_id, 1 if restrict else 0, _s())
     return x
+
+
+REVEAL_L_MAX = 8192   # udm_reveal_rows holds a sample's row in registers (csrc/reveal_plan.h): a longer row is refused (the sampler keeps the tensor path)
+
+
+def reveal_supported(x):
+    """whether the fused sampler-step tail takes this case: token ids [B, L] on a GPU with L <= REVEAL_L_MAX (the callers keep their tensor path otherwise)"""
+    return bool(x.is_cuda) and x.dim() == 2 and 1 <= int(x.shape[1]) <= REVEAL_L_MAX
+
+
+def reveal_rows(x, mask_id, *, rows=None, tok=None, logp=None, sched=None, t=None, noise=None, out_noise=None, seed=0, r_temp=0.0, lottery=False, eos_id=None,
+                pad_id=None, modality=None, x0=None, x0_unmask=None, out=None):
+    """x_out [B, L] (`out`, or a new tensor): the second half of a maskgit / first_hitting step, the padding behind the first EOS and the x0 write-back in one launch
+    (`udm_reveal_rows`, include/unidisc_hip.h).  rows / tok / logp [n]: the step's compacted [MASK] rows (flat indices ascending), their tokens and, for
+    the confidence mode, log p; sched int64 [B]; t fp32 [B]; noise fp32 [B, L]: explicit Gumbel noise (lottery=True: lottery uniforms), else Philox(seed);
+    out_noise fp32 [B, L] receives the noise used.  eos_id / pad_id / modality [B, L]: the EOS rule (None: off).  Nothing given but x, the EOS operands and
+    x0: the pad-only call."""
+    B, L = x.shape
+    n = 0 if rows is None else int(rows.numel())
+    for v, name in ((x, "x"), (rows, "rows"), (tok, "tok"), (sched, "sched"), (modality, "modality"), (x0, "x0")):
+        if v is not None and (v.dtype != torch.int64 or v.stride(-1) != 1):
+            raise TypeError(f"reveal_rows: {name} must be int64 with contiguous rows")
+    for v, name in ((logp, "logp"), (t, "t"), (noise, "noise"), (out_noise, "out_noise")):
+        if v is not None and (v.dtype != F32 or v.stride(-1) != 1):
+            raise TypeError(f"reveal_rows: {name} must be float32 with contiguous rows")
+    if n and (tok is None or tok.numel() != n or (not lottery and (logp is None or logp.numel() != n))):
+        raise ValueError("reveal_rows: tok (and logp in the confidence mode) must have one entry per row index")
+    if (sched is not None and sched.numel() != B) or (t is not None and t.numel() != B):
+        raise ValueError("reveal_rows: sched and t have one entry per sample")
+    for v, name in ((noise, "noise"), (out_noise, "out_noise"), (modality, "modality"), (x0, "x0"), (x0_unmask, "x0_unmask")):
+        if v is not None and tuple(v.shape) != (B, L):
+            raise ValueError(f"reveal_rows: {name} must be [B, L] like x")
+    if (x0 is None) != (x0_unmask is None):
+        raise ValueError("reveal_rows: the write-back needs both x0 and x0_unmask")
+    if x0_unmask is not None and (x0_unmask.dtype != torch.bool or x0_unmask.stride(-1) != 1 or x0_unmask.stride(0) != x0.stride(0)):
+        raise TypeError("reveal_rows: x0_unmask must be bool and laid out like x0")
+    if eos_id is not None and (pad_id is None or modality is None):
+        raise ValueError("reveal_rows: the EOS rule needs pad_id and the modality map")
+    x_out = torch.empty((B, L), dtype=torch.int64, device=x.device) if out is None else out
+    if x_out.dtype != torch.int64 or tuple(x_out.shape) != (B, L) or x_out.stride(-1) != 1:
+        raise TypeError("reveal_rows: out must be int64 [B, L] with contiguous rows")
+    ld = lambda v: v.stride(0) if v is not None else 0
+    _lib.call("udm_reveal_rows", _p(x), x.stride(0), _p(x_out), x_out.stride(0), _p(rows) if n else None, _p(tok) if n else None,
+              _p(logp) if n else None, n, _p(sched), _p(t), _p(noise), ld(noise), _p(out_noise), ld(out_noise), int(seed) & 0xFFFFFFFFFFFFFFFF, float(r_temp),
+              1 if lottery else 0, -1 if eos_id is None else int(eos_id), -1 if pad_id is None else int(pad_id), _p(modality), ld(modality), _p(x0), _p(x0_unmask),
+              ld(x0), B, L, int(mask_id), _s())
+    return x_out
