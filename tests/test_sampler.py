@@ -591,18 +591,28 @@ def test_attention_caching_sampler_host_logic_replays_reference_run(monkeypatch)
 
 def test_attention_caching_cache_moves_between_views():
     """the logits cache of the [MASK] rows follows the reference's p_x0 slicing: to the text slice and back"""
-    from unidisc_amd.diffusion import Diffusion
+    from unidisc_amd.diffusion import Diffusion, MaskedLogits
     L, Lt, B = 6, 2, 2
     rows = torch.tensor([0, 3, 7, 8, 11])          # b0: l = 0, 3; b1: l = 1, 2, 5
     logits = torch.arange(5, dtype=torch.float32)[:, None].repeat(1, 4)
-    cache = (torch.cat([logits, torch.zeros(3, 4)]), torch.cat([rows, torch.tensor([1, 2, 4])]), 5)   # padded to 8 rows like the product's
-    tl, tr, tn = Diffusion._cache_to_text(cache, L, Lt)
+    cache = MaskedLogits.of(torch.cat([logits, torch.zeros(3, 4)]), torch.cat([rows, torch.tensor([1, 2, 4])]), 5)   # padded to 8 rows like the product's
+    tl, tr, tn = Diffusion._cache_to_slice(cache, L, slice(0, Lt))[:3]
     assert tn == 2 and tr.tolist() == [0, 3] and tl[:, 0].tolist() == [0.0, 2.0]      # (b0, l0) -> 0, (b1, l1) -> 1 * Lt + 1
-    new_text = (torch.full((1, 4), 9.0), torch.tensor([3]), 1)                          # the text slice was re-evaluated: one [MASK] left at (b1, l1)
-    fl, fr, fn = Diffusion._cache_to_full(cache, new_text, L, Lt)
+    new_text = MaskedLogits.of(torch.full((1, 4), 9.0), torch.tensor([3]), 1)           # the text slice was re-evaluated: one [MASK] left at (b1, l1)
+    fl, fr, fn = Diffusion._cache_to_full(cache, new_text, L, Lt)[:3]
     assert fn == 4 and fr.tolist() == [3, 8, 11, 7] and fl[:, 0].tolist() == [1.0, 3.0, 4.0, 9.0]
     assert Diffusion._cache_to_full(None, new_text, L, Lt) is None and Diffusion._cache_to_full(cache, None, L, Lt) is None
-    assert Diffusion._cache_to_text(None, L, Lt) is None
+    assert Diffusion._cache_to_slice(None, L, slice(0, Lt)) is None
+    # a slice that does not start at 0 (eval.conditioning_cache with the text given: the image columns): (b0, l3) -> 3 - Lt, (b1, l2) -> 4 + 0, (b1, l5) -> 4 + 3
+    il, ir, inn = Diffusion._cache_to_slice(cache, L, slice(Lt, L))[:3]
+    assert inn == 3 and ir.tolist() == [1, 4, 7] and il[:, 0].tolist() == [1.0, 3.0, 4.0]
+    # a guided record: the unconditional half and the weights stay on the rows of `logits`
+    guided = cache._replace(logits_u=cache.logits + 100.0, w_rows=torch.tensor([0.5, 1.5, 2.5, 3.5, 4.5]))
+    for sl in (slice(0, Lt), slice(Lt, L), slice(1, 4)):
+        g = Diffusion._cache_to_slice(guided, L, sl)
+        assert g.n == g.rows.numel() == g.logits.shape[0] == g.logits_u.shape[0] == g.w_rows.numel() > 0
+        assert torch.equal(g.logits_u, g.logits + 100.0) and torch.equal(g.w_rows, g.logits[:, 0] + 0.5)
+    assert Diffusion._cache_to_slice(guided, L, slice(1, 4)).rows.tolist() == [2, 3, 4]     # (b0, l3) -> 2, (b1, l1) -> 3 + 0, (b1, l2) -> 3 + 1
 
 
 @pytest.mark.gpu

@@ -16,14 +16,15 @@ from __future__ import annotations
 import math
 import os
 
+from collections import namedtuple
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
 
 from . import kernels as K
-from .dit import DIT, ModalityMask, cfg_get
+from .dit import DIT, ModalityMask, cfg_get, static_modality
 from .noise_schedule import LogLinearNoise, get_noise
 
 
@@ -52,6 +53,66 @@ class _LinearLoss(torch.autograd.Function):
     def backward(ctx, g):
         (coef,) = ctx.saved_tensors
         return (g * coef).to(coef.dtype), None, None
+
+
+# ---- the records of the host sampler (Diffusion.sample and the methods around it, below)
+class MaskedLogits(NamedTuple):
+    """The logits of the [MASK] rows of one forward, every tensor already cut to its n rows: logits [n, Vp], rows [n] (flat indices into [B, L]), and with
+    guidance the unconditional half's logits_u [n, Vp] on the same rows and the guidance weight of every row, w_rows [n] (both None without guidance).
+    The samplers keep it as their cache while x does not change (the reference's p_x0 cache)."""
+    logits: torch.Tensor
+    rows: torch.Tensor
+    n: int
+    logits_u: Optional[torch.Tensor] = None
+    w_rows: Optional[torch.Tensor] = None
+
+    @classmethod
+    def of(cls, logits, rows, n):
+        """from what `DIT.forward_masked_logits` returns: the [MASK] rows first, then padding rows"""
+        return cls(logits[:n], rows[:n], n)
+
+
+# `Diffusion.sample`'s predictors: the update method, the mode of its unmasking schedule (None: it has none and keeps a logits cache instead), the keywords
+# its pair of recorded draws is passed as, whether it takes the fused step tail (`tail=`) and whether the tensor tail has anything to write back after it
+_Predictor = namedtuple("_Predictor", "update schedule draws fuses_tail writes_back")
+_PREDICTORS = {
+    "ddpm_cache": _Predictor("_ddpm_cache_step", None, None, False, True),
+    "maskgit": _Predictor("_maskgit_update", "arccos", ("pred", "gumbel"), True, True),
+    "maskgit_nucleus": _Predictor("_maskgit_nucleus_update", "arccos", ("pred", "gumbel"), True, True),
+    "first_hitting": _Predictor("_first_hitting_update", "linear", ("u", "pos_u"), True, False),   # (the update leaves every given position alone)
+}
+
+
+class _SamplerState:
+    """What the sampler loop mutates - x, the conditioning x0 / x0_unmask, the modality map, the EOS rule's modality map and the logits cache - with the one way
+    to run on a slice of the positions: `narrow(sl)` keeps the full tensors and continues on their columns sl, `widen()` writes the slice's x back into the
+    full x and restores the rest.  eval.attention_caching narrows to the text and widens again every few steps, eval.conditioning_cache narrows once."""
+
+    def __init__(self, x, x0, x0_unmask, modality, eos_mod):
+        self.x, self.x0, self.x0_unmask, self.modality, self.eos_mod = x, x0, x0_unmask, modality, eos_mod
+        self.cache, self._full = None, None
+
+    @property
+    def narrowed(self):
+        return self._full is not None
+
+    def narrow(self, sl, modality):
+        """`modality`: the map the slice's rows read (the state's own, or the static slices written out)"""
+        cut = (lambda v: None if v is None else v[:, sl].contiguous())
+        self._full = (sl, self.x.clone(), self.x0, self.x0_unmask, self.modality, self.eos_mod, self.cache)
+        self.cache = Diffusion._cache_to_slice(self.cache, self.x.shape[1], sl)
+        self.x, self.x0, self.x0_unmask, self.modality, self.eos_mod = cut(self.x), cut(self.x0), cut(self.x0_unmask), cut(modality), cut(self.eos_mod)
+
+    def widen(self, keep_cache=False):
+        """keep_cache: the full cache saved by narrow() takes the slice's current cache back (`_cache_to_full`: a text slice); otherwise the cache is dropped"""
+        sl, x_full, self.x0, self.x0_unmask, self.modality, self.eos_mod, cache_full = self._full
+        x_full[:, sl] = self.x
+        self.cache = Diffusion._cache_to_full(cache_full, self.cache, x_full.shape[1], sl.stop) if keep_cache else None
+        self.x, self._full = x_full, None
+
+
+def _seed_or_default(seed):
+    return int(seed if seed is not None else torch.initial_seed())
 
 
 class Diffusion:
@@ -238,8 +299,7 @@ class Diffusion:
             if mm and mod.ndim == 2 and mod.shape[-1] == 1:    # one modality per sample -> per token
                 mod = mod.expand(-1, cfg_get(m, "length")).contiguous()
         elif self.image_model and not mm:                     # static layout: the image occupies the last img_length positions
-            mod = torch.zeros_like(b["input_ids"], dtype=torch.int64)
-            mod[:, self.static_img_sl] = 1
+            mod = self._static_modality(*b["input_ids"].shape, b["input_ids"].device)
         elif cfg_get(data, "txt_only", False):
             mod = torch.zeros_like(b["input_ids"], dtype=torch.int64)
         if mod is None:
@@ -490,8 +550,7 @@ class Diffusion:
         if self._restrict() and mod is None and batch is not None and cfg_get(cfg_get(self.config, "trainer"), "multimodal_batches", False):
             mod = batch["modality"]
         if self._restrict() and mod is None:  # static slices (model.py:634-635)
-            mod = torch.zeros((B, L), dtype=torch.int64, device=logits.device)
-            mod[:, self.static_img_sl] = 1
+            mod = self._static_modality(B, L, logits.device)
         out = K.subs_logprobs(flat, xt.reshape(-1).contiguous() if xt is not None else None, mod.reshape(-1).contiguous() if mod is not None else None, V,
                               self.text_vocab_size, self.mask_index, self._restrict(), out_dtype=logits.dtype if logits.dtype == torch.float32 else torch.bfloat16)
         return out.view(B, L, V)
@@ -539,8 +598,7 @@ class Diffusion:
         B, Lo, V = logits.shape
         mod = kwargs.get("modality") if batch is None else batch.get("modality")
         if self._restrict() and mod is None:
-            mod = torch.zeros((B, x.shape[1]), dtype=torch.int64, device=x.device)
-            mod[:, self.static_img_sl] = 1
+            mod = self._static_modality(B, x.shape[1], x.device)
         mod = mod[:, 1:] if (self._restrict() and mod is not None and mod.shape[1] == Lo + 1) else None
         xt = torch.full((B, Lo), self.mask_index, dtype=torch.int64, device=x.device)   # every row "masked": the SUBS log-prob of such a row is the AR one
         flat = torch.zeros((B * Lo, (V + 7) // 8 * 8), dtype=torch.bfloat16, device=logits.device)
@@ -549,19 +607,42 @@ class Diffusion:
                               mod is not None, out_dtype=torch.bfloat16)
         return out.view(B, Lo, V)
 
-    # ---- sampler inner loop: the `ddpm_cache` predictor (config.sampling.predictor default) with classifier-free guidance
-    # (config.eval.cfg, one pass over [x ; x_uncond] or two with config.eval.split_cfg_batches); no attention caching
+    # ---- the host sampler: `Diffusion.sample` with its four predictors, classifier-free guidance (config.eval.cfg, one pass over
+    # [x ; x_uncond] or two with config.eval.split_cfg_batches), eval.attention_caching, eval.conditioning_cache, the step tail, and the AR sampler
     def _sample_prior(self, *batch_dims):  # model_eval.py:1734-1735
         return self.mask_index * torch.ones(*batch_dims, dtype=torch.int64, device=self.device)
+
+    def _static_modality(self, B, L, device):
+        return static_modality(B, L, self.static_img_sl, device)
 
     def _row_modality(self, rows, B, L, modality):
         """Per-row modality for the SUBS vocabulary restriction (model.py:627-635), or None when it is off."""
         if not self._restrict():
             return None
         if modality is None:  # static slices
-            modality = torch.zeros((B, L), dtype=torch.int64, device=rows.device)
-            modality[:, self.static_img_sl] = 1
+            modality = self._static_modality(B, L, rows.device)
         return modality.reshape(-1).to(torch.int64).index_select(0, rows)
+
+    def _sigma(self, t):
+        """what the backbone takes as sigma at time t"""
+        sigma_t, _ = self.noise(t)
+        return self._process_sigma(sigma_t)
+
+    def _excluded_ids(self, ids, row_modality):
+        """bool [1 or R, V] over ids = arange(V): the [MASK] id and, with row_modality [R] (force_argmax_valid_indices), the other modality's ids"""
+        bad = (ids == self.mask_index)[None]
+        if row_modality is not None:
+            bad = bad | torch.where((row_modality == 1)[:, None], ids[None] < self.text_vocab_size, ids[None] >= self.text_vocab_size)
+        return bad
+
+    @staticmethod
+    def _top_p_draw(probs, top_p, generator=None):
+        """the shared end of both nucleus samplers: sort, keep cumsum <= top_p plus the top id, renormalise, multinomial -> id per row"""
+        sp, si = torch.sort(probs, descending=True, dim=-1)
+        keep = sp.cumsum(-1) <= top_p
+        keep[..., 0] = True
+        fp = sp * keep
+        return si.gather(-1, torch.multinomial(fp / fp.sum(-1, keepdim=True), 1, generator=generator)).squeeze(-1)
 
     def get_cfg_weight(self, t):  # model_eval.py:1737-1758
         ev = cfg_get(self.config, "eval", None)
@@ -582,10 +663,41 @@ class Diffusion:
             w = torch.where(t < hi, w, torch.tensor(0.0, device=t.device))
         return w if isinstance(w, torch.Tensor) else torch.tensor(w)
 
+    def _pair_masked_logits(self, x, x_uncond, sigma, modality, sample_ids, plan_ids, w, split, **fwd_kw):
+        """The guided pair forward (CFG branch of `_ddpm_forward`, model_eval.py:1763-1817) -> MaskedLogits: the conditional input x and the unconditional
+        one x_uncond [B, L] through the backbone, the head on the [MASK] positions of `plan_ids` in both, so the two logits blocks line up row for row.
+        Unsplit (:1787-1803): ONE pass over [x ; x_uncond]; `split` (:1770-1784, eval.split_cfg_batches): two passes of B rows, half the activation memory.
+        w: the guidance weight per batch row ([B], or one value for all), or None - both halves still run and the record is the unguided one (the
+        conditioning-cache build step).  `fwd_kw` goes to `forward_masked_logits`; with `conditioning_cache` the unconditional half lives at cache row B."""
+        fwd = self.backbone.forward_masked_logits
+        B, L = x.shape
+        cat2 = (lambda v: None if v is None else torch.cat([v, v], 0))
+        if sample_ids is not None:   # (named only where there are some: the conditioning cache's forward takes none)
+            fwd_kw = dict(fwd_kw, sample_ids=sample_ids if split else cat2(sample_ids))
+        if split:
+            second = dict(fwd_kw, cache_row0=B) if "conditioning_cache" in fwd_kw else fwd_kw
+            logits, rows, n = fwd(x, sigma, modality=modality, plan_ids=plan_ids, **fwd_kw)
+            logits_u, _, n_u = fwd(x_uncond, sigma, modality=modality, plan_ids=plan_ids, **second)
+            assert n_u == n
+        else:
+            both, rows, n2 = fwd(torch.cat([x, x_uncond], 0), cat2(sigma), modality=cat2(modality), plan_ids=cat2(plan_ids), **fwd_kw)
+            n = n2 // 2   # the stable partition lists the [MASK] rows of the first half, then the same positions of the second half
+            logits, logits_u = both, both[n:]
+        if w is None:
+            return MaskedLogits.of(logits, rows, n)
+        b_of = torch.div(rows[:n], L, rounding_mode="floor")
+        w_b = w.to(torch.float32).reshape(-1)
+        w_rows = (w_b.index_select(0, b_of) if w_b.numel() == B else w_b.expand(B).index_select(0, b_of)).contiguous()
+        return MaskedLogits(logits[:n], rows[:n], n, logits_u[:n], w_rows)
+
+    def _uncond_input(self, x, x0_unmask):
+        """x with the conditioning masked: the unconditional half of a guided forward"""
+        x_uncond = x.clone()
+        x_uncond[x0_unmask] = self.mask_index
+        return x_uncond
+
     def _guided_masked_logits(self, x, t, sigma, x0_unmask, modality, sample_ids):
-        """CFG branch of `_ddpm_forward` (model_eval.py:1763-1817) for the [MASK] rows of x: ONE backbone pass over [x ; x with the conditioning
-        masked] (the reference's non-split form, :1787-1803), head on the same positions of both halves.  Returns the cache tuple
-        (logits_cond [R, Vp], rows [R], n, logits_uncond [R, Vp], per-row weights [n]) or None when the guidance weight is zero everywhere."""
+        """The guided MaskedLogits of the [MASK] rows of x, or None - without a forward - when there is no guidance or its weight is zero everywhere."""
         ev = cfg_get(self.config, "eval", None)
         if getattr(self, "_cond", None) is not None:   # eval.conditioning_cache: every forward of the run goes through the conditioning K / V cache
             return self._cond_masked_logits(x, t, sigma, x0_unmask)
@@ -594,25 +706,16 @@ class Diffusion:
         w = self.get_cfg_weight(t)
         if not bool((w > 0).any()):
             return None
-        B, L = x.shape
-        x_uncond = x.clone()
-        x_uncond[x0_unmask] = self.mask_index
-        if cfg_get(ev, "split_cfg_batches", False):
-            # model_eval.py:1770-1784: two backbone passes of batch B instead of one of 2 B (half the activation memory); the head runs on the
-            # SAME [MASK] positions of both (plan_ids = x), so the two logits blocks line up row for row
-            logits, rows, n = self.backbone.forward_masked_logits(x, sigma, modality=modality, sample_ids=sample_ids, plan_ids=x)
-            logits_u, _, n_u = self.backbone.forward_masked_logits(x_uncond, sigma, modality=modality, sample_ids=sample_ids, plan_ids=x)
-            assert n_u == n
-        else:
-            cat2 = (lambda v: None if v is None else torch.cat([v, v], 0))
-            both, rows, n2 = self.backbone.forward_masked_logits(torch.cat([x, x_uncond], 0), cat2(sigma), modality=cat2(modality), sample_ids=cat2(sample_ids),
-                                                                 plan_ids=torch.cat([x, x], 0))
-            n = n2 // 2   # the stable partition lists the [MASK] rows of the first half, then the same positions of the second half
-            logits, logits_u = both, both[n:]
-        b_of = torch.div(rows[:n], L, rounding_mode="floor")
-        w_b = w.to(torch.float32).reshape(-1)
-        w_rows = (w_b.index_select(0, b_of) if w_b.numel() == B else w_b.expand(B).index_select(0, b_of)).contiguous()
-        return logits[:n], rows[:n], n, logits_u[:n], w_rows
+        return self._pair_masked_logits(x, self._uncond_input(x, x0_unmask), sigma, modality, sample_ids, x, w, bool(cfg_get(ev, "split_cfg_batches", False)))
+
+    def _step_logits(self, x, t, x0_unmask, modality, sample_ids, **fwd_kw):
+        """The MaskedLogits a sampler step draws from, at time t [B]: guided where guidance applies, else one plain forward.  `fwd_kw` (a block mask, the
+        modality cache of eval.attention_caching) rules guidance out."""
+        sig = self._sigma(t)
+        rec = self._guided_masked_logits(x, t, sig, x0_unmask, modality, sample_ids) if not fwd_kw else None
+        if rec is None:
+            rec = MaskedLogits.of(*self.backbone.forward_masked_logits(x, sig, modality=modality, sample_ids=sample_ids, **fwd_kw))
+        return rec
 
     # ---- `eval.conditioning_cache` (extension key): conditional sampling with one modality fully given.  Under the ModalityMask that blinds the given
     # modality's queries to the other one, its K / V in every block depend on its own tokens alone - constant for the whole run (and all-[MASK], so constant
@@ -639,56 +742,41 @@ class Diffusion:
         self.backbone.set_conditioning_cache(B, L, self.device, given="text" if txt_given else "image", guided=guided)
         mod_rows = modality   # what the SUBS vocabulary restriction reads per row: the static slices, written out, once x is a slice
         if mod_rows is None and self._restrict():
-            mod_rows = torch.zeros((B, L), dtype=torch.int64, device=self.device)
-            mod_rows[:, self.static_img_sl] = 1
-        return dict(sl=slice(Lt, L) if txt_given else slice(0, Lt), guided=guided, split=bool(cfg_get(ev, "split_cfg_batches", False)), built=False, sliced=False,
-                    modality=modality, mod_rows=mod_rows, B=B, L=L)
+            mod_rows = self._static_modality(B, L, self.device)
+        return dict(sl=slice(Lt, L) if txt_given else slice(0, Lt), guided=guided, split=bool(cfg_get(ev, "split_cfg_batches", False)), built=False,
+                    modality=modality, mod_rows=mod_rows)
 
     def _cond_masked_logits(self, x, t, sigma, x0_unmask):
-        """the cache tuple of `_guided_masked_logits` (5 entries with guidance weights > 0 somewhere, else (logits, rows, n)) from a conditioning-cache forward:
-        "build" on the full x while the cache is empty - with guidance always on both halves, whatever the weights, since both halves' keys are needed later -
-        and "read" on the generated slice afterwards"""
-        st, bb = self._cond, self.backbone
-        what = "read" if st["built"] else "build"
-        mod = None if st["built"] else st["modality"]
-        B, L = x.shape
+        """The MaskedLogits (guided where a guidance weight is > 0, t = None: unguided) of a conditioning-cache forward: "build" on the full x while the cache
+        is empty - with guidance always on both halves, whatever the weights, since both halves' keys are needed later - and "read" on the generated slice
+        afterwards."""
+        st = self._cond
+        what, mod = ("read", None) if st["built"] else ("build", st["modality"])
         w = self.get_cfg_weight(t) if (st["guided"] and t is not None) else None
-        use_w = w is not None and bool((w > 0).any())
-        if not st["guided"] or (st["built"] and not use_w):
-            out = bb.forward_masked_logits(x, sigma, modality=mod, conditioning_cache=what)
-            st["built"] = True
-            return out
-        x_uncond = x.clone()
-        x_uncond[x0_unmask] = self.mask_index
-        if st["split"]:   # two passes of B rows, each on its half of the cache
-            logits, rows, n = bb.forward_masked_logits(x, sigma, modality=mod, plan_ids=x, conditioning_cache=what, cache_row0=0)
-            logits_u, _, n_u = bb.forward_masked_logits(x_uncond, sigma, modality=mod, plan_ids=x, conditioning_cache=what, cache_row0=B)
-            assert n_u == n
-        else:
-            cat2 = (lambda v: None if v is None else torch.cat([v, v], 0))
-            both, rows, n2 = bb.forward_masked_logits(torch.cat([x, x_uncond], 0), cat2(sigma), modality=cat2(mod), plan_ids=torch.cat([x, x], 0),
-                                                      conditioning_cache=what)
-            n = n2 // 2
-            logits, logits_u = both, both[n:]
+        if w is not None and not bool((w > 0).any()):
+            w = None
+        if not st["guided"] or (st["built"] and w is None):
+            out = MaskedLogits.of(*self.backbone.forward_masked_logits(x, sigma, modality=mod, conditioning_cache=what))
+        else:   # (split: two passes of B rows, each on its half of the cache)
+            out = self._pair_masked_logits(x, self._uncond_input(x, x0_unmask), sigma, mod, None, x, w, st["split"], conditioning_cache=what)
         st["built"] = True
-        if not use_w:
-            return logits[:n], rows[:n], n
-        b_of = torch.div(rows[:n], L, rounding_mode="floor")
-        w_b = w.to(torch.float32).reshape(-1)
-        w_rows = (w_b.index_select(0, b_of) if w_b.numel() == B else w_b.expand(B).index_select(0, b_of)).contiguous()
-        return logits[:n], rows[:n], n, logits_u[:n], w_rows
+        return out
 
     @staticmethod
     def _cache_to_slice(cache, L, sl):
-        """the logits cache over [B, L] -> its rows inside positions sl, re-indexed for [B, len(sl)] (guided caches keep their second half and weights)"""
+        """the logits cache over [B, L] -> its rows inside positions sl, re-indexed for [B, len(sl)] (the reference slices p_x0[:, sl]; a guided cache keeps
+        its second half and its weights, row for row)"""
         if cache is None:
             return None
-        logits, rows, n = cache[:3]
-        r = rows[:n]
-        keep = ((r % L) >= sl.start) & ((r % L) < sl.stop)
-        r2 = r[keep]
-        out = (logits[:n][keep], torch.div(r2, L, rounding_mode="floor") * (sl.stop - sl.start) + r2 % L - sl.start, int(keep.sum()))
-        return out if len(cache) == 3 else out + (cache[3][:n][keep], cache[4][:n][keep])
+        pos = cache.rows % L
+        keep = pos < sl.stop
+        if sl.start > 0:
+            keep = keep & (pos >= sl.start)
+        rows = torch.div(cache.rows[keep], L, rounding_mode="floor") * (sl.stop - sl.start) + pos[keep]
+        if sl.start > 0:
+            rows = rows - sl.start
+        cut = (lambda v: None if v is None else v[keep])
+        return MaskedLogits(cache.logits[keep], rows, int(keep.sum()), cut(cache.logits_u), cut(cache.w_rows))
 
     @torch.no_grad()
     def _ddpm_caching_update(self, x, t, dt, p_x0=None, x0=None, x0_unmask=None, modality=None, sample_ids=None, u=None, seed=None, **kwargs):
@@ -700,52 +788,38 @@ class Diffusion:
             t = t.squeeze(-1)
         B, L = x.shape
         nfe = 0
-        if p_x0 is None:
-            sigma_t, _ = self.noise(t)
-            sig = self._process_sigma(sigma_t)
-            block_mask = kwargs.get("block_mask")
-            mc_kw = dict(modality_cache=kwargs["modality_cache"]) if kwargs.get("modality_cache") is not None else {}   # (eval.attention_caching_read_cache)
-            p_x0 = self._guided_masked_logits(x, t, sig, x0_unmask, modality, sample_ids) if (block_mask is None and not mc_kw) else None
-            if p_x0 is None:
-                p_x0 = self.backbone.forward_masked_logits(x, sig, modality=modality, sample_ids=sample_ids, block_mask=block_mask, **mc_kw)
+        if p_x0 is None:   # (a block mask / the modality cache of eval.attention_caching_read_cache go to the forward and rule guidance out)
+            p_x0 = self._step_logits(x, t, x0_unmask, modality, sample_ids, **{k: kwargs[k] for k in ("block_mask", "modality_cache") if kwargs.get(k) is not None})
             nfe = 1
-        logits, rows, n = p_x0[:3]
-        logits_u, w_rows = (p_x0[3], p_x0[4]) if len(p_x0) == 5 else (None, None)
         x_next = x.clone()
-        if n > 0:
-            rows_n = rows[:n]
+        if p_x0.n > 0:
+            rows_n = p_x0.rows
             b_of = torch.div(rows_n, L, rounding_mode="floor")
             t_rows = t.to(torch.float32).index_select(0, b_of).contiguous()
             s_rows = (t.to(torch.float32) - dt).index_select(0, b_of).contiguous()
             u_rows = u.reshape(B * L, -1).index_select(0, rows_n).contiguous() if u is not None else None
-            tok = K.ddpm_sample_rows(logits[:n], self.vocab_size, self.text_vocab_size, self.mask_index, t=t_rows, s=s_rows,
+            tok = K.ddpm_sample_rows(p_x0.logits, self.vocab_size, self.text_vocab_size, self.mask_index, t=t_rows, s=s_rows,
                                      modality=self._row_modality(rows_n, B, L, modality), restrict=self._restrict(), u=u_rows,
-                                     seed=int(seed if seed is not None else torch.initial_seed()), logits_u=logits_u, w=w_rows)
+                                     seed=_seed_or_default(seed), logits_u=p_x0.logits_u, w=p_x0.w_rows)
             x_next.view(-1).index_copy_(0, rows_n, tok)
         return p_x0, x_next, nfe
 
-    # ---- `eval.attention_caching` (model_eval.py:2296-2366): the logits cache of the [MASK] rows, moved between the full view and the text slice
-    @staticmethod
-    def _cache_to_text(cache, L, Lt):
-        """(logits, rows, n) over [B, L] -> the rows inside positions < Lt, re-indexed for [B, Lt] (the reference slices p_x0[:, txt_sl])"""
-        if cache is None:
-            return None
-        logits, rows, n = cache[:3]
-        r = rows[:n]
-        keep = (r % L) < Lt
-        r2 = r[keep]
-        return logits[:n][keep], torch.div(r2, L, rounding_mode="floor") * Lt + r2 % L, int(keep.sum())
+    def _ddpm_cache_step(self, x, t, dt, state=None, **kwargs):
+        """`_ddpm_caching_update` as a step of `sample`: the logits cache lives in `state` and is dropped once x has changed -> (x_next, nfe)"""
+        state.cache, x_next, nfe = self._ddpm_caching_update(x, t, dt, p_x0=state.cache, **kwargs)
+        if self.time_conditioning or not torch.equal(x_next, x):
+            state.cache = None  # the reference's `if not allclose(x_next, x) or time_conditioning: p_x0_cache = None`
+        return x_next, nfe
 
     @staticmethod
     def _cache_to_full(saved, text_cache, L, Lt):
-        """model_eval.py:2312-2323: the full cache saved when the state was sliced takes the text slice's current cache back (None when either is)"""
+        """model_eval.py:2312-2323 (eval.attention_caching): the full cache saved when the state was sliced to the text takes the text slice's current cache back
+        (None when either is)"""
         if saved is None or text_cache is None:
             return None
-        lg, rows, n = saved[:3]
-        keep = (rows[:n] % L) >= Lt
-        lt, rt, nt = text_cache[:3]
-        rows_t = torch.div(rt[:nt], Lt, rounding_mode="floor") * L + rt[:nt] % Lt
-        return torch.cat([lg[:n][keep], lt[:nt]], 0), torch.cat([rows[:n][keep], rows_t], 0), int(keep.sum()) + nt
+        keep = (saved.rows % L) >= Lt
+        rows_t = torch.div(text_cache.rows, Lt, rounding_mode="floor") * L + text_cache.rows % Lt
+        return MaskedLogits(torch.cat([saved.logits[keep], text_cache.logits], 0), torch.cat([saved.rows[keep], rows_t], 0), int(keep.sum()) + text_cache.n)
 
     # ---- `maskgit` predictor (model_eval.py:2964-3001 schedule, :3046-3114 update)
     @staticmethod
@@ -780,7 +854,7 @@ class Diffusion:
         """Token per [MASK] row from the nucleus-filtered SUBS distribution (`nucleus_sampling_batch`, model_eval.py:2642-2685, quirks included: the
         temperature divides probabilities, the top id always stays).  Sort / cumsum / multinomial over [rows, V] are device tensor ops in row
         chunks: the default path; with eval.fused_nucleus the step draws through `udm_nucleus_sample_rows` instead (`_maskgit_update`)."""
-        V, Vt = self.vocab_size, self.text_vocab_size
+        V = self.vocab_size
         out = torch.empty(logits.shape[0], dtype=torch.int64, device=logits.device)
         gen = torch.Generator(device=logits.device).manual_seed(int(seed) + 2)
         ids = torch.arange(V, device=logits.device)
@@ -789,16 +863,9 @@ class Diffusion:
             if logits_u is not None:
                 wv = w_rows[lo:lo + 2048, None]
                 z = (1 + wv) * z - wv * logits_u[lo:lo + 2048, :V].float()
-            bad = (ids == self.mask_index)[None].expand_as(z)
-            if row_modality is not None:
-                is_img = row_modality[lo:lo + 2048, None] == 1
-                bad = bad | torch.where(is_img, ids[None] < Vt, ids[None] >= Vt)
+            bad = self._excluded_ids(ids, None if row_modality is None else row_modality[lo:lo + 2048])
             p = torch.softmax(z.masked_fill(bad, float("-inf")), dim=-1)
-            sp, si = torch.sort(p / temperature, descending=True, dim=-1)
-            keep = sp.cumsum(-1) <= top_p
-            keep[:, 0] = True
-            fp = sp * keep
-            out[lo:lo + 2048] = si.gather(-1, torch.multinomial(fp / fp.sum(-1, keepdim=True), 1, generator=gen)).squeeze(-1)
+            out[lo:lo + 2048] = self._top_p_draw(p / temperature, top_p, gen)
         return out
 
     @torch.no_grad()
@@ -821,28 +888,22 @@ class Diffusion:
         if bool(torch.all(num_unmask <= 0)):
             return (x if not tail else K.reveal_rows(x, self.mask_index, **tail)), 0      # (early exit: the padding and the write-back still apply)
         r_temp = float(cfg_get(cfg_get(self.config, "eval", None), "maskgit_r_temp", 10))
-        sigma_t, _ = self.noise(t_col.squeeze(-1))
-        sig = self._process_sigma(sigma_t)
-        cache = self._guided_masked_logits(x, t_col.squeeze(-1), sig, x0_unmask, modality, sample_ids)
-        if cache is None:
-            cache = self.backbone.forward_masked_logits(x, sig, modality=modality, sample_ids=sample_ids)
-        logits, rows, n = cache[:3]
-        logits_u, w_rows = (cache[3], cache[4]) if len(cache) == 5 else (None, None)
-        rows_n = rows[:n]
+        logits, rows_n, n, logits_u, w_rows = self._step_logits(x, t_col.squeeze(-1), x0_unmask, modality, sample_ids)
         given = pred.reshape(-1).index_select(0, rows_n).contiguous() if pred is not None else None
-        if given is None and nucleus is not None and n > 0 and self._fused_nucleus(logits):
+        draw_nucleus = given is None and nucleus is not None and n > 0
+        base = _seed_or_default(seed)
+        if draw_nucleus and self._fused_nucleus(logits):
             # eval.fused_nucleus: token and log p(token) from one launch (`udm_nucleus_sample_rows`); nucleus_sampling_batch divides the probabilities by the
             # temperature, which is the temperature-1 distribution against the budget top_p * temperature
-            tok, logp = K.nucleus_sample_rows(logits[:n], self.vocab_size, self.text_vocab_size, self.mask_index, inv_temperature=1.0,
+            tok, logp = K.nucleus_sample_rows(logits, self.vocab_size, self.text_vocab_size, self.mask_index, inv_temperature=1.0,
                                               budget=nucleus[0] * nucleus[1], modality=self._row_modality(rows_n, B, L, modality), restrict=self._restrict(),
-                                              seed=int(seed if seed is not None else torch.initial_seed()) + 2, logits_u=logits_u, w=w_rows)
-            return self._maskgit_reveal(x, copy_flag, num_unmask, rows_n, tok, logp, gumbel, seed, r_temp, t_col, tail=tail)
-        if given is None and nucleus is not None and n > 0:
-            given = self._nucleus_draw(logits[:n], logits_u, w_rows, self._row_modality(rows_n, B, L, modality), nucleus[0], nucleus[1],
-                                       int(seed if seed is not None else torch.initial_seed()))
-        tok, logp = K.categorical_sample_rows(logits[:n], self.vocab_size, self.text_vocab_size, self.mask_index,
-                                              modality=self._row_modality(rows_n, B, L, modality), restrict=self._restrict(), given=given,
-                                              seed=int(seed if seed is not None else torch.initial_seed()), logits_u=logits_u, w=w_rows)
+                                              seed=base + 2, logits_u=logits_u, w=w_rows)
+        else:
+            if draw_nucleus:
+                given = self._nucleus_draw(logits, logits_u, w_rows, self._row_modality(rows_n, B, L, modality), nucleus[0], nucleus[1], base)
+            tok, logp = K.categorical_sample_rows(logits, self.vocab_size, self.text_vocab_size, self.mask_index,
+                                                  modality=self._row_modality(rows_n, B, L, modality), restrict=self._restrict(), given=given,
+                                                  seed=base, logits_u=logits_u, w=w_rows)
         return self._maskgit_reveal(x, copy_flag, num_unmask, rows_n, tok, logp, gumbel, seed, r_temp, t_col, tail=tail)
 
     def _fused_nucleus(self, logits):
@@ -883,11 +944,7 @@ class Diffusion:
 
     def _eos_modality(self, x, modality):
         """the modality map [B, L] the EOS rule reads: the given one, else the static slices written out"""
-        if modality is not None:
-            return modality.to(torch.int64).contiguous()
-        mod = torch.zeros(x.shape, dtype=torch.int64, device=x.device)
-        mod[:, self.static_img_sl] = 1
-        return mod
+        return modality.to(torch.int64).contiguous() if modality is not None else self._static_modality(*x.shape, x.device)
 
     def _maskgit_reveal(self, x, copy_flag, num_unmask, rows_n, tok, logp, gumbel, seed, r_temp, t_col, tail=None):
         """the second half of a maskgit step: confidence = log p + r_temp * gumbel * t, each sample keeps its num_unmask most confident predictions.
@@ -896,9 +953,9 @@ class Diffusion:
         if tail is not None:
             return K.reveal_rows(x, self.mask_index, rows=rows_n, tok=tok, logp=logp, sched=num_unmask, t=t_col.reshape(-1).to(torch.float32).contiguous(),
                                  noise=None if gumbel is None else gumbel.to(torch.float32).contiguous(),
-                                 seed=int(seed if seed is not None else torch.initial_seed()) + 1, r_temp=r_temp, **tail), 1
+                                 seed=_seed_or_default(seed) + 1, r_temp=r_temp, **tail), 1
         if gumbel is None:
-            g = torch.Generator(device=x.device).manual_seed(int(seed if seed is not None else torch.initial_seed()) + 1)
+            g = torch.Generator(device=x.device).manual_seed(_seed_or_default(seed) + 1)
             u = torch.rand(B, L, device=x.device, generator=g).clamp_(1e-20, 1.0)
             gumbel = -torch.log(-torch.log(u))
         conf = torch.full((B * L,), float("-inf"), dtype=torch.float32, device=x.device)
@@ -921,20 +978,13 @@ class Diffusion:
         B, L = x.shape
         t_col = t if t.ndim > 1 else t[:, None]
         copy_flag = x != self.mask_index
-        sigma_t, _ = self.noise(t_col.squeeze(-1))
-        sig = self._process_sigma(sigma_t)
-        cache = self._guided_masked_logits(x, t_col.squeeze(-1), sig, x0_unmask, modality, sample_ids)
-        if cache is None:
-            cache = self.backbone.forward_masked_logits(x, sig, modality=modality, sample_ids=sample_ids)
+        logits, rows_n, n, logits_u, w_rows = self._step_logits(x, t_col.squeeze(-1), x0_unmask, modality, sample_ids)
         num_unmask = torch.minimum(schedule[:, step].to(torch.int64).to(x.device), (~copy_flag).sum(dim=-1))
         if bool(torch.all(num_unmask <= 0)):
             return (x if not tail else K.reveal_rows(x, self.mask_index, **tail)), 1
-        logits, rows, n = cache[:3]
-        logits_u, w_rows = (cache[3], cache[4]) if len(cache) == 5 else (None, None)
-        rows_n = rows[:n]
         u_rows = u.reshape(B * L, -1).index_select(0, rows_n).contiguous() if u is not None else None
-        base = int(seed if seed is not None else torch.initial_seed())
-        tok, _ = K.categorical_sample_rows(logits[:n], self.vocab_size, self.text_vocab_size, self.mask_index, modality=self._row_modality(rows_n, B, L, modality),
+        base = _seed_or_default(seed)
+        tok, _ = K.categorical_sample_rows(logits, self.vocab_size, self.text_vocab_size, self.mask_index, modality=self._row_modality(rows_n, B, L, modality),
                                            restrict=self._restrict(), u=u_rows, seed=base, logits_u=logits_u, w=w_rows)
         if tail is not None:   # eval.fused_reveal: the lottery, the padding behind the EOS and the x0 write-back in one launch (`udm_reveal_rows`)
             return K.reveal_rows(x, self.mask_index, rows=rows_n, tok=tok, sched=num_unmask, noise=None if pos_u is None else pos_u.to(torch.float32).contiguous(),
@@ -980,23 +1030,11 @@ class Diffusion:
     def _ar_nucleus(z, top_p, temperature, generator=None):
         """`nucleus_sampling` (model_eval.py:2691-2734), not the p / T quirk of nucleus_sampling_batch: softmax(z / T), sort, keep cumsum <= top_p plus the top
         id, renormalise, multinomial.  z fp32 [R, V] with excluded ids at -inf (softmax is shift-invariant: raw logits give the log-probs' distribution)."""
-        probs = torch.softmax(z / temperature, dim=-1)
-        sp, si = torch.sort(probs, descending=True, dim=-1)
-        keep = sp.cumsum(-1) <= top_p
-        keep[..., 0] = True
-        fp = sp * keep.float()
-        fp = fp / fp.sum(-1, keepdim=True)
-        return si.gather(-1, torch.multinomial(fp, 1, generator=generator)).squeeze(-1)
+        return Diffusion._top_p_draw(torch.softmax(z / temperature, dim=-1), top_p, generator)
 
-    def _ar_excluded(self, next_modality):
-        """bool [R, V]: the [MASK] id and, with force_argmax_valid_indices, the other modality's ids than next_modality [R]"""
-        V, Vt = self.vocab_size, self.text_vocab_size
-        ids = torch.arange(V, device=next_modality.device if next_modality is not None else self.device)
-        bad = (ids == self.mask_index)[None]
-        if next_modality is not None:
-            img = (next_modality == 1)[:, None]
-            bad = bad | torch.where(img, ids[None] < Vt, ids[None] >= Vt)
-        return bad
+    def _ar_require_gpu(self):
+        if self.device.type != "cuda":
+            raise NotImplementedError("unidisc_amd.Diffusion: the AR sampler runs on the GPU only (KV-cached decoding in HIP kernels; there is no CPU path)")
 
     @torch.no_grad()
     def _ar_sampler(self, B, x0=None, x0_unmask=None, modality=None, noise=None, seed=None, bos_token_id=None, **kwargs):
@@ -1004,8 +1042,7 @@ class Diffusion:
         then one decode step per token; token = argmax(next + Gumbel) (noise [B, L-1, V] replays a recorded draw, otherwise Philox Gumbel from `seed`), or
         the reference's nucleus_sampling with eval.top_p.  CFG (eval.cfg with x0, eval.force_cfg_value) runs [x ; where(x0_unmask, [MASK], x)] as one
         batch on one cache.  Returns (x [B, L], nfe) - nfe counts the argmax steps (0 with top_p, the reference's quirk)."""
-        if self.device.type != "cuda":
-            raise NotImplementedError("unidisc_amd.Diffusion: the AR sampler runs on the GPU only (KV-cached decoding in HIP kernels; there is no CPU path)")
+        self._ar_require_gpu()
         assert B > 0
         assert (x0 is None) == (x0_unmask is None)
         m, ev = cfg_get(self.config, "model"), cfg_get(self.config, "eval", None)
@@ -1032,8 +1069,7 @@ class Diffusion:
             x = torch.where(x0_unmask, x0, x)
         restrict = self._restrict()
         if modality is None and (restrict or self.backbone.modality_embed is not None or self.backbone.rope_2d):
-            modality = torch.zeros((B, L), dtype=torch.int64, device=dev)
-            modality[:, self.static_img_sl] = 1
+            modality = self._static_modality(B, L, dev)
         if modality is not None:
             modality = modality.to(dev).to(torch.int64).contiguous()
         if noise is not None:
@@ -1046,7 +1082,7 @@ class Diffusion:
                           modality=torch.cat([modality, modality], 0) if (guided and modality is not None) else modality)
         kv = bb._kv
         w = torch.full((4,), float(cfg_w) if guided else 0.0, dtype=torch.float32, device=dev)
-        base_seed = int(seed if seed is not None else torch.initial_seed()) & ((1 << 63) - 1)
+        base_seed = _seed_or_default(seed) & ((1 << 63) - 1)
         gen = torch.Generator(device=dev).manual_seed(base_seed + 3) if top_p is not None else None
         logits = kv.logits
 
@@ -1066,7 +1102,7 @@ class Diffusion:
             z = logits[:B, :V].float()
             if guided:
                 z = (1 + float(cfg_w)) * z - float(cfg_w) * logits[B:2 * B, :V].float()
-            z = z.masked_fill(self._ar_excluded(modality[:, i + 1] if restrict else None), float("-inf"))
+            z = z.masked_fill(self._excluded_ids(torch.arange(V, device=dev), modality[:, i + 1] if restrict else None), float("-inf"))
             y = self._ar_nucleus(z, float(top_p), temperature, gen)
             col = y if x0 is None else torch.where(x0_unmask[:, i + 1], x0[:, i + 1], y)
             x[:, i + 1] = col
@@ -1101,8 +1137,7 @@ class Diffusion:
         if self.parameterization == "ar" and bool(cfg_get(cfg_get(self.config, "eval", None), "conditioning_cache", False)):
             raise NotImplementedError("unidisc_amd.Diffusion.sample: eval.conditioning_cache with parameterization=ar - the AR sampler has its own causal KV cache")
         if self.parameterization == "ar":   # model_eval.py:2736-2822: one step per token
-            if self.device.type != "cuda":
-                raise NotImplementedError("unidisc_amd.Diffusion: the AR sampler runs on the GPU only (KV-cached decoding in HIP kernels; there is no CPU path)")
+            self._ar_require_gpu()
             L_ar = int(cfg_get(cfg_get(self.config, "model"), "length"))
             for name, v, ok in (("sample_ids", sample_ids, sample_ids is None), ("replay", replay, replay is None),
                                 ("predictor", predictor, predictor in (None, "ar")), ("num_steps", num_steps, num_steps in (None, L_ar - 1))):
@@ -1127,166 +1162,140 @@ class Diffusion:
             modality = modality.to(self.device)
         timesteps = torch.linspace(1, eps, num_steps + 1, device=self.device)
         dt = (1 - eps) / num_steps
-        base_seed = int(seed if seed is not None else torch.initial_seed())
-        cache, nfe = None, 0
+        base_seed = _seed_or_default(seed)
+        nfe = 0
         if predictor is None:
             predictor = cfg_get(sampling, "predictor", "ddpm_cache") if sampling is not None else "ddpm_cache"
-        if predictor not in ("ddpm_cache", "maskgit", "maskgit_nucleus", "first_hitting"):
+        if predictor not in _PREDICTORS:
             raise NotImplementedError(f"unidisc_amd.Diffusion.sample: predictor {predictor!r} is not built (ddpm_cache, maskgit, maskgit_nucleus, first_hitting)")
-        schedule = None
-        if predictor in ("maskgit", "maskgit_nucleus", "first_hitting"):   # model_eval.py:2274-2290
-            schedule = self.adap_sche(x, num_steps, self.mask_index, "linear" if predictor == "first_hitting" else "arccos")
-        # eval.attention_caching (model_eval.py:2296-2366): every `ratio` steps a full joint update, the step after it a full update in which image
-        # queries see image keys only, every other step on the text slice alone (x, modality and the logits cache sliced to static_txt_sl)
+        spec = _PREDICTORS[predictor]
+        update = getattr(self, spec.update)
+        schedule = self.adap_sche(x, num_steps, self.mask_index, spec.schedule) if spec.schedule is not None else None   # model_eval.py:2274-2290
         ev = cfg_get(self.config, "eval", None)
-        caching = bool(cfg_get(ev, "attention_caching", False)) if ev is not None else False
-        ratio = int(cfg_get(ev, "attention_caching_txt_to_img_ratio", 10)) if caching else 0
         self.sample_step_modes = []
-        if caching:
-            if predictor != "ddpm_cache" or x0 is not None or cfg_get(ev, "cfg", None) is not None or sample_ids is not None:
-                raise NotImplementedError("unidisc_amd.Diffusion.sample: eval.attention_caching is built for the unconditional ddpm_cache predictor only")
-            from .dit import ModalityMask
-            Lt = int(cfg_get(cfg_get(self.config, "model"), "txt_length"))
-            # eval.attention_caching_read_cache (extension key, default false: the reference's behaviour above): the build step also fills a per-block K / V
-            # cache with every position's keys, and the text steps attend to [fresh text keys ; cached image keys] instead of the text keys alone - what the
-            # reference's comment at models/dit.py:790-792 intends.  The cached image keys are those of the x that ENTERED the last build step; they are not
-            # refreshed by the tokens that step or the next full step draw (the next build step does that).
-            read_cache = bool(cfg_get(ev, "attention_caching_read_cache", False))
-            if read_cache:
-                if self.time_conditioning:
-                    raise NotImplementedError("unidisc_amd.Diffusion.sample: eval.attention_caching_read_cache with time_conditioning - the cached image keys "
-                                              "would depend on sigma")
-                if modality is not None and not (bool((modality[:, :Lt] == 0).all()) and bool((modality[:, Lt:] != 0).all())):
-                    raise NotImplementedError("unidisc_amd.Diffusion.sample: eval.attention_caching_read_cache needs the text in the static slice [:txt_length] "
-                                              "of every sample")
-                self.backbone.set_flex_attention_cache(B, L, self.device, None, read_cache=True)
-            else:
-                self.backbone.set_flex_attention_cache(B, L, self.device, None)
-        sliced, saved = False, None
-        read_cache = caching and read_cache
+        caching = self._attention_caching_setup(predictor, x0, modality, sample_ids, B, L)
         # eval.conditioning_cache (extension key, default false): step 0 on the full x fills the conditioning K / V cache, every later step and the
-        # noise-removal forward run on the generated slice (x, x0, x0_unmask, modality and the logits cache sliced; written back at the end)
+        # noise-removal forward run on the generated slice (the state narrowed to it; widened again at the end)
         self._cond = None
         if ev is not None and bool(cfg_get(ev, "conditioning_cache", False)):
-            self._cond = self._conditioning_setup(x0, x0_unmask, modality, sample_ids, caching, B, L)
-        cond, cond_full = self._cond, None
+            self._cond = self._conditioning_setup(x0, x0_unmask, modality, sample_ids, caching is not None, B, L)
+        cond = self._cond
         # trainer.force_after_eos_padding (model_eval.py:2390-2394): after every update, padding behind each row's first EOS, then the x0 write-back.  With
         # eval.fused_reveal (extension key, default false) the second half of a maskgit / first_hitting step, this padding and the write-back are one launch
         # (`udm_reveal_rows`); ddpm_cache then pads and writes back through the same kernel.
-        eos_pad = self._eos_padding_ids(caching)
-        eos_mod = self._eos_modality(x, modality) if eos_pad is not None else None
+        eos_pad = self._eos_padding_ids(caching is not None)
         if x0 is not None and self._fused_reveal(x):
             x0, x0_unmask = x0.contiguous(), x0_unmask.contiguous()
-
-        def fused_tail():   # the operands of the step tail for `udm_reveal_rows`, or None on the tensor path
-            if not self._fused_reveal(x):
-                return None
-            ops = dict(eos_id=eos_pad[0], pad_id=eos_pad[1], modality=eos_mod) if eos_pad is not None else {}
-            return dict(ops, x0=x0, x0_unmask=x0_unmask) if x0 is not None else ops
-
-        def step_tail(x):
-            if eos_pad is not None:
-                x = self._pad_after_eos(x, eos_pad, eos_mod)
-            return torch.where(x0_unmask, x0, x) if x0 is not None else x
-
-        def cond_slice():   # once the cache is built: from here on the sampler's state is the generated slice
-            nonlocal x, x0, x0_unmask, modality, cache, cond_full, eos_mod
-            sl = cond["sl"]
-            if eos_mod is not None:
-                eos_mod = eos_mod[:, sl].contiguous()
-            cond_full = (x.clone(), x0, x0_unmask, modality)
-            cache = self._cache_to_slice(cache, L, sl)
-            x, x0, x0_unmask = x[:, sl].contiguous(), x0[:, sl].contiguous(), x0_unmask[:, sl].contiguous()
-            modality = None if cond["mod_rows"] is None else cond["mod_rows"][:, sl].contiguous()
-            cond["sliced"] = True
-
+        st = _SamplerState(x, x0, x0_unmask, modality, self._eos_modality(x, modality) if eos_pad is not None else None)
         for i in range(num_steps):
             t = timesteps[i] * torch.ones(B, 1, device=self.device)
-            if cond is not None:
-                if cond["built"] and not cond["sliced"]:
-                    cond_slice()
-                self.sample_step_modes.append("slice" if cond["sliced"] else "build")
-            block_mask = None
-            mc_kw = {}
-            if caching:
-                if i % ratio == 0:
-                    if sliced:   # the saved full tensors take the text slice back
-                        x_full, mod_full, cache_full = saved
-                        x_full[:, :Lt] = x
-                        cache = self._cache_to_full(cache_full, cache, L, Lt)
-                        x, modality, sliced, saved = x_full, mod_full, False, None
-                    self.sample_step_modes.append("full")
-                elif (i - 1) % ratio == 0:
-                    block_mask = ModalityMask(torch.zeros(B, dtype=torch.bool, device=self.device), torch.ones(B, dtype=torch.bool, device=self.device), Lt)
-                    self.sample_step_modes.append("build")
-                    if read_cache:   # the step must run its forward (a reused logits cache would leave the K / V cache unbuilt or stale)
-                        cache, mc_kw = None, dict(modality_cache="build")
-                else:
-                    if not sliced:
-                        saved = (x.clone(), modality, cache)
-                        cache = self._cache_to_text(cache, L, Lt)
-                        x, modality, sliced = x[:, :Lt].contiguous(), (None if modality is None else modality[:, :Lt].contiguous()), True
-                    self.sample_step_modes.append("text")
-                    if read_cache:
-                        mc_kw = dict(modality_cache="read")
-            if predictor in ("maskgit", "maskgit_nucleus"):   # replay: list of (pred [B, L] or None, gumbel [B, L] or None) per step
-                pr, gm = replay[i] if replay is not None else (None, None)
-                upd = self._maskgit_update if predictor == "maskgit" else self._maskgit_nucleus_update
-                tail = fused_tail()
-                x, n = upd(x, t, dt, schedule=schedule, step=i, x0=x0, x0_unmask=x0_unmask, modality=modality, sample_ids=sample_ids,
-                           pred=pr, gumbel=gm, seed=base_seed + 7919 * i, tail=tail)
-                nfe += n
-                if tail is None:
-                    x = step_tail(x)
-                continue
-            if predictor == "first_hitting":   # replay: list of (u [B, L, V] or None, pos_u [B, L] or None) per step
-                uu, pu = replay[i] if replay is not None else (None, None)
-                tail = fused_tail()
-                x, n = self._first_hitting_update(x, t, dt, schedule=schedule, step=i, x0=x0, x0_unmask=x0_unmask, modality=modality, sample_ids=sample_ids,
-                                                  u=uu, pos_u=pu, seed=base_seed + 7919 * i, tail=tail)
-                nfe += n
-                if tail is None and eos_pad is not None:   # (without the padding the write-back is a no-op here: the update leaves every given position alone)
-                    x = step_tail(x)
-                continue
-            cache, x_next, n = self._ddpm_caching_update(x, t, dt, p_x0=cache, x0=x0, x0_unmask=x0_unmask, modality=modality, sample_ids=sample_ids,
-                                                         u=noise[i] if noise is not None else None, seed=base_seed + 7919 * i, block_mask=block_mask, **mc_kw)
+            if cond is not None:   # once the cache is built the sampler's state is the generated slice
+                if cond["built"] and not st.narrowed:
+                    st.narrow(cond["sl"], cond["mod_rows"])
+                self.sample_step_modes.append("slice" if st.narrowed else "build")
+            fwd_kw = self._attention_caching_step(caching, st, i, B)   # (may narrow or widen the state; {} without eval.attention_caching)
+            kw = dict(x0=st.x0, x0_unmask=st.x0_unmask, modality=st.modality, sample_ids=sample_ids, seed=base_seed + 7919 * i)
+            tail = None
+            if spec.schedule is None:   # ddpm_cache: the logits cache in the state; `noise`: the recorded uniforms [B, L, V] per step
+                kw.update(fwd_kw, state=st, u=noise[i] if noise is not None else None)
+            else:   # `replay`: per step the predictor's pair of recorded draws (pred, gumbel [B, L] / u [B, L, V], pos_u [B, L]), each or None
+                tail = self._tail_operands(st, eos_pad)
+                kw.update(zip(spec.draws, replay[i] if replay is not None else (None, None)), schedule=schedule, step=i, tail=tail)
+            st.x, n = update(st.x, t, dt, **kw)
             nfe += n
-            if self.time_conditioning or not torch.equal(x_next, x):
-                cache = None  # the reference's `if not allclose(x_next, x) or time_conditioning: p_x0_cache = None`
-            x = x_next
-            tail = fused_tail() if eos_pad is not None else None
-            x = step_tail(x) if tail is None else K.reveal_rows(x, self.mask_index, **tail)   # (the pad-only call)
-        if sliced:   # model_eval.py:2425-2440
-            x_full, mod_full, _ = saved
-            x_full[:, :Lt] = x
-            x, modality = x_full, mod_full
-        if caching:
+            # the step tail: fused into the update, or - ddpm_cache under the padding key - the pad-only call of the same kernel, or the tensor statements
+            in_kernel = tail is not None
+            if not spec.fuses_tail and eos_pad is not None:
+                tail = self._tail_operands(st, eos_pad)
+                if tail is not None:
+                    st.x, in_kernel = K.reveal_rows(st.x, self.mask_index, **tail), True
+            if not in_kernel and (eos_pad is not None or spec.writes_back):
+                st.x = self._tensor_tail(st, eos_pad)
+        if caching is not None:
+            if st.narrowed:   # model_eval.py:2425-2440
+                st.widen()
             self.backbone.reset_kv_cache()
-        if cond is not None and cond["built"] and not cond["sliced"]:
-            cond_slice()
+        if cond is not None and cond["built"] and not st.narrowed:
+            st.narrow(cond["sl"], cond["mod_rows"])
         if noise_removal:  # x = forward(x, sigma(t_last)).argmax(-1): unmasked positions keep their token, masked ones take the best valid id
-            t = timesteps[-1] * torch.ones(B, device=self.device)
-            sigma_t, _ = self.noise(t)
+            sig = self._sigma(timesteps[-1] * torch.ones(B, device=self.device))
             if cond is not None:   # (unguided, like the line below: the conditional half of the cache alone)
-                logits, rows, n = self._cond_masked_logits(x, None, self._process_sigma(sigma_t), x0_unmask)[:3]
+                rec = self._cond_masked_logits(st.x, None, sig, st.x0_unmask)
             else:
-                logits, rows, n = self.backbone.forward_masked_logits(x, self._process_sigma(sigma_t), modality=modality, sample_ids=sample_ids)
+                rec = MaskedLogits.of(*self.backbone.forward_masked_logits(st.x, sig, modality=st.modality, sample_ids=sample_ids))
             nfe += 1
-            if n > 0:
-                tok = K.ddpm_sample_rows(logits[:n], self.vocab_size, self.text_vocab_size, self.mask_index,
-                                         modality=self._row_modality(rows[:n], B, x.shape[1], modality), restrict=self._restrict(), greedy=True)
-                x = x.clone()
-                x.view(-1).index_copy_(0, rows[:n], tok)
-            if x0 is not None:
-                x = torch.where(x0_unmask, x0, x)
+            if rec.n > 0:
+                tok = K.ddpm_sample_rows(rec.logits, self.vocab_size, self.text_vocab_size, self.mask_index,
+                                         modality=self._row_modality(rec.rows, B, st.x.shape[1], st.modality), restrict=self._restrict(), greedy=True)
+                st.x = st.x.clone()
+                st.x.view(-1).index_copy_(0, rec.rows, tok)
+            if st.x0 is not None:
+                st.x = torch.where(st.x0_unmask, st.x0, st.x)
         if cond is not None:
-            if cond["sliced"]:   # the full tensors take the generated slice back
-                x_full, x0, x0_unmask, modality = cond_full
-                x_full[:, cond["sl"]] = x
-                x = x_full
+            if st.narrowed:   # the full tensors take the generated slice back
+                st.widen()
             self._cond = None
             self.backbone.reset_kv_cache()
-        return (x, nfe) if return_nfe else x
+        return (st.x, nfe) if return_nfe else st.x
+
+    def _attention_caching_setup(self, predictor, x0, modality, sample_ids, B, L):
+        """eval.attention_caching (model_eval.py:2296-2366): every `ratio` steps a full joint update, the step after it a full update in which image queries
+        see image keys only, every other step on the text slice alone (the state narrowed to static_txt_sl).  Returns None when the key is off, else
+        dict(ratio, Lt, read_cache) with the backbone's cache set.
+        eval.attention_caching_read_cache (extension key, default false: the reference's behaviour above): the build step also fills a per-block K / V cache
+        with every position's keys, and the text steps attend to [fresh text keys ; cached image keys] instead of the text keys alone - what the reference's
+        comment at models/dit.py:790-792 intends.  The cached image keys are those of the x that ENTERED the last build step; they are not refreshed by the
+        tokens that step or the next full step draw (the next build step does that)."""
+        ev = cfg_get(self.config, "eval", None)
+        if ev is None or not bool(cfg_get(ev, "attention_caching", False)):
+            return None
+        if predictor != "ddpm_cache" or x0 is not None or cfg_get(ev, "cfg", None) is not None or sample_ids is not None:
+            raise NotImplementedError("unidisc_amd.Diffusion.sample: eval.attention_caching is built for the unconditional ddpm_cache predictor only")
+        Lt = int(cfg_get(cfg_get(self.config, "model"), "txt_length"))
+        read_cache = bool(cfg_get(ev, "attention_caching_read_cache", False))
+        if read_cache:
+            if self.time_conditioning:
+                raise NotImplementedError("unidisc_amd.Diffusion.sample: eval.attention_caching_read_cache with time_conditioning - the cached image keys "
+                                          "would depend on sigma")
+            if modality is not None and not (bool((modality[:, :Lt] == 0).all()) and bool((modality[:, Lt:] != 0).all())):
+                raise NotImplementedError("unidisc_amd.Diffusion.sample: eval.attention_caching_read_cache needs the text in the static slice [:txt_length] "
+                                          "of every sample")
+        self.backbone.set_flex_attention_cache(B, L, self.device, None, read_cache=read_cache)
+        return dict(ratio=int(cfg_get(ev, "attention_caching_txt_to_img_ratio", 10)), Lt=Lt, read_cache=read_cache)
+
+    def _attention_caching_step(self, caching, st, i, B):
+        """Step i of eval.attention_caching: puts the state into the step's view, notes the mode in `sample_step_modes` and returns the forward's extra
+        keywords (the build step's block mask, the modality cache's "build" / "read")."""
+        if caching is None:
+            return {}
+        ratio, Lt, read_cache = caching["ratio"], caching["Lt"], caching["read_cache"]
+        if i % ratio == 0:
+            if st.narrowed:   # the saved full tensors take the text slice back
+                st.widen(keep_cache=True)
+            self.sample_step_modes.append("full")
+            return {}
+        if (i - 1) % ratio == 0:
+            self.sample_step_modes.append("build")
+            if read_cache:   # the step must run its forward (a reused logits cache would leave the K / V cache unbuilt or stale)
+                st.cache = None
+            block_mask = ModalityMask(torch.zeros(B, dtype=torch.bool, device=self.device), torch.ones(B, dtype=torch.bool, device=self.device), Lt)
+            return dict(block_mask=block_mask, modality_cache="build") if read_cache else dict(block_mask=block_mask)
+        if not st.narrowed:
+            st.narrow(slice(0, Lt), st.modality)
+        self.sample_step_modes.append("text")
+        return dict(modality_cache="read") if read_cache else {}
+
+    def _tail_operands(self, st, eos_pad):
+        """the operands of the step tail for `udm_reveal_rows` (eval.fused_reveal), or None on the tensor path"""
+        if not self._fused_reveal(st.x):
+            return None
+        ops = dict(eos_id=eos_pad[0], pad_id=eos_pad[1], modality=st.eos_mod) if eos_pad is not None else {}
+        return dict(ops, x0=st.x0, x0_unmask=st.x0_unmask) if st.x0 is not None else ops
+
+    def _tensor_tail(self, st, eos_pad):
+        """the step tail as tensor statements: the padding behind the EOS, then the x0 write-back"""
+        x = self._pad_after_eos(st.x, eos_pad, st.eos_mod) if eos_pad is not None else st.x
+        return torch.where(st.x0_unmask, st.x0, x) if st.x0 is not None else x
 
     # ---- model.py:797-1173, SUBS / continuous-time branch
     def compute_loss(self, batch, prefix, batch_idx=-1):
@@ -1524,26 +1533,12 @@ class Diffusion:
             kk = len(conds)
             cond, plan = torch.cat(conds, 0), torch.cat(plans, 0)
             mod_k = modality.repeat(kk, 1) if modality is not None else None
-            logits_u = None
-            if not guided:
-                logits, rows, n = self.backbone.forward_masked_logits(cond, None, modality=mod_k, plan_ids=plan)
-            elif split:   # two passes of k B rows, the head on the same positions of both (as _guided_masked_logits)
-                logits, rows, n = self.backbone.forward_masked_logits(cond, None, modality=mod_k, plan_ids=plan)
-                logits_u, _, n_u = self.backbone.forward_masked_logits(torch.cat(unconds, 0), None, modality=mod_k, plan_ids=plan)
-                assert n_u == n
-            else:         # one pass over [cond ; uncond]: the stable partition lists the rows of the first half, then the same positions of the second
-                both, rows, n2 = self.backbone.forward_masked_logits(torch.cat([cond, torch.cat(unconds, 0)], 0), None,
-                                                                     modality=torch.cat([mod_k, mod_k], 0) if mod_k is not None else None,
-                                                                     plan_ids=torch.cat([plan, plan], 0))
-                n = n2 // 2
-                logits, logits_u = both, both[n:]
-            rows_n = rows[:n].contiguous()
-            w_rows = None
-            if guided:
-                w_rows = torch.cat(ws, 0).index_select(0, torch.div(rows_n, L, rounding_mode="floor")).contiguous()
-                logits_u = logits_u[:n]
+            if guided:   # the pair forward of the samplers, the weights of the k B rows one per row
+                logits, rows_n, n, logits_u, w_rows = self._pair_masked_logits(cond, torch.cat(unconds, 0), None, mod_k, None, plan, torch.cat(ws, 0), split)
+            else:
+                logits, rows_n, n, logits_u, w_rows = MaskedLogits.of(*self.backbone.forward_masked_logits(cond, None, modality=mod_k, plan_ids=plan))
             x0_rows = x0.repeat(kk, 1).reshape(-1).index_select(0, rows_n)
-            log_p = K.subs_logp_rows(logits[:n], x0_rows, self._row_modality(rows_n, kk * B, L, mod_k), self.vocab_size, self.text_vocab_size, mask_id,
+            log_p = K.subs_logp_rows(logits, x0_rows, self._row_modality(rows_n, kk * B, L, mod_k), self.vocab_size, self.text_vocab_size, mask_id,
                                      self._restrict(), logits_u=logits_u, w=w_rows)
             weighted, unweighed = K.likelihood_scores(log_p, rows_n, torch.cat(wstds, 0).contiguous(), count.repeat(kk).contiguous(), L)
             out_w.append(weighted.view(kk, B))

@@ -51,6 +51,13 @@ def cfg_get(node, key, default=None):
     return v
 
 
+def static_modality(B, L, static_img_sl, device):
+    """The modality map [B, L] of the static layout, written out: 1 (image) inside `static_img_sl`, 0 (text) elsewhere."""
+    mod = torch.zeros((B, L), dtype=torch.int64, device=device)
+    mod[:, static_img_sl] = 1
+    return mod
+
+
 def _ceil(x, m):
     return (x + m - 1) // m * m
 
@@ -1274,9 +1281,7 @@ class DIT(nn.Module, _HubMixin):
         return log_p.view(B, L), S
 
     def _static_modality(self, B, L, dev):
-        cm = torch.zeros(L, dtype=torch.int64, device=dev)
-        cm[self.static_img_sl] = 1
-        return cm[None].expand(B, L).contiguous()
+        return static_modality(B, L, self.static_img_sl, dev)
 
     def _plan_masked_rows(self, ids, mod=None):
         """Queue (without synchronising) a stable partition of the row indices with the [MASK] rows first and their count.  With `mod` (the rows' modality,
