@@ -81,7 +81,7 @@ def test_masked_row_head_compaction_is_exact(name, fake_k):
         diff.backbone.split_head = split     # (text rows x text ids) + (image rows x image ids) instead of rows x all ids: exact under force_argmax_valid_indices
         seen = []
         orig = type(diff.backbone)._engine_backward
-        diff.backbone._engine_backward = lambda S, grad, mode, orig=orig, bb=diff.backbone: (seen.append((S["hf"].shape[0], bool(S.get("stream_compact")))), splits.append((compact, split, S.get("head_groups"))), orig(bb, S, grad, mode))[2]
+        diff.backbone._engine_backward = lambda S, grad, mode, orig=orig, bb=diff.backbone: (seen.append((S.hf.shape[0], bool(S.stream_compact))), splits.append((compact, split, S.head_groups)), orig(bb, S, grad, mode))[2]
         torch.manual_seed(g.case["step_seed"])
         batch = {k: torch.cat([v] * 4) for k, v in g.batch().items()}   # 512 rows: the padded [MASK] row list is shorter than the batch
         out = diff.training_step(batch, 1)
@@ -255,3 +255,37 @@ def test_low_precision_loss_is_accepted_and_changes_nothing(fake_k):
         out = diff2.training_step(g.batch(), 1)
         vals.append((float(out.loss.detach()), out.nlls.detach().clone()))
     assert vals[0][0] == vals[1][0] and torch.equal(vals[0][1], vals[1][1])
+
+
+def test_saved_state_is_freed_by_the_backward_without_the_cyclic_collector(fake_k):
+    """Activation checkpointing re-runs `_block_forward` from the saved state; nothing callable is kept in that state and it does not refer to itself, so once the
+    backward has run and the outputs are gone the saved activations (here the fp32 residual stream `x_final`) are freed by reference counting alone."""
+    import gc
+    import weakref
+
+    from unidisc_amd.dit import DIT
+
+    g = Golden("c_large")
+    diff = build_product(g, device="cpu")
+    diff.rng_device = "cpu"
+    diff.backbone.use_gradient_checkpointing = True
+    refs = []
+    orig = DIT._engine_forward
+
+    def spy(inp, mode, save):
+        out, S = orig(diff.backbone, inp, mode, save)
+        refs.append(weakref.ref(S.x_final))
+        return out, S
+
+    diff.backbone._engine_forward = spy
+    gc.collect()
+    gc.disable()
+    try:
+        torch.manual_seed(g.case["step_seed"])
+        out = diff.training_step(g.batch(), 1)
+        assert len(refs) == 1 and refs[0]() is not None     # (the graph is alive: so is what it saved)
+        out.loss.backward()
+        del out
+        assert refs[0]() is None, "the engine's saved state outlives its backward: something in it refers back to it"
+    finally:
+        gc.enable()

@@ -19,6 +19,7 @@ from __future__ import annotations
 import math
 import types
 import os
+from dataclasses import dataclass
 from typing import Dict, List, Optional
 
 import weakref
@@ -220,6 +221,90 @@ class _Lin:
 
 
 # ------------------------------------------------------------------------------------------------
+# the engine's records
+# ------------------------------------------------------------------------------------------------
+@dataclass
+class _KVRead:
+    """Attend to a K / V cache: K, V per block [B, Lmax, d]; slot0: where this call's rows go; Lk: the slots the queries see; split: the conditioning cache's
+    form (small batches, the keys split over workgroups where the plan says so) with its workspace `ws`."""
+    K: list
+    V: list
+    slot0: int
+    Lk: int
+    split: bool = False
+    ws: Optional[torch.Tensor] = None
+
+
+@dataclass
+class _EngineInputs:
+    """What one engine forward runs on.  Every caller builds this record; what a caller does not say is off."""
+    indices: torch.Tensor
+    sigma: Optional[torch.Tensor] = None
+    modality: Optional[torch.Tensor] = None
+    sample_ids: Optional[torch.Tensor] = None
+    x0: Optional[torch.Tensor] = None               # "logp": the clean tokens
+    restrict: bool = False                          # "logp": restrict_modality
+    save: bool = False                              # keep what the backward reads (grad mode is off inside Function.forward, so the caller decides)
+    block_mask: object = None                       # a ModalityMask (anything else is ignored)
+    key_mask: Optional[torch.Tensor] = None         # the key-padding mask of model.use_attention_mask
+    plan_ids: Optional[torch.Tensor] = None         # take the [MASK] row selection from this tensor instead of `indices`
+    ar_shift: bool = False                          # "logp": the AR baseline's shifted head
+    rope: Optional[tuple] = None                    # (cos, sin) rows of the full-length tables (the cached paths)
+    kv_sink: Optional[list] = None                  # per block (K, V): every position's post-rope k and its v go there
+    kv_read: Optional[_KVRead] = None
+    head_out: Optional[torch.Tensor] = None         # "logits": the head on each row's last position only, into this buffer (KV-cache prefill)
+
+
+class _Record:
+    """Named fields only - a misspelt one is an AttributeError, not a silent None - and every field None until it is set."""
+    __slots__ = ()
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    def __getattr__(self, name):   # (reached only by a name that has no value yet: None for a field, an error for anything else)
+        if name not in self.__slots__:
+            raise AttributeError(f"{type(self).__name__} has no field {name!r}")
+
+
+class _Saved(_Record):
+    """One forward's context, and with `save` what its backward reads.  It holds tensors and plain values only - nothing callable, nothing that refers back to
+    it - so dropping the record frees everything at once."""
+    __slots__ = ("mode", "save", "ckpt", "B", "L", "nt", "ids", "modality", "emb_mod", "sid", "doc_ranges", "p_drop", "p_attn", "seed0", "dgrad_form", "cos", "sin",
+                 "cnt_j", "kv_sink", "kv_read", "head_plan", "ada_cache", "blocks",                    # the forward's context (what _block_forward reads)
+                 "Bp", "te", "l1", "s1", "l2", "c", "any_img",                                        # the sigma map
+                 "x_final", "hf", "rstdf", "meanf", "fmod", "logits", "head_rows", "ids_h", "x0", "ce_mod", "restrict", "lse_ce", "stream_compact", "head_chunk",
+                 "head_groups")                                                                        # the final layer and the head
+
+    def attn_drop_kw(self, i):
+        """Attention-probability dropout of block i: seed slot 4 i + 3 (4 i + 1, 4 i + 2 are the block's residual dropouts).  Passed only when p > 0, like
+        _attn_mask_kw.  The forward, the backward and the checkpointing recompute read this one method, so the three kernels of one attention regenerate one mask."""
+        return dict(dropout_p=self.p_attn, seed=self.seed0 + 4 * i + 3) if self.p_attn > 0.0 else {}
+
+
+class _BlockActs(_Record):
+    """What one block's backward reads.  Under activation checkpointing (`ckpt`) only the block's input `x_in` and the compacted row list `rows_c`."""
+    __slots__ = ("ckpt", "x_in", "rows_c", "mod", "h1", "rstd1", "mean1", "qkv", "qkr", "qstats", "o", "lse", "a_out", "rstd_a", "mean_a", "x_mid", "h2", "rstd2",
+                 "mean2", "u1", "g", "u2", "rstd_m", "mean_m", "o_c")
+
+
+class _PendingNorm(_Record):
+    """Without adaLN every pre-norm backward is immediately followed by the backward of the residual branch that produced the norm's input, on the dx it has just
+    updated: the pair runs as ONE fused pass (K.norm_residual_bwd; adaLN-Zero, round 5: its modulated / gated form K.norm_residual_bwd_ada where that kernel covers
+    the shape).  This record carries the norm half to the branch that consumes it: the norm's operands, with adaLN its modulation `mod` and the chunks `mod_idx` =
+    (shift, scale) whose gradients go into `dmod`, and `finish`: the block (n_blocks: the final layer) whose gradient range is reported, and whose activations
+    are dropped, only after that pass - the final norm and each block's norm1 pair with the MLP branch of the block below them in the schedule."""
+    __slots__ = ("dy", "x", "rstd", "mean", "w", "dw", "accumulate", "mod", "dmod", "mod_idx", "finish")
+
+
+class _Backward(_Record):
+    """The state of one backward pass: the flat gradient buffer and its per-parameter views G, the residual-stream gradient dx, the pending norm, and with adaLN
+    dc and the partial tiles the adaLN_modulation backwards leave for `_sigma_map_backward` (`ada_buf`, filled up to `ada_off`)."""
+    __slots__ = ("S", "nt", "flat", "G", "dx", "dc", "pend", "tc_fused", "ada_buf", "ada_off")
+
+
+# ------------------------------------------------------------------------------------------------
 # the module
 # ------------------------------------------------------------------------------------------------
 class DIT(nn.Module, _HubMixin):
@@ -231,12 +316,11 @@ class DIT(nn.Module, _HubMixin):
         self.autocast_dtype = dtype
         self.vocab_size, self.text_vocab_size, self.mask_index = vocab_size, text_vocab_size, mask_index
         self.time_conditioning = bool(cfg_get(config, "time_conditioning", False) or cfg_get(m, "force_time_conditioning", False))
-        self.use_gradient_checkpointing = cfg_get(tr, "use_gradient_checkpointing", False)
         # trainer.use_gradient_checkpointing (models/dit.py:1486-1490: every block is recomputed in the backward; the reference needs it on 48 GB parts): the
         # engine then keeps only each block's input (and the head's activations) and re-runs the block's forward right before its backward - same kernels,
         # same dropout seeds, bit-identical gradients (tests/test_engine_orchestration.py, tests/test_gpu_e2e.py).  Off, a block's activations stay resident
         # (0.92 GB per block at 1.4 B, B = 8: 22 GB of 288 GB), which is the faster choice whenever they fit.
-        self.use_gradient_checkpointing = bool(self.use_gradient_checkpointing)
+        self.use_gradient_checkpointing = bool(cfg_get(tr, "use_gradient_checkpointing", False))
         self.sandwich_normalization = cfg_get(m, "sandwich_normalization", False)
         self.static_img_sl, self.static_txt_sl = static_img_sl, static_txt_sl
         for flag, why in (("img_cond", "cross-attention image conditioning"), ("cond_label", "class-label conditioning"),
@@ -249,9 +333,7 @@ class DIT(nn.Module, _HubMixin):
         if self.use_kv_cache and cfg_get(m, "full_attention", True):
             raise NotImplementedError("unidisc_amd.DIT: model.use_kv_cache (inference KV cache) needs a causal backbone (model.full_attention=false, the AR "
                                       "baseline): a bidirectional block's keys change with every new token")
-        self._kv = None
-        self._mc = None
-        self._cc = None
+        self._kv = self._mc = self._cc = None
         # model.full_attention=false (models/dit.py:1118, the AR baseline of configs/experiments/ar.yaml): every block attends causally (sdpa is_causal=True,
         # :768 / :826 / :843) - the attention kernels' UDM_ATTN_CAUSAL form.  The reference never combines it with another mask: an attention_mask beside
         # is_causal is an SDPA error, and the packed / flex-mask paths sit inside `parameterization != "ar"`.
@@ -307,30 +389,7 @@ class DIT(nn.Module, _HubMixin):
         self.head_chunk_rows = int(cfg_get(m, "head_chunk_rows", 0) or 0)
         self.require_sample_ids = bool(cfg_get(data, "require_sample_ids", False))
         assert (self.txt_length + self.img_length == self.total_length) or self.multimodal_batches
-        D = self.head_dim
-        if self.rope_2d:  # models/dit.py:1203-1232
-            if not (self.multimodal_batches and self.modality_embed is not None):
-                raise NotImplementedError("unidisc_amd.DIT: rope_2d needs multimodal_batches and modality_embed (as in every shipped config)")
-            if self.require_sample_ids:  # interleaved / packed batches (:1209-1216): one table per supported image block, image-count embedding
-                for n_img, lf in self.IMG_BLOCKS:
-                    side = int(math.sqrt(n_img))
-                    emb = self._lumina(D, side, side, lf)
-                    self.register_buffer(f"rotary_cos_emb_img_{n_img}", emb.flatten(0, 1).real.contiguous(), persistent=False)
-                    self.register_buffer(f"rotary_sin_emb_img_{n_img}", emb.flatten(0, 1).imag.contiguous(), persistent=False)
-                self.img_count_embedding = nn.Parameter(torch.zeros((16, d)))
-            else:
-                side = int(math.sqrt(self.img_length))
-                assert side * side == self.img_length, f"seq_len_2d must be a square number, got {self.img_length}"
-                emb = self._lumina(D, side, side, cfg_get(m, "linear_factor", 1.0))
-                self.register_buffer("rotary_cos_emb_img", emb.flatten(0, 1).real.contiguous(), persistent=False)
-                self.register_buffer("rotary_sin_emb_img", emb.flatten(0, 1).imag.contiguous(), persistent=False)
-            c, s = rotary_table_1d(self.total_length, D)
-            self.register_buffer("rotary_cos_emb_txt", c, persistent=False)
-            self.register_buffer("rotary_sin_emb_txt", s, persistent=False)
-        else:  # :1234-1239
-            c, s = rotary_table_1d(self.total_length, D)
-            self.register_buffer("rotary_cos_emb", c, persistent=False)
-            self.register_buffer("rotary_sin_emb", s, persistent=False)
+        self._register_rotary_tables(cfg_get(m, "linear_factor", 1.0))
 
         self.blocks = nn.ModuleList([
             DDiTBlock(d, H, self.cond_dim, dropout=self.dropout, time_conditioning=self.time_conditioning, norm_type=self.norm_type,
@@ -360,6 +419,32 @@ class DIT(nn.Module, _HubMixin):
         self.recast_every_forward = True  # mirror autocast: fp32 master -> bf16 shadow on every training forward
         self.overlap_weight_cast = os.environ.get("UDM_OVERLAP_CAST", "0") != "0"   # opt-in: the casts on a side stream under the blocks before (measured: no gain, 96.1 vs 96.2 ms)
         self._shadow_versions = None
+
+    def _register_rotary_tables(self, linear_factor):
+        D = self.head_dim
+        if self.rope_2d:  # models/dit.py:1203-1232
+            if not (self.multimodal_batches and self.modality_embed is not None):
+                raise NotImplementedError("unidisc_amd.DIT: rope_2d needs multimodal_batches and modality_embed (as in every shipped config)")
+            if self.require_sample_ids:  # interleaved / packed batches (:1209-1216): one table per supported image block, image-count embedding
+                for n_img, lf in self.IMG_BLOCKS:
+                    side = int(math.sqrt(n_img))
+                    emb = self._lumina(D, side, side, lf)
+                    self.register_buffer(f"rotary_cos_emb_img_{n_img}", emb.flatten(0, 1).real.contiguous(), persistent=False)
+                    self.register_buffer(f"rotary_sin_emb_img_{n_img}", emb.flatten(0, 1).imag.contiguous(), persistent=False)
+                self.img_count_embedding = nn.Parameter(torch.zeros((16, self.hidden_size)))
+            else:
+                side = int(math.sqrt(self.img_length))
+                assert side * side == self.img_length, f"seq_len_2d must be a square number, got {self.img_length}"
+                emb = self._lumina(D, side, side, linear_factor)
+                self.register_buffer("rotary_cos_emb_img", emb.flatten(0, 1).real.contiguous(), persistent=False)
+                self.register_buffer("rotary_sin_emb_img", emb.flatten(0, 1).imag.contiguous(), persistent=False)
+            c, s = rotary_table_1d(self.total_length, D)
+            self.register_buffer("rotary_cos_emb_txt", c, persistent=False)
+            self.register_buffer("rotary_sin_emb_txt", s, persistent=False)
+        else:  # :1234-1239
+            c, s = rotary_table_1d(self.total_length, D)
+            self.register_buffer("rotary_cos_emb", c, persistent=False)
+            self.register_buffer("rotary_sin_emb", s, persistent=False)
 
     @staticmethod
     def _lumina(D, h, w, linear_factor):
@@ -511,8 +596,7 @@ class DIT(nn.Module, _HubMixin):
         rope = None
         if kv.cos is not None:
             rope = (kv.cos[:n].transpose(0, 1).contiguous(), kv.sin[:n].transpose(0, 1).contiguous())
-        inputs = dict(indices=idsp, sigma=None, modality=modp, sample_ids=None, x0=None, save=False, block_mask=None, key_mask=None,
-                      kv_sink=list(zip(kv.K, kv.V)), rope=rope, head_out=kv.logits if last_only else None)
+        inputs = _EngineInputs(indices=idsp, modality=modp, kv_sink=list(zip(kv.K, kv.V)), rope=rope, head_out=kv.logits if last_only else None)
         out, _ = self._engine_forward(inputs, "logits", save=False)
         kv.pos = n
         return out if last_only else out[:B]
@@ -710,8 +794,8 @@ class DIT(nn.Module, _HubMixin):
         if start_pos is not None:
             return self._forward_cached(indices, modality, int(start_pos), attention_mask, block_mask)
         params = self._ordered_params()
-        inputs = dict(indices=indices, sigma=sigma, modality=modality, sample_ids=sample_ids, x0=None, save=self._needs_grad(params),
-                      block_mask=block_mask if isinstance(block_mask, ModalityMask) else None, key_mask=self._key_mask(attention_mask, indices))
+        inputs = _EngineInputs(indices=indices, sigma=sigma, modality=modality, sample_ids=sample_ids, save=self._needs_grad(params),
+                               block_mask=block_mask if isinstance(block_mask, ModalityMask) else None, key_mask=self._key_mask(attention_mask, indices))
         return _DitFn.apply(self, "logits", inputs, *params)
 
     @torch.no_grad()
@@ -761,8 +845,8 @@ class DIT(nn.Module, _HubMixin):
         ar_shift (the AR baseline, model.py:717-781 + :935-967; pass xt = x0): column r of the result is log p(x0[:, r+1] | x0[:, :r+1]) - the [MASK] id and,
         with restrict_modality, the ids of the other modality than the TARGET's excluded - and the last column, which has no target, is 0 (zero gradient)."""
         params = self._ordered_params()
-        inputs = dict(indices=xt, sigma=sigma, modality=modality, sample_ids=sample_ids, x0=x0, restrict=restrict_modality, save=self._needs_grad(params),
-                      block_mask=block_mask, key_mask=self._key_mask(attention_mask, xt), ar_shift=bool(ar_shift))
+        inputs = _EngineInputs(indices=xt, sigma=sigma, modality=modality, sample_ids=sample_ids, x0=x0, restrict=bool(restrict_modality),
+                               save=self._needs_grad(params), block_mask=block_mask, key_mask=self._key_mask(attention_mask, xt), ar_shift=bool(ar_shift))
         return _DitFn.apply(self, "logp", inputs, *params)
 
     @torch.no_grad()
@@ -787,8 +871,8 @@ class DIT(nn.Module, _HubMixin):
             if modality_cache is not None:
                 raise ValueError("unidisc_amd.DIT.forward_masked_logits: modality_cache and conditioning_cache are two different caches - pass one")
             return self._conditioning_forward(xt, sigma, modality, sample_ids, plan_ids, block_mask, conditioning_cache, int(cache_row0))
-        inputs = dict(indices=xt, sigma=sigma, modality=modality, sample_ids=sample_ids, x0=None, save=False, plan_ids=plan_ids,
-                      block_mask=block_mask if isinstance(block_mask, ModalityMask) else None)
+        inputs = _EngineInputs(indices=xt, sigma=sigma, modality=modality, sample_ids=sample_ids, plan_ids=plan_ids,
+                               block_mask=block_mask if isinstance(block_mask, ModalityMask) else None)
         mc = self._mc
         if modality_cache is not None:
             if modality_cache not in ("build", "read"):
@@ -803,9 +887,9 @@ class DIT(nn.Module, _HubMixin):
                 raise ValueError(f"unidisc_amd.DIT.forward_masked_logits(modality_cache={modality_cache!r}): xt {tuple(xt.shape)}, the cache serves "
                                  f"[{mc.B}, {mc.L}] with {mc.Lt} text positions")
         if modality_cache == "build":
-            inputs["kv_sink"] = list(zip(mc.K, mc.V))
+            inputs.kv_sink = list(zip(mc.K, mc.V))
             out, S = self._engine_forward(inputs, "rows", save=False)
-            mc.cos, mc.sin = S["cos"], S["sin"]                                   # the full-length rotary tables ([L, D/2], or per sample [B, L, D/2])
+            mc.cos, mc.sin = S.cos, S.sin                                         # the full-length rotary tables ([L, D/2], or per sample [B, L, D/2])
             mc.mod = modality.to(torch.int64).contiguous() if modality is not None else None
             mc.built = True
             return out
@@ -814,11 +898,10 @@ class DIT(nn.Module, _HubMixin):
                 raise RuntimeError("unidisc_amd.DIT.forward_masked_logits(modality_cache=\"read\"): the cache holds no image keys yet (no \"build\" step ran)")
             Lt = mc.Lt
             if mc.mod is not None:   # row p takes exactly the modality id and the rotary row of the full-length forward
-                inputs["modality"] = mc.mod[:, :Lt].contiguous()
-            inputs["rope"] = (mc.cos[..., :Lt, :].contiguous(), mc.sin[..., :Lt, :].contiguous())
-            inputs["kv_read"] = dict(K=mc.K, V=mc.V, slot0=0, Lk=mc.L)
-        out, _ = self._engine_forward(inputs, "rows", save=False)
-        return out
+                inputs.modality = mc.mod[:, :Lt].contiguous()
+            inputs.rope = (mc.cos[..., :Lt, :].contiguous(), mc.sin[..., :Lt, :].contiguous())
+            inputs.kv_read = _KVRead(K=mc.K, V=mc.V, slot0=0, Lk=mc.L)
+        return self._engine_forward(inputs, "rows", save=False)[0]
 
     def _conditioning_forward(self, xt, sigma, modality, sample_ids, plan_ids, block_mask, what, row0):
         name = f"unidisc_amd.DIT.forward_masked_logits(conditioning_cache={what!r})"
@@ -834,14 +917,14 @@ class DIT(nn.Module, _HubMixin):
             raise ValueError(f"{name}: xt {tuple(xt.shape)} at cache row {row0}; the cache serves {cc.R} rows of length {cc.L}, in passes of {cc.R} or {cc.B} rows, "
                              f"with a generated slice of {cc.Lq} positions")
         dev = xt.device
-        inputs = dict(indices=xt, sigma=sigma, modality=modality, sample_ids=None, x0=None, save=False, plan_ids=plan_ids, block_mask=None)
+        inputs = _EngineInputs(indices=xt, sigma=sigma, modality=modality, plan_ids=plan_ids)
         span = range(row0, row0 + rows)
         if what == "build":
             on = torch.ones(rows, dtype=torch.bool, device=dev)
-            inputs["block_mask"] = ModalityMask(on if cc.given == "text" else ~on, on if cc.given == "image" else ~on, cc.Lt)
-            inputs["kv_sink"] = [(k[row0:row0 + rows], v[row0:row0 + rows]) for k, v in zip(cc.K, cc.V)]
+            inputs.block_mask = ModalityMask(on if cc.given == "text" else ~on, on if cc.given == "image" else ~on, cc.Lt)
+            inputs.kv_sink = [(k[row0:row0 + rows], v[row0:row0 + rows]) for k, v in zip(cc.K, cc.V)]
             out, S = self._engine_forward(inputs, "rows", save=False)
-            cos, sin = S["cos"], S["sin"]                # [L, D/2], or per sample [rows, L, D/2]
+            cos, sin = S.cos, S.sin                      # [L, D/2], or per sample [rows, L, D/2]
             if cos.dim() == 3:                           # per-sample tables: kept per cache row
                 if cc.cos is None or cc.cos.dim() != 3:
                     cc.cos, cc.sin = cos.new_zeros((cc.R,) + tuple(cos.shape[1:])), sin.new_zeros((cc.R,) + tuple(sin.shape[1:]))
@@ -864,11 +947,10 @@ class DIT(nn.Module, _HubMixin):
             cc.sliced[(row0, rows)] = (None if cc.mod is None else cc.mod[row0:row0 + rows, sl].contiguous(), pick(cc.cos), pick(cc.sin))
         mod_sl, cos_sl, sin_sl = cc.sliced[(row0, rows)]
         if mod_sl is not None:
-            inputs["modality"] = mod_sl
-        inputs["rope"] = (cos_sl, sin_sl)
-        inputs["kv_read"] = dict(K=[k[row0:row0 + rows] for k in cc.K], V=[v[row0:row0 + rows] for v in cc.V], slot0=sl.start, Lk=cc.L, split=True, ws=cc.ws)
-        out, _ = self._engine_forward(inputs, "rows", save=False)
-        return out
+            inputs.modality = mod_sl
+        inputs.rope = (cos_sl, sin_sl)
+        inputs.kv_read = _KVRead(K=[k[row0:row0 + rows] for k in cc.K], V=[v[row0:row0 + rows] for v in cc.V], slot0=sl.start, Lk=cc.L, split=True, ws=cc.ws)
+        return self._engine_forward(inputs, "rows", save=False)[0]
 
     @staticmethod
     def _needs_grad(params):
@@ -970,315 +1052,286 @@ class DIT(nn.Module, _HubMixin):
             return cos, sin
         return self.rotary_cos_emb[:L].contiguous(), self.rotary_sin_emb[:L].contiguous()
 
-    def _engine_forward(self, inp, mode, save):
-        ids = inp["indices"]
-        K.require_gpu(ids)
-        dev = ids.device
-        B, L = ids.shape
-        M, d, H, D = B * L, self.hidden_size, self.n_heads, self.head_dim
-        if M % 8 != 0:
-            raise ValueError(f"unidisc_amd.DIT: batch*length = {M} must be a multiple of 8")
-        nt = K.norm_id(self.norm_type)
-        tc, sw = self.time_conditioning, self.sandwich_normalization
-        train = self.training
-        self.refresh_weight_shadows(rows=M)
-        lin = self._lins
-        p_drop = self.dropout if train else 0.0
-        if train and save:   # only training forwards advance the dropout stream (eval / sampler passes draw no dropout masks)
+    def _engine_forward(self, inp: _EngineInputs, mode, save):
+        """-> (by `mode`: "logits" [B, L, V] / "logp" log p(x0 | xt) [B, L] through the fused head / "rows" the sampler's [MASK]-row logits; the forward's _Saved)"""
+        K.require_gpu(inp.indices)
+        (B, L), dev = inp.indices.shape, inp.indices.device
+        if (B * L) % 8 != 0:
+            raise ValueError(f"unidisc_amd.DIT: batch*length = {B * L} must be a multiple of 8")
+        S = _Saved(mode=mode, save=save, B=B, L=L, nt=K.norm_id(self.norm_type), kv_sink=inp.kv_sink, kv_read=inp.kv_read, ada_cache={}, blocks=[],
+                   ckpt=bool(self.use_gradient_checkpointing) and save)
+        self.refresh_weight_shadows(rows=B * L)
+        S.p_drop = self.dropout if self.training else 0.0
+        if self.training and save:   # only training forwards advance the dropout stream (eval / sampler passes draw no dropout masks)
             self._fwd_count += 1
-        seed0 = ((torch.initial_seed() * 1000003 + self._fwd_count * 4096) ^ (self._dropout_rank() * 0x9E3779B97F4A7C15)) & ((1 << 62) - 1)
-
-        ids = ids.contiguous().view(-1).to(torch.int64)
-        modality = inp["modality"]
-        mod_flat = modality.contiguous().view(-1).to(torch.int64) if modality is not None else None
-        sample_ids = inp["sample_ids"]
-        sid = sample_ids.contiguous().to(torch.int64) if sample_ids is not None else None
-        if self.modality_embed is not None and mod_flat is None:
+        S.seed0 = ((torch.initial_seed() * 1000003 + self._fwd_count * 4096) ^ (self._dropout_rank() * 0x9E3779B97F4A7C15)) & ((1 << 62) - 1)
+        S.ids = inp.indices.contiguous().view(-1).to(torch.int64)
+        S.modality = inp.modality.contiguous().view(-1).to(torch.int64) if inp.modality is not None else None
+        S.emb_mod = S.modality
+        if self.modality_embed is not None and S.modality is None:
             if self.multimodal_batches:
                 raise ValueError("unidisc_amd.DIT: modality_embed with multimodal_batches needs the `modality` argument")
-            pos = torch.arange(L, device=dev)  # static slices (models/dit.py:1409-1411)
-            is_img = torch.zeros(L, dtype=torch.bool, device=dev)
-            is_img[self.static_img_sl] = True
-            emb_mod = is_img.to(torch.int64)[None].expand(B, L).contiguous().view(-1)
-            del pos
-        else:
-            emb_mod = mod_flat
-        bm = inp.get("block_mask")
-        if self.causal and (sid is not None or isinstance(bm, ModalityMask) or inp.get("key_mask") is not None):
+            S.emb_mod = self._static_modality(B, L, dev).view(-1)   # static slices (models/dit.py:1409-1411)
+        raw_sid = self._attention_masks(S, inp, dev)
+        S.dgrad_form = {name: lin.dgrad_form() for name, lin in self._lins.items()}   # NN vs NT per Linear, fixed by THIS forward's shadows (not re-derived at backward time)
+        ce = self._plan_head(S, inp, dev)
+        x = K.embedding_fwd(S.ids, self.vocab_embed.embedding.detach(), S.emb_mod if self.modality_embed is not None else None,
+                            self.modality_embed.embedding.detach() if self.modality_embed is not None else None)
+        self._rotary_rows(S, inp, x, raw_sid)
+        if self.time_conditioning:
+            self._sigma_map_forward(S, inp.sigma, dev)
+        pre = None
+        for i in range(self.n_blocks):
+            x, pre, R = self._block_forward(S, i, x, pre)
+            S.blocks.append(R)   # (None unless `save`)
+        self._await_cast("head")
+        fmod = self._ada_mod(S, self.n_blocks) if self.time_conditioning else None   # [Bp, 2d]
+        hf, rstdf, meanf = pre if pre is not None else K.norm_fwd(x, self.output_layer.norm_final.weight.detach(), S.nt, L, mod=fmod, mod_idx=(0, 1),
+                                                                  modality=S.modality, any_img=S.any_img)
+        S.ada_cache = S.ada_cache if S.ckpt else None   # (only the checkpointing recompute reads it again)
+        if save:
+            S.x_final, S.rstdf, S.meanf, S.fmod = x, rstdf, meanf, fmod
+        if mode == "rows":
+            return self._head_rows(S, hf), S
+        if mode == "logits":
+            return self._head_logits(S, hf, inp.head_out), S
+        return self._head_logp(S, inp, hf, ce), S
+
+    def _attention_masks(self, S, inp, dev):
+        """Sample ids -> mask codes -> key mask -> doc_ranges: what the attention kernels take in their sample-id slot (S.sid, S.doc_ranges), the attention-dropout
+        probability (S.p_attn), the combinations that are refused.  Returns the document ids as given (the per-sample rotary positions need them without class bits)."""
+        sid = raw_sid = inp.sample_ids.contiguous().to(torch.int64) if inp.sample_ids is not None else None
+        bm, km = inp.block_mask, inp.key_mask
+        if self.causal and (sid is not None or isinstance(bm, ModalityMask) or km is not None):
             raise NotImplementedError("unidisc_amd.DIT: causal attention (model.full_attention=false) with packed sample_ids, a ModalityMask or an attention mask - "
                                       "the reference never combines is_causal with another mask")
-        doc_ranges = K.attention_doc_ranges(sid) if sid is not None else None   # once per step, shared by every block's forward and backward
+        S.doc_ranges = K.attention_doc_ranges(sid) if sid is not None else None   # once per step, shared by every block's forward and backward
         if isinstance(bm, ModalityMask) and sid is None:
             # modality attention dropout (model.py:863-878): an asymmetric per-sample mask, carried to the attention kernels as mask codes in
             # the sample-id slot (class bits: no tile skipping, every tile takes the per-element test)
-            sid = K.modality_mask_codes(bm.txt_drop.to(dev), bm.img_drop.to(dev), bm.txt_length, L)
-        raw_sid = sid if sample_ids is not None else None   # (document ids as given: the per-sample rotary positions below need them without class bits)
-        km = inp.get("key_mask")
+            sid = K.modality_mask_codes(bm.txt_drop.to(dev), bm.img_drop.to(dev), bm.txt_length, S.L)
         if km is not None:
             # key-padding mask (model.use_attention_mask): padded keys get a key class (4) no query mask contains; positions without other codes become
             # sample 0 / key class 1 / query mask "classes 1 | 2".  Class bits switch tile skipping off (doc_ranges = None): every tile takes the element test.
-            km = km.to(dev).reshape(B, L)
-            base = sid if sid is not None else torch.zeros((B, L), dtype=torch.int64, device=dev)
-            kbits = (base >> 32) & 0xff
-            qbits = (base >> 40) & 0xff
+            km = km.to(dev).reshape(S.B, S.L)
+            base = sid if sid is not None else torch.zeros((S.B, S.L), dtype=torch.int64, device=dev)
+            kbits, qbits = (base >> 32) & 0xff, (base >> 40) & 0xff
             kbits = torch.where(km, torch.where(kbits == 0, torch.ones_like(kbits), kbits), torch.full_like(kbits, 4))
             qbits = torch.where(qbits == 0, torch.full_like(qbits, 3), qbits)
             sid = ((base & 0xffffffff) | (kbits << 32) | (qbits << 40)).contiguous()
-            doc_ranges = None
-        p_attn = self.attn_dropout if train else 0.0
-        if p_attn > 0.0 and sid is not None:
+            S.doc_ranges = None
+        S.sid = sid
+        S.p_attn = self.attn_dropout if self.training else 0.0
+        if S.p_attn > 0.0 and sid is not None:
             raise NotImplementedError("unidisc_amd.DIT: model.attn_dropout with packed sample_ids, a ModalityMask or an attention mask - the reference's "
                                       "FlexAttention path applies no attention dropout")
-        S = dict(B=B, L=L, ids=ids, modality=mod_flat, emb_mod=emb_mod, sid=sid, p_drop=p_drop, seed0=seed0, blocks=[])
-        # attention-probability dropout of block i: seed slot 4 i + 3 (4 i + 1, 4 i + 2 are the block's residual dropouts).  The keywords are passed only
-        # when p > 0, like _attn_mask_kw: every other call into the attention entry points is what it was.  The backward and the checkpointing recompute
-        # read the same function, so the three kernels of one attention regenerate one mask.
-        S["attn_drop_kw"] = (lambda i: dict(dropout_p=p_attn, seed=seed0 + 4 * i + 3)) if p_attn > 0.0 else (lambda i: {})
-        S["doc_ranges"] = doc_ranges
-        S["dgrad_form"] = {name: lin.dgrad_form() for name, lin in self._lins.items()}   # NN vs NT per Linear, fixed by THIS forward's shadows (not re-derived at backward time)
-        # SUBS: only [MASK] rows have a non-zero log-probability (model.py:621-658), so in "logp" mode the vocabulary head (GEMM fwd,
-        # dgrad, wgrad and the cross-entropy) runs on the masked rows only.  Their number is data dependent: it is counted on a side
-        # stream NOW and only read back right before the head, when the host has already queued every block of this forward -- the
-        # device never waits for the host.
-        plan_ids = inp.get("plan_ids")
-        ar = mode == "logp" and bool(inp.get("ar_shift", False))
-        if ar:   # the AR baseline's shifted head: row r predicts token r + 1 (ar_head_operands)
-            ar_mod = modality.reshape(B, L) if modality is not None else (self._static_modality(B, L, dev) if bool(inp.get("restrict", False)) else None)
-            ce_ids, ce_x0, ce_mod_ar = ar_head_operands(inp["x0"].reshape(B, L), ar_mod, self.mask_index)
-        split_ok = (mode == "logp" and self.compact_head and self.split_head and bool(inp.get("restrict", False)) and mod_flat is not None and plan_ids is None
-                    and 0 < self.text_vocab_size < self.vocab_size and self.head_chunk_rows <= 0)
-        plan_src, plan_mod = (ce_ids, ce_mod_ar) if ar else (ids if plan_ids is None else plan_ids.reshape(ids.shape), mod_flat)
-        head_plan = (self._plan_masked_rows(plan_src, plan_mod if split_ok else None)
-                     if ((mode == "logp" and self.compact_head) or mode == "rows") else None)
+        if S.kv_read is not None and (sid is not None or S.save or S.kv_sink is not None or self.causal):
+            raise NotImplementedError("unidisc_amd.DIT: the cache-reading forward is an inference path without masks (no sample ids, ModalityMask, attention mask)")
+        return raw_sid
 
-        x = K.embedding_fwd(ids, self.vocab_embed.embedding.detach(), emb_mod if self.modality_embed is not None else None,
-                            self.modality_embed.embedding.detach() if self.modality_embed is not None else None)
+    def _plan_head(self, S, inp, dev):
+        """SUBS: only [MASK] rows have a non-zero log-probability (model.py:621-658), so in "logp" mode the vocabulary head (GEMM fwd, dgrad, wgrad and the
+        cross-entropy) runs on the masked rows only.  Their number is data dependent: it is counted on a side stream NOW (S.head_plan) and only read back right
+        before the head, when the host has already queued every block of this forward - the device never waits for the host.  Returns the operands of the AR
+        baseline's shifted head (ar_head_operands: row r predicts token r + 1), or None."""
+        B, L, mode, restrict, ce = S.B, S.L, S.mode, bool(inp.restrict), None
+        if mode == "logp" and bool(inp.ar_shift):
+            ar_mod = inp.modality.reshape(B, L) if inp.modality is not None else (self._static_modality(B, L, dev) if restrict else None)
+            ce = ar_head_operands(inp.x0.reshape(B, L), ar_mod, self.mask_index)
+        split_ok = (mode == "logp" and self.compact_head and self.split_head and restrict and S.modality is not None and inp.plan_ids is None
+                    and 0 < self.text_vocab_size < self.vocab_size and self.head_chunk_rows <= 0)
+        plan_src, plan_mod = (ce[0], ce[2]) if ce is not None else (S.ids if inp.plan_ids is None else inp.plan_ids.reshape(S.ids.shape), S.modality)
+        if (mode == "logp" and self.compact_head) or mode == "rows":
+            S.head_plan = self._plan_masked_rows(plan_src, plan_mod if split_ok else None)
+        return ce
+
+    def _rotary_rows(self, S, inp, x, raw_sid):
+        """The rotary tables of this forward's rows (S.cos, S.sin); packed batches also add the image-count embedding to x."""
         if self.rope_2d and self.require_sample_ids:
             if raw_sid is None:
                 raise ValueError("unidisc_amd.DIT: data.require_sample_ids needs sample_ids")
-            cos, sin, count_idx = self._rotary_interleaved(modality.to(torch.int64), raw_sid)
+            S.cos, S.sin, count_idx = self._rotary_interleaved(inp.modality.to(torch.int64), raw_sid)
             # x[b, l] += img_count_embedding[j] on the positions of supported image blocks.  Static shapes (no nonzero(): that is a host read in the step's preamble):
             # every position gathers a row of the table extended by one zero row, positions without an image index take that row
             n_cnt = self.img_count_embedding.shape[0]
-            cnt_j = torch.where(count_idx.view(-1) >= 0, count_idx.view(-1), torch.full_like(count_idx.view(-1), n_cnt))
+            S.cnt_j = torch.where(count_idx.view(-1) >= 0, count_idx.view(-1), torch.full_like(count_idx.view(-1), n_cnt))
             tab = torch.cat([self.img_count_embedding.detach().to(x.dtype), torch.zeros((1, x.shape[1]), dtype=x.dtype, device=x.device)], 0)
-            x.add_(tab.index_select(0, cnt_j))
-            S["cnt_j"] = cnt_j
-        elif inp.get("rope") is not None:   # (KV-cache prefill: rows of the full-length tables)
-            cos, sin = inp["rope"]
+            x.add_(tab.index_select(0, S.cnt_j))
+        elif inp.rope is not None:   # (the cached paths: rows of the full-length tables)
+            S.cos, S.sin = inp.rope
         else:
-            cos, sin = self._rotary(modality, L)
-        S["cos"], S["sin"] = cos, sin
-        kv_sink = inp.get("kv_sink")
-        kv_read = inp.get("kv_read")   # attend to a K / V cache: dict(K, V: per block [B, Lmax, d]; slot0: where this call's rows go; Lk: the slots the queries see)
-        if kv_read is not None and (sid is not None or save or kv_sink is not None or self.causal):
-            raise NotImplementedError("unidisc_amd.DIT: the cache-reading forward is an inference path without masks (no sample ids, ModalityMask, attention mask)")
+            S.cos, S.sin = self._rotary(inp.modality, S.L)
 
-        any_img = None
-        if tc:
-            sigma = inp["sigma"]
-            if sigma is None:
-                raise ValueError("unidisc_amd.DIT: time_conditioning needs sigma")
-            sigma = sigma.reshape(-1).to(F32).contiguous()
-            Bp = _ceil(B, 8)
-            te = torch.zeros((Bp, 256), dtype=BF16, device=dev)
-            K.timestep_embedding(sigma, te, B, 256)
-            self._await_cast("pre")
-            l1 = K.gemm_nt(te, lin["sig0"].w16, N=lin["sig0"].out, epilogue=K.EPI_BIAS, bias=lin["sig0"].bias.detach())
-            s1 = K.silu_fwd(l1)
-            l2 = K.gemm_nt(s1, lin["sig2"].w16, N=lin["sig2"].out, epilogue=K.EPI_BIAS, bias=lin["sig2"].bias.detach())
-            c = K.silu_fwd(l2)
-            if mod_flat is not None:
-                any_img = (mod_flat != 0).any().to(torch.int32).reshape(1)
-            S.update(Bp=Bp, te=te, l1=l1, s1=s1, l2=l2, c=c, any_img=any_img)
+    def _sigma_map_forward(self, S, sigma, dev):
+        """c = silu(W2 silu(W0 te + b0) + b2), the conditioning every adaLN_modulation reads"""
+        if sigma is None:
+            raise ValueError("unidisc_amd.DIT: time_conditioning needs sigma")
+        lin, sigma = self._lins, sigma.reshape(-1).to(F32).contiguous()
+        S.Bp = _ceil(S.B, 8)
+        S.te = torch.zeros((S.Bp, 256), dtype=BF16, device=dev)
+        K.timestep_embedding(sigma, S.te, S.B, 256)
+        self._await_cast("pre")
+        S.l1 = K.gemm_nt(S.te, lin["sig0"].w16, N=lin["sig0"].out, epilogue=K.EPI_BIAS, bias=lin["sig0"].bias.detach())
+        S.s1 = K.silu_fwd(S.l1)
+        S.l2 = K.gemm_nt(S.s1, lin["sig2"].w16, N=lin["sig2"].out, epilogue=K.EPI_BIAS, bias=lin["sig2"].bias.detach())
+        S.c = K.silu_fwd(S.l2)
+        if S.modality is not None:
+            S.any_img = (S.modality != 0).any().to(torch.int32).reshape(1)
 
-        ckpt = bool(self.use_gradient_checkpointing) and save
-        ada_cache = {}
+    def _ada_mod(self, S, i):
+        """adaLN_modulation(c) of block i (i == n_blocks: the final layer's), computed once per forward: the residual add in front of a modulated norm needs it
+        one block early"""
+        key = str(i) if i < self.n_blocks else "head"
+        if key not in S.ada_cache:
+            self._await_cast(i if i < self.n_blocks else "head")
+            a = self._lins[f"{key}.ada"]
+            S.ada_cache[key] = K.gemm_nt(S.c, a.w16, N=a.out, epilogue=K.EPI_BIAS, bias=a.bias.detach())   # [Bp, 6d] (final layer: [Bp, 2d]) bf16
+        return S.ada_cache[key]
 
-        def ada_mod(i):
-            """adaLN_modulation(c) of block i (i == n_blocks: the final layer's), computed once: the residual add in front of a modulated norm needs it one block early"""
-            key = str(i) if i < self.n_blocks else "head"
-            if key not in ada_cache:
-                self._await_cast(i if i < self.n_blocks else "head")
-                a = lin[f"{key}.ada"]
-                ada_cache[key] = K.gemm_nt(S["c"], a.w16, N=a.out, epilogue=K.EPI_BIAS, bias=a.bias.detach())   # [Bp, 6d] (final layer: [Bp, 2d]) bf16
-            return ada_cache[key]
-
-        def block_fwd(i, x, pre, last_rows=None, recompute=False):
-            """One DiT block: x [M, d] fp32 -> (x_out, pre_out, R).  R holds what the block's backward reads.  `recompute` (activation checkpointing,
-            models/dit.py:1486-1490): the backward re-runs the block from its saved input - same kernels, same dropout seeds, the fused next-block pre-norm
-            replaced by the block's own norm kernel (bit-identical) - so only x_in (and the compacted row list of the last block) is kept per block."""
-            blk = self.blocks[i]
-            R = {}
-            mod = None
-            if not recompute:
-                self._await_cast(i)
-            if tc:
-                mod = ada_mod(i)   # [Bp, 6d] bf16
-                R["mod"] = mod
-            if pre is not None:  # norm1 came fused out of the previous block's MLP residual add
-                h1, rstd1, mean1 = pre
+    def _block_forward(self, S, i, x, pre, last_rows=None, recompute=False):
+        """One DiT block: x [M, d] fp32 -> (x_out, pre_out, what the block's backward reads).  `recompute` (activation checkpointing, models/dit.py:1486-1490): the
+        backward re-runs the block from its saved input - same kernels, same dropout seeds, the fused next-block pre-norm replaced by the block's own norm kernel
+        (bit-identical) - so only x_in (and the compacted row list of the last block) is kept per block."""
+        blk, lin, tc, sw = self.blocks[i], self._lins, self.time_conditioning, self.sandwich_normalization
+        B, L, nt, mod_flat, any_img, p_drop, seed0 = S.B, S.L, S.nt, S.modality, S.any_img, S.p_drop, S.seed0
+        M, d, H, D = B * L, self.hidden_size, self.n_heads, self.head_dim
+        if not recompute:
+            self._await_cast(i)
+        mod = self._ada_mod(S, i) if tc else None   # [Bp, 6d] bf16
+        # (norm1 comes fused out of the previous block's MLP residual add where there is one)
+        h1, rstd1, mean1 = pre if pre is not None else K.norm_fwd(x, blk.norm1.weight.detach(), nt, L, mod=mod, mod_idx=(0, 1), modality=mod_flat, any_img=any_img)
+        qkv = K.gemm_nt(h1, lin[f"{i}.qkv"].w16, N=3 * d)
+        at, qn = blk.attention, self.qk_norm
+        qkr, qstats = K.qknorm_rope_fwd(qkv, S.cos, S.sin, L, D, q_scale=self.attn_q_scale, gq=at.q_norm.weight.detach() if qn else None,
+                                        bq=at.q_norm.bias.detach() if qn else None, gk=at.k_norm.weight.detach() if qn else None,
+                                        bk=at.k_norm.bias.detach() if qn else None)
+        if S.kv_sink is not None:   # KV-cache prefill: the post-rope k and the v of every position into cache slots [0, L)
+            S.kv_sink[i][0][:, :L].copy_(qkr.view(B, L, 2 * d)[:, :, d:])
+            S.kv_sink[i][1][:, :L].copy_(qkv.view(B, L, 3 * d)[:, :, 2 * d:])
+        kvr = S.kv_read
+        if kvr is not None:   # this call's post-rope k and v into cache slots [slot0, slot0 + L) (the kernel only reads), then the L queries against slots [0, Lk)
+            s0 = kvr.slot0
+            kvr.K[i][:, s0:s0 + L].copy_(qkr.view(B, L, 2 * d)[:, :, d:])
+            kvr.V[i][:, s0:s0 + L].copy_(qkv.view(B, L, 3 * d)[:, :, 2 * d:])
+            if kvr.split:
+                o, lse = K.attention_fwd_kv_split(qkr[:, :d], kvr.K[i], kvr.V[i], B, L, kvr.Lk, H, D, q_prescaled=True, ws=kvr.ws), None
             else:
-                h1, rstd1, mean1 = K.norm_fwd(x, blk.norm1.weight.detach(), nt, L, mod=mod, mod_idx=(0, 1), modality=mod_flat, any_img=any_img)
-            qkv = K.gemm_nt(h1, lin[f"{i}.qkv"].w16, N=3 * d)
-            at = blk.attention
-            qn_kw = dict(gq=at.q_norm.weight.detach() if self.qk_norm else None, bq=at.q_norm.bias.detach() if self.qk_norm else None,
-                         gk=at.k_norm.weight.detach() if self.qk_norm else None, bk=at.k_norm.bias.detach() if self.qk_norm else None)
-            qkr, qstats = K.qknorm_rope_fwd(qkv, cos, sin, L, D, q_scale=self.attn_q_scale, **qn_kw)
-            if kv_sink is not None:   # KV-cache prefill: the post-rope k and the v of every position into cache slots [0, L)
-                kv_sink[i][0][:, :L].copy_(qkr.view(B, L, 2 * d)[:, :, d:])
-                kv_sink[i][1][:, :L].copy_(qkv.view(B, L, 3 * d)[:, :, 2 * d:])
-            if kv_read is not None:   # this call's post-rope k and v into cache slots [slot0, slot0 + L) (the kernel only reads), then the L queries against slots [0, Lk)
-                s0 = kv_read["slot0"]
-                kv_read["K"][i][:, s0:s0 + L].copy_(qkr.view(B, L, 2 * d)[:, :, d:])
-                kv_read["V"][i][:, s0:s0 + L].copy_(qkv.view(B, L, 3 * d)[:, :, 2 * d:])
-                if kv_read.get("split"):   # the conditioning cache: small batches, the keys split over workgroups where the plan says so
-                    o, lse = K.attention_fwd_kv_split(qkr[:, :d], kv_read["K"][i], kv_read["V"][i], B, L, kv_read["Lk"], H, D, q_prescaled=True, ws=kv_read["ws"]), None
-                else:
-                    o, lse = K.attention_fwd_kv(qkr[:, :d], kv_read["K"][i], kv_read["V"][i], B, L, kv_read["Lk"], H, D, q_prescaled=True), None
-            else:
-                o, lse = K.attention_fwd(qkr, qkv, B, L, H, D, sid, S["doc_ranges"], q_prescaled=True, **self._attn_mask_kw, **S["attn_drop_kw"](i))
-            rows_c = last_rows
-            if not recompute and i + 1 == self.n_blocks and head_plan is not None and mode == "logp" and self.compact_last_block and not tc:
-                head_rows_c = self._masked_rows(head_plan, M)   # (the count was queued at the top of this forward: the host does not wait for the device here)
-                if head_rows_c is not None:
-                    rows_c = head_rows_c[0]
-            x_full, o_full = x, o
-            if rows_c is not None:   # from here on this block works on the [MASK] rows (+ padding) only
-                o = o.index_select(0, rows_c)
-                x = x.index_select(0, rows_c)
-                Mb = rows_c.numel()
-            else:
-                Mb = M
-            a_out = K.gemm_nt(o, lin[f"{i}.out"].w16, N=d)
-            # The next pre-norm is fused into the residual add (x_out is normalised while in registers) - with adaLN in its modulated form (round 5)
-            fuse_w2 = blk.norm2.weight.detach()
-            nkw2 = dict(next_mod=mod, next_mod_idx=(3, 4), next_modality=mod_flat, next_any_img=any_img) if tc else {}
-            if sw:  # x = x_skip + pre_residual_norm(attn)   (dit.py:993-994; no gate, no dropout)
-                res = K.residual_fwd(x, a_out, L, w_b=blk.pre_residual_norm.weight.detach(), norm_type=nt, next_w=fuse_w2, **nkw2)
-            else:   # bias_dropout_add_scale with gate_msa on every token (Attention.time_conditioning is never set: dit.py:533,884)
-                res = K.residual_fwd(x, a_out, L, norm_type=nt, mod=mod, gate_idx=2 if tc else None, p_drop=p_drop, seed=seed0 + 4 * i + 1, next_w=fuse_w2, **nkw2)
-            x_mid, rstd_a, mean_a = res[:3]
-            h2, rstd2, mean2 = res[3]
-            f1, f2 = lin[f"{i}.fc1"], lin[f"{i}.fc2"]
-            u1 = torch.empty((Mb, 4 * d), dtype=BF16, device=dev)
-            g = K.gemm_nt(h2, f1.w16, N=4 * d, epilogue=K.EPI_BIAS_GELU, bias=f1.bias.detach(), aux=u1)
-            u2 = K.gemm_nt(g, f2.w16, N=d, epilogue=K.EPI_BIAS, bias=f2.bias.detach())
-            # the consumer of x_out: norm1 of the next block, or norm_final (with adaLN: modulated by the NEXT block's / the final layer's adaLN output)
-            nxt_w = (self.blocks[i + 1].norm1.weight if i + 1 < self.n_blocks else self.output_layer.norm_final.weight).detach()
-            nkw = {}
-            if tc and not recompute:
-                nkw = dict(next_mod=ada_mod(i + 1), next_mod_idx=(0, 1), next_modality=mod_flat, next_any_img=any_img)
-            elif tc:      # (recomputation of ONE block in the backward: its output's norm is not needed)
-                nxt_w = None
-            res = K.residual_fwd(x_mid, u2, L, w_b=blk.post_ff_norm.weight.detach() if sw else None, norm_type=nt, mod=mod,
-                                 gate_idx=5 if tc else None, modality=mod_flat if tc else None, p_drop=p_drop, seed=seed0 + 4 * i + 2, next_w=nxt_w, **nkw)
-            x_out, rstd_m, mean_m = res[:3]
-            pre = res[3] if nxt_w is not None else None
-            if save:
-                if ckpt and not recompute:
-                    R = dict(x_in=x_full, rows_c=rows_c, ckpt=True)
-                else:
-                    R.update(x_in=x_full, h1=h1, rstd1=rstd1, mean1=mean1, qkv=qkv, qkr=qkr, qstats=qstats, o=o_full, lse=lse, a_out=a_out, rstd_a=rstd_a,
-                             mean_a=mean_a, x_mid=x_mid, h2=h2, rstd2=rstd2, mean2=mean2, u1=u1, g=g, u2=u2, rstd_m=rstd_m, mean_m=mean_m, rows_c=rows_c,
-                             o_c=o if rows_c is not None else None)
-            return x_out, pre, R
-
-        pre = None
-        for i in range(self.n_blocks):
-            x, pre, R = block_fwd(i, x, pre)
-            if save:
-                S["blocks"].append(R)
-        if ckpt:
-            S["block_fwd"] = block_fwd
-
-        fl = self.output_layer
-        fmod = None
-        self._await_cast("head")
-        if tc:
-            fmod = ada_mod(self.n_blocks)  # [Bp, 2d]
-        if pre is not None:
-            hf, rstdf, meanf = pre
+                o, lse = K.attention_fwd_kv(qkr[:, :d], kvr.K[i], kvr.V[i], B, L, kvr.Lk, H, D, q_prescaled=True), None
         else:
-            hf, rstdf, meanf = K.norm_fwd(x, fl.norm_final.weight.detach(), nt, L, mod=fmod, mod_idx=(0, 1), modality=mod_flat, any_img=any_img)
-        head = lin["head"]
-        V, Vp = self.vocab_size, head.outp
-        if mode == "rows":  # sampler: logits of the [MASK] rows only (no autograd); rows = their flat indices, padded to a multiple of 64
-            rows_p, n_masked = self._masked_rows(head_plan, M, always=True)
-            hf_h = hf.index_select(0, rows_p)
-            logits = torch.empty((hf_h.shape[0], Vp), dtype=BF16, device=dev)
-            K.gemm_nt(hf_h, head.w16, out=logits, N=V, epilogue=K.EPI_BIAS, bias=head.bias.detach())
-            return (logits, rows_p, n_masked), S
-        if mode == "logits" and inp.get("head_out") is not None:   # (KV-cache prefill: the head on each row's last position only)
-            last = torch.arange(B, device=dev) * L + (L - 1)
-            K.gemm_nt(hf.index_select(0, last), head.w16, out=inp["head_out"], N=V, epilogue=K.EPI_BIAS, bias=head.bias.detach())
-            return inp["head_out"], S
-        if mode == "logits":
-            logits = torch.empty((M, Vp), dtype=BF16, device=dev)
-            K.gemm_nt(hf, head.w16, out=logits, N=V, epilogue=K.EPI_BIAS, bias=head.bias.detach())
-            if save:
-                S.update(x_final=x, hf=hf, rstdf=rstdf, meanf=meanf, fmod=fmod, logits=logits, head_rows=None)
-            return logits[:, :V].view(B, L, V), S
-        x0 = (ce_x0 if ar else inp["x0"]).contiguous().view(-1).to(torch.int64)
-        restrict = bool(inp.get("restrict", False))
-        if ar:
-            ce_mod = ce_mod_ar
-        elif restrict and mod_flat is None:  # static slices (model.py:634-635)
+            o, lse = K.attention_fwd(qkr, qkv, B, L, H, D, S.sid, S.doc_ranges, q_prescaled=True, **self._attn_mask_kw, **S.attn_drop_kw(i))
+        rows_c = last_rows   # (None unless `recompute`)
+        if not recompute and i + 1 == self.n_blocks and S.head_plan is not None and S.mode == "logp" and self.compact_last_block and not tc:
+            head_rows_c = self._masked_rows(S.head_plan, M)   # (the count was queued at the top of this forward: the host does not wait for the device here)
+            rows_c = head_rows_c[0] if head_rows_c is not None else None
+        x_full, o_full = x, o
+        if rows_c is not None:   # from here on this block works on the [MASK] rows (+ padding) only
+            o = o.index_select(0, rows_c)
+            x = x.index_select(0, rows_c)
+        a_out = K.gemm_nt(o, lin[f"{i}.out"].w16, N=d)
+        # The next pre-norm is fused into the residual add (x_out is normalised while in registers) - with adaLN in its modulated form (round 5)
+        fuse_w2 = blk.norm2.weight.detach()
+        nkw2 = dict(next_mod=mod, next_mod_idx=(3, 4), next_modality=mod_flat, next_any_img=any_img) if tc else {}
+        if sw:  # x = x_skip + pre_residual_norm(attn)   (dit.py:993-994; no gate, no dropout)
+            res = K.residual_fwd(x, a_out, L, w_b=blk.pre_residual_norm.weight.detach(), norm_type=nt, next_w=fuse_w2, **nkw2)
+        else:   # bias_dropout_add_scale with gate_msa on every token (Attention.time_conditioning is never set: dit.py:533,884)
+            res = K.residual_fwd(x, a_out, L, norm_type=nt, mod=mod, gate_idx=2 if tc else None, p_drop=p_drop, seed=seed0 + 4 * i + 1, next_w=fuse_w2, **nkw2)
+        x_mid, rstd_a, mean_a, (h2, rstd2, mean2) = res[:4]
+        f1, f2 = lin[f"{i}.fc1"], lin[f"{i}.fc2"]
+        u1 = torch.empty((o.shape[0], 4 * d), dtype=BF16, device=x.device)
+        g = K.gemm_nt(h2, f1.w16, N=4 * d, epilogue=K.EPI_BIAS_GELU, bias=f1.bias.detach(), aux=u1)
+        u2 = K.gemm_nt(g, f2.w16, N=d, epilogue=K.EPI_BIAS, bias=f2.bias.detach())
+        # the consumer of x_out: norm1 of the next block, or norm_final (with adaLN: modulated by the NEXT block's / the final layer's adaLN output)
+        nxt_w = (self.blocks[i + 1].norm1.weight if i + 1 < self.n_blocks else self.output_layer.norm_final.weight).detach()
+        nkw = dict(next_mod=self._ada_mod(S, i + 1), next_mod_idx=(0, 1), next_modality=mod_flat, next_any_img=any_img) if tc and not recompute else {}
+        if tc and recompute:      # (recomputation of ONE block in the backward: its output's norm is not needed)
+            nxt_w = None
+        res = K.residual_fwd(x_mid, u2, L, w_b=blk.post_ff_norm.weight.detach() if sw else None, norm_type=nt, mod=mod,
+                             gate_idx=5 if tc else None, modality=mod_flat if tc else None, p_drop=p_drop, seed=seed0 + 4 * i + 2, next_w=nxt_w, **nkw)
+        x_out, rstd_m, mean_m = res[:3]
+        pre = res[3] if nxt_w is not None else None
+        R = None
+        if S.save and S.ckpt and not recompute:
+            R = _BlockActs(ckpt=True, x_in=x_full, rows_c=rows_c)
+        elif S.save:
+            R = _BlockActs(mod=mod, x_in=x_full, h1=h1, rstd1=rstd1, mean1=mean1, qkv=qkv, qkr=qkr, qstats=qstats, o=o_full, lse=lse, a_out=a_out, rstd_a=rstd_a,
+                           mean_a=mean_a, x_mid=x_mid, h2=h2, rstd2=rstd2, mean2=mean2, u1=u1, g=g, u2=u2, rstd_m=rstd_m, mean_m=mean_m, rows_c=rows_c,
+                           o_c=o if rows_c is not None else None)
+        return x_out, pre, R
+
+    def _head_split_cols(self):
+        """Split head: (text rows) x ids [0, c_up) + (image rows) x ids [c_al, V).  The boundary is rounded to multiples of 8 outwards so that every operand and
+        output pointer keeps its alignment; the few extra columns are never read (the cross-entropy reads a row's valid ids only)."""
+        return self.text_vocab_size // 8 * 8, _ceil(self.text_vocab_size, 8)
+
+    def _head_gemm(self, rows, out, c0=0, c1=None):
+        """out = rows W[c0:c1]^T + b[c0:c1]: the vocabulary head (c1 = None: up to V), or a column range of it"""
+        head = self._lins["head"]
+        return K.gemm_nt(rows, head.w16[c0:], out=out, N=(self.vocab_size if c1 is None else c1) - c0, epilogue=K.EPI_BIAS, bias=head.bias.detach()[c0:])
+
+    def _head_rows(self, S, hf):
+        """sampler: logits of the [MASK] rows only (no autograd); rows = their flat indices, padded to a multiple of 64"""
+        rows_p, n_masked = self._masked_rows(S.head_plan, S.B * S.L, always=True)
+        logits = torch.empty((rows_p.numel(), self._lins["head"].outp), dtype=BF16, device=hf.device)
+        self._head_gemm(hf.index_select(0, rows_p), logits)
+        return logits, rows_p, n_masked
+
+    def _head_logits(self, S, hf, head_out):
+        B, L, V = S.B, S.L, self.vocab_size
+        if head_out is not None:   # (KV-cache prefill: the head on each row's last position only)
+            last = torch.arange(B, device=hf.device) * L + (L - 1)
+            self._head_gemm(hf.index_select(0, last), head_out)
+            return head_out
+        logits = torch.empty((B * L, self._lins["head"].outp), dtype=BF16, device=hf.device)
+        self._head_gemm(hf, logits)
+        if S.save:
+            S.hf, S.logits = hf, logits
+        return logits[:, :V].view(B, L, V)
+
+    def _head_logp(self, S, inp, hf, ce):
+        """The fused head + SUBS cross-entropy: log p(x0 | xt) [B, L] fp32, on the [MASK] rows only where the plan compacts them."""
+        B, L, M, dev, restrict = S.B, S.L, S.B * S.L, hf.device, bool(inp.restrict)
+        ids_h, x0, ce_mod = ce if ce is not None else (S.ids, inp.x0, S.modality)
+        if ce is None and restrict and S.modality is None:  # static slices (model.py:634-635)
             ce_mod = self._static_modality(B, L, dev).view(-1)
-        else:
-            ce_mod = mod_flat
-        ids_h = ce_ids if ar else ids
-        head_rows = self._masked_rows(head_plan, M) if head_plan is not None else None
+        x0 = x0.contiguous().view(-1).to(torch.int64)
+        head_rows = self._masked_rows(S.head_plan, M) if S.head_plan is not None else None
         stream_compact = head_rows is not None and hf.shape[0] != M   # the last block already runs on the compacted rows (same list, same order)
+        hf_h = hf
         if head_rows is not None:  # compact operands: masked rows first, padded (with an unmasked row: zero loss, zero gradient) to a multiple of 64
-            rows_p, n_masked = head_rows
+            rows_p = head_rows[0]
             # fixed-capacity buffers (views of M-row allocations): a different size every step would make the caching allocator go back
             # to hipMalloc until its pool covers every size seen (measured: occasional 120+ ms steps)
             hf_h = hf if stream_compact else torch.index_select(hf, 0, rows_p, out=torch.empty_like(hf)[: rows_p.numel()])
             x0, ids_h = x0.index_select(0, rows_p), ids_h.index_select(0, rows_p)
             ce_mod = ce_mod.index_select(0, rows_p) if ce_mod is not None else None
-        else:
-            hf_h = hf
-        Mh = hf_h.shape[0]
         chunk = _ceil(self.head_chunk_rows, 64) if self.head_chunk_rows > 0 else 0
-        if chunk and chunk < Mh:   # fused head + cross-entropy over row chunks: only one chunk of logits exists at a time, none is kept
-            logits = None
-            buf = torch.empty((chunk, Vp), dtype=BF16, device=dev)
-            lps, lses = [], []
-            for r0 in range(0, Mh, chunk):
-                r1 = min(Mh, r0 + chunk)
-                lg = buf[: r1 - r0]
-                K.gemm_nt(hf_h[r0:r1], head.w16, out=lg, N=V, epilogue=K.EPI_BIAS, bias=head.bias.detach())
-                lp_c, lse_c = K.subs_ce_fwd(lg, x0[r0:r1], ids_h[r0:r1], ce_mod[r0:r1] if ce_mod is not None else None, V, self.text_vocab_size, self.mask_index, restrict)
-                lps.append(lp_c)
-                lses.append(lse_c)
-            log_p, lse_ce = torch.cat(lps), torch.cat(lses)
-            del buf
+        chunk = chunk if chunk < hf_h.shape[0] else 0
+        groups = S.head_plan.get("groups") if (S.head_plan is not None and head_rows is not None and restrict and not chunk) else None
+        ce_args = (self.vocab_size, self.text_vocab_size, self.mask_index, restrict)
+        if chunk:   # fused head + cross-entropy over row chunks: only one chunk of logits exists at a time, none is kept
+            logits, buf, parts = None, torch.empty((chunk, self._lins["head"].outp), dtype=BF16, device=dev), []
+            for r0 in range(0, hf_h.shape[0], chunk):
+                r1 = min(hf_h.shape[0], r0 + chunk)
+                self._head_gemm(hf_h[r0:r1], buf[: r1 - r0])
+                parts.append(K.subs_ce_fwd(buf[: r1 - r0], x0[r0:r1], ids_h[r0:r1], ce_mod[r0:r1] if ce_mod is not None else None, *ce_args))
+            log_p, lse_ce = (torch.cat(t) for t in zip(*parts))
         else:
-            chunk = 0
-            logits = torch.empty((M, Vp), dtype=BF16, device=dev)[:Mh]
-            groups = head_plan.get("groups") if (head_plan is not None and head_rows is not None and restrict) else None
+            logits = torch.empty((M, self._lins["head"].outp), dtype=BF16, device=dev)[:hf_h.shape[0]]
             if groups is not None:
-                # (text rows) x ids [0, c_up) and (image rows) x ids [c_al, V): the boundary Vt is rounded to multiples of 8 outwards so that every operand and
-                # output pointer keeps its alignment; the few extra columns are never read (the cross-entropy reads a row's valid ids only)
-                n_tp, n_ip = groups
-                Vt = self.text_vocab_size
-                c_al, c_up = Vt // 8 * 8, _ceil(Vt, 8)
-                bias = head.bias.detach()
+                (n_tp, n_ip), (c_al, c_up) = groups, self._head_split_cols()
                 if n_tp:
-                    K.gemm_nt(hf_h[:n_tp], head.w16, out=logits[:n_tp], N=c_up, epilogue=K.EPI_BIAS, bias=bias)
+                    self._head_gemm(hf_h[:n_tp], logits[:n_tp], 0, c_up)
                 if n_ip:
-                    K.gemm_nt(hf_h[n_tp:], head.w16[c_al:], out=logits[n_tp:, c_al:], N=V - c_al, epilogue=K.EPI_BIAS, bias=bias[c_al:])
+                    self._head_gemm(hf_h[n_tp:], logits[n_tp:, c_al:], c_al)
             else:
-                K.gemm_nt(hf_h, head.w16, out=logits, N=V, epilogue=K.EPI_BIAS, bias=head.bias.detach())
-            log_p, lse_ce = K.subs_ce_fwd(logits, x0, ids_h, ce_mod, V, self.text_vocab_size, self.mask_index, restrict)
+                self._head_gemm(hf_h, logits)
+            log_p, lse_ce = K.subs_ce_fwd(logits, x0, ids_h, ce_mod, *ce_args)
         if head_rows is not None:   # (padding rows are unmasked: their log p is exactly 0, like every row left out)
             log_p = torch.zeros(M, dtype=log_p.dtype, device=dev).index_copy_(0, rows_p, log_p)
-        if save:
-            S.update(x_final=x, hf=hf_h, rstdf=rstdf, meanf=meanf, fmod=fmod, logits=logits, head_rows=head_rows, ids_h=ids_h,
-                     x0=x0, ce_mod=ce_mod, restrict=restrict, lse_ce=lse_ce, stream_compact=stream_compact, head_chunk=chunk,
-                     head_groups=(head_plan.get("groups") if (head_plan is not None and head_rows is not None and restrict and not chunk) else None))
-        return log_p.view(B, L), S
+        if S.save:
+            S.hf, S.logits, S.head_rows, S.ids_h, S.x0, S.ce_mod, S.restrict, S.lse_ce = hf_h, logits, head_rows, ids_h, x0, ce_mod, restrict, lse_ce
+            S.stream_compact, S.head_chunk, S.head_groups = stream_compact, chunk, groups
+        return log_p.view(B, L)
 
     def _static_modality(self, B, L, dev):
         return static_modality(B, L, self.static_img_sl, dev)
@@ -1390,9 +1443,7 @@ class DIT(nn.Module, _HubMixin):
 
     def _wgrad(self, dY, X, lin: _Lin, G, n_rows=None, bias_done=False, beta=0.0):
         """dW[out,in] = dY[M,out]^T X[M,in] (fp32), db = colsum(dY).  dY/X bf16 [M, *]."""
-        Mrows = dY.shape[0]
-        outp = dY.shape[1]
-        db = None
+        (Mrows, outp), db = dY.shape, None
         if lin.bias is not None and not bias_done:
             db = G[id(lin.bias)] if outp == lin.out else torch.zeros(outp, dtype=F32, device=dY.device)
         few_tiles = K.gemm_tn_wants_splitk(lin.out, lin.inp)
@@ -1413,61 +1464,92 @@ class DIT(nn.Module, _HubMixin):
             else:
                 G[id(lin.bias)].copy_(db[: lin.out])
 
-    def _engine_backward(self, S, grad_out, mode):
+    def _engine_backward(self, S: _Saved, grad_out, mode):
         params = self._ordered_params()
-        B, L = S["B"], S["L"]
-        M, d, H, D = B * L, self.hidden_size, self.n_heads, self.head_dim
-        dev = S["ids"].device
-        nt = K.norm_id(self.norm_type)
-        tc, sw = self.time_conditioning, self.sandwich_normalization
-        lin = self._lins
-        flat, G = self._alloc_grads(params, dev)
-        S["grad_flat"] = flat
-        mod_flat, any_img, p_drop, seed0 = S["modality"], S.get("any_img"), S["p_drop"], S["seed0"]
-        V = self.vocab_size
-        head = lin["head"]
-        logits = S["logits"]
+        M, d, dev = S.B * S.L, self.hidden_size, S.ids.device
+        bp = _Backward(S=S, nt=K.norm_id(self.norm_type), ada_off=0)
+        bp.flat, bp.G = self._alloc_grads(params, dev)
+        G, tc, fl = bp.G, self.time_conditioning, self.output_layer
+        dhf = self._head_backward(bp, grad_out, mode)
+        dmodf = None
+        if tc:
+            bp.dc = torch.zeros((S.Bp, self.cond_dim), dtype=F32, device=dev)
+            dmodf = torch.zeros((S.Bp, 2 * d), dtype=F32, device=dev)
+            # the adaLN_modulation backwards leave their input gradients as partial tiles in one buffer; summed once, where dc is consumed (`_sigma_map_backward`)
+            if S.Bp <= K.SMALL_BATCH_LINEAR_MAX_B and self.cond_dim <= K.SMALL_BATCH_LINEAR_MAX_IN and self.cond_dim % 8 == 0:
+                tiles = K.small_batch_linear_bwd_tiles(2 * d) + self.n_blocks * K.small_batch_linear_bwd_tiles(6 * d)
+                bp.ada_buf = torch.empty((tiles, S.Bp, self.cond_dim), dtype=F32, device=dev)
+        # (compacted last block: its residual-stream gradient lives on the compacted rows until the block's attention is reached)
+        bp.dx = torch.empty((dhf.shape[0] if S.stream_compact else M, d), dtype=F32, device=dev)
+        # (the final norm and each block's norm1 wait in `bp.pend` for the MLP branch below them, see _PendingNorm; with adaLN where the fused pass covers the shape)
+        bp.tc_fused = tc and not S.stream_compact and K.norm_residual_bwd_ada_ok(M, d, S.L)
+        pn = _PendingNorm(dy=dhf, x=S.x_final, rstd=S.rstdf, mean=S.meanf, w=fl.norm_final.weight.detach(), dw=G[id(fl.norm_final.weight)], accumulate=False,
+                          mod=S.fmod, dmod=dmodf, mod_idx=(0, 1), finish=self.n_blocks)
+        if tc:
+            self._norm_backward(bp, pn)
+        else:
+            bp.pend = pn
+        for i in reversed(range(self.n_blocks)):
+            self._block_backward(bp, i)
+        if bp.pend is not None:   # block 0's norm1 (or the final norm of a model without blocks): nothing below it to pair with
+            self._norm_backward(bp, bp.pend)
+        # ---- embeddings
+        dx = bp.dx
+        if S.cnt_j is not None:
+            n_cnt = self.img_count_embedding.shape[0]
+            if dx.is_cuda and dx.dtype == F32:   # sums formed in LDS per run of equal indices (an index_add_ here is 19 M contended atomics: 225 us)
+                K.rowgroup_sum(dx, S.cnt_j, G[id(self.img_count_embedding)])
+            else:
+                gext = torch.zeros((n_cnt + 1, dx.shape[1]), dtype=dx.dtype, device=dx.device).index_add_(0, S.cnt_j, dx)   # (row n_cnt collects the positions without an image index)
+                G[id(self.img_count_embedding)].add_(gext[:n_cnt])
+        K.embedding_bwd(S.ids, dx, G[id(self.vocab_embed.embedding)], self.mask_index, modality=S.emb_mod if self.modality_embed is not None else None,
+                        dEm=G[id(self.modality_embed.embedding)] if self.modality_embed is not None else None)
+        tail = list(self.vocab_embed.parameters()) + (list(self.modality_embed.parameters()) if self.modality_embed is not None else [])
+        if getattr(self, "img_count_embedding", None) is not None:
+            tail.append(self.img_count_embedding)
+        if tc:
+            self._sigma_map_backward(bp)
+            tail += list(self.sigma_map.parameters())
+        self._notify(bp.flat, tail)
+        if self.grad_sync_finish is not None:
+            self.grad_sync_finish()
+        # for the fused optimizer's one-pass global norm; a weak reference: the buffer lives exactly as long as the p.grad views do
+        self._last_grad_flat_ref, self._last_grad_numel = weakref.ref(bp.flat), sum(p.numel() for p in params)
+        return [G[id(p)] for p in params]
 
-        # ---- head: d logits -> dhf, dW_head, db_head
-        head_rows = S.get("head_rows")
-        chunk = S.get("head_chunk", 0) if mode == "logp" else 0
+    def _head_backward(self, bp, grad_out, mode):
+        """d logits -> dhf (the gradient of the final norm's output, on the rows the head ran on or scattered back to all rows), dW_head, db_head"""
+        S, G, head = bp.S, bp.G, self._lins["head"]
+        M, d, V, dev = S.B * S.L, self.hidden_size, self.vocab_size, S.ids.device
+        logits, head_rows, groups = S.logits, S.head_rows, S.head_groups if mode == "logp" else None
+        ce_args = (V, self.text_vocab_size, self.mask_index, S.restrict)
         if mode == "logp":
             g = grad_out.contiguous().view(-1).to(F32)
             if head_rows is not None:
                 g = g.index_select(0, head_rows[0])
-        if chunk:   # fused head + cross-entropy: per row chunk recompute the logits, form d logits in place, consume them (dgrad, wgrad accumulated)
-            hf_h = S["hf"]
-            Mh, Vp = hf_h.shape[0], head.outp
+        if mode == "logp" and S.head_chunk:   # fused head + cross-entropy: per row chunk recompute the logits, form d logits in place, consume them (dgrad, wgrad accumulated)
+            hf_h, chunk, cm, Mh = S.hf, S.head_chunk, S.ce_mod, S.hf.shape[0]
             dhf = torch.empty((M, d), dtype=BF16, device=dev)[:Mh]
-            buf = torch.empty((chunk, Vp), dtype=BF16, device=dev)
-            cm = S["ce_mod"]
+            buf = torch.empty((chunk, head.outp), dtype=BF16, device=dev)
             for r0 in range(0, Mh, chunk):
                 r1 = min(Mh, r0 + chunk)
                 lg = buf[: r1 - r0]
-                K.gemm_nt(hf_h[r0:r1], head.w16, out=lg, N=V, epilogue=K.EPI_BIAS, bias=head.bias.detach())
-                K.subs_ce_bwd(lg, S["x0"][r0:r1], S["ids_h"][r0:r1], cm[r0:r1] if cm is not None else None, S["lse_ce"][r0:r1], g[r0:r1], V, self.text_vocab_size,
-                              self.mask_index, S["restrict"])
+                self._head_gemm(hf_h[r0:r1], lg)
+                K.subs_ce_bwd(lg, S.x0[r0:r1], S.ids_h[r0:r1], cm[r0:r1] if cm is not None else None, S.lse_ce[r0:r1], g[r0:r1], *ce_args)
                 K.gemm_nt_splitk(lg, head.w16t, N=d, out=dhf[r0:r1])
                 self._wgrad(lg, hf_h[r0:r1], head, G, beta=0.0 if r0 == 0 else 1.0)
-            del buf
-            dlogits = None
         else:
             if mode == "logp":
-                K.subs_ce_bwd(logits, S["x0"], S["ids_h"], S["ce_mod"], S["lse_ce"], g, V, self.text_vocab_size, self.mask_index, S["restrict"],
-                              narrow_txt_rows=S["head_groups"][0] if S.get("head_groups") is not None else -1)
+                K.subs_ce_bwd(logits, S.x0, S.ids_h, S.ce_mod, S.lse_ce, g, *ce_args, narrow_txt_rows=groups[0] if groups is not None else -1)
                 dlogits = logits
             else:
                 dlogits = torch.zeros_like(logits)
                 dlogits[:, :V].copy_(grad_out.reshape(M, V))
-            groups = S.get("head_groups") if mode == "logp" else None
             if groups is not None:   # the same two (rows of one modality) x (ids of that modality) problems as the forward; d logits is zero everywhere else
-                n_tp, n_ip = groups
-                Vt, Vp = self.text_vocab_size, head.outp
-                c_al, c_up = Vt // 8 * 8, _ceil(Vt, 8)
-                k_t = min(_ceil(Vt, 64), Vp)
-                hf_h = S["hf"]
+                (n_tp, n_ip), (c_al, c_up) = groups, self._head_split_cols()
+                Vp, hf_h, Gw = head.outp, S.hf, G[id(head.weight)]
+                k_t = min(_ceil(self.text_vocab_size, 64), Vp)
                 dhf = torch.empty((M, d), dtype=BF16, device=dev)[: dlogits.shape[0]]
-                Gw = G[id(head.weight)]
                 db = torch.zeros(Vp, dtype=F32, device=dev)   # (column sums over widths that are multiples of 8; d logits is zero in the padding columns)
                 if n_tp:
                     K.gemm_nt_splitk(dlogits[:n_tp, :k_t], head.w16t[:, :k_t], N=d, out=dhf[:n_tp])
@@ -1488,254 +1570,172 @@ class DIT(nn.Module, _HubMixin):
             else:
                 # few output tiles (compacted rows x d) over K = V: split K so that all CUs work (falls back to the plain kernel otherwise)
                 dhf = K.gemm_nt_splitk(dlogits, head.w16t, N=d, out=torch.empty((M, d), dtype=BF16, device=dev)[: dlogits.shape[0]])
-                self._wgrad(dlogits, S["hf"], head, G)
-        stream_compact = bool(S.get("stream_compact"))
-        if head_rows is not None and not stream_compact:  # scatter the masked rows' gradient back; every other row of d(final norm output) is exactly zero
-            rows_p, n_masked = head_rows
-            dhf = torch.zeros((M, d), dtype=dhf.dtype, device=dev).index_copy_(0, rows_p, dhf)   # (padding rows: d logits = 0, so their rows of dhf are 0 too)
-        del dlogits
-        S["logits"] = None
+                self._wgrad(dlogits, S.hf, head, G)
+        if head_rows is not None and not S.stream_compact:  # scatter the masked rows' gradient back; every other row of d(final norm output) is exactly zero
+            dhf = torch.zeros((M, d), dtype=dhf.dtype, device=dev).index_copy_(0, head_rows[0], dhf)   # (padding rows: d logits = 0, so their rows of dhf are 0 too)
+        S.logits = None
+        return dhf
 
-        dc = dmodf = None
-        Bp = S.get("Bp")
-        if tc:
-            dc = torch.zeros((Bp, self.cond_dim), dtype=F32, device=dev)
-            dmodf = torch.zeros((Bp, 2 * d), dtype=F32, device=dev)
-            # the adaLN_modulation backwards leave their input gradients as partial tiles in one buffer; summed once, where dc is consumed (`_ada_collect`)
-            self._ada_buf, self._ada_off = None, 0
-            if Bp <= K.SMALL_BATCH_LINEAR_MAX_B and self.cond_dim <= K.SMALL_BATCH_LINEAR_MAX_IN and self.cond_dim % 8 == 0:
-                tiles = K.small_batch_linear_bwd_tiles(2 * d) + self.n_blocks * K.small_batch_linear_bwd_tiles(6 * d)
-                self._ada_buf = torch.empty((tiles, Bp, self.cond_dim), dtype=F32, device=dev)
-        fl = self.output_layer
-        fmod = S["fmod"]
-        # (compacted last block: its residual-stream gradient lives on the compacted rows until the block's attention is reached)
-        dx = torch.empty((dhf.shape[0] if stream_compact else M, d), dtype=F32, device=dev)
-        # Without adaLN every pre-norm backward is immediately followed by the backward of the residual branch that produced the norm's input, on
-        # the dx it has just updated: the pair runs as ONE fused pass (K.norm_residual_bwd).  `pend` carries the norm half to the branch that
-        # consumes it - the final norm and each block's norm1 pair with the MLP branch of the block below them in the schedule, so a block's
-        # gradient range is reported (and its activations dropped) only after that fused pass.
-        pend = None
-        # adaLN-Zero (round 5): the same pairing with the modulated / gated forms of the fused pass where the kernel covers the shape (K.norm_residual_bwd_ada)
-        tc_fused = tc and not stream_compact and K.norm_residual_bwd_ada_ok(M, d, L)
-        if tc:
-            K.norm_bwd(dhf, S["x_final"], S["rstdf"], S["meanf"], fl.norm_final.weight.detach(), nt, L, dx, G[id(fl.norm_final.weight)], accumulate=False,
-                       mod=fmod, dmod=dmodf, mod_idx=(0, 1), modality=mod_flat, any_img=any_img)
-            self._ada_backward(dmodf, lin["head.ada"], S["c"], dc, G)
-            self._notify(flat, list(fl.parameters()))
-        else:
-            pend = dict(dy=dhf, x=S["x_final"], rstd=S["rstdf"], mean=S["meanf"], w=fl.norm_final.weight.detach(), dw=G[id(fl.norm_final.weight)], accumulate=False,
-                        done=lambda: self._notify(flat, list(fl.parameters())))
+    def _finish_block(self, bp, i, dmod=None):
+        """Block i (n_blocks: the final layer; None: nothing) has all its gradients but, with adaLN, those of its adaLN_modulation, which needs the shift / scale /
+        gate gradients `dmod` collected up to here: run that backward, drop the block's activations, report its gradient range."""
+        if i is None:
+            return
+        if dmod is not None:
+            self._ada_backward(bp, dmod, self._lins[f"{i}.ada" if i < self.n_blocks else "head.ada"])
+        if i < self.n_blocks:
+            bp.S.blocks[i] = None
+        self._notify(bp.flat, list((self.blocks[i] if i < self.n_blocks else self.output_layer).parameters()))
 
-        def branch_bwd(pend, branch, **kw):
-            """residual-branch backward, fused with the pending norm backward when there is one (dbias: += column sums of the result)"""
-            if pend is None:
-                dbias = kw.pop("dbias", None)
-                out = K.residual_bwd(dx, branch, L, **kw)
-                if dbias is not None:
-                    K.colsum(out, dbias)
-                return out
-            if pend.get("mod") is not None or kw.get("gate_idx") is not None:   # adaLN-Zero: modulated norm and / or gated branch, still one pass per row
-                out = K.norm_residual_bwd_ada(pend["dy"], pend["x"], pend["rstd"], pend["mean"], pend["w"], nt, L, dx, pend["dw"], branch, accumulate=pend["accumulate"],
-                                              w_b=kw.get("w_b"), rstd_b=kw.get("rstd"), mean_b=kw.get("mean"), dw_b=kw.get("dw_b"), p_drop=kw.get("p_drop", 0.0),
-                                              seed=kw.get("seed", 0), dbias=kw.get("dbias"), mod_n=pend.get("mod"), dmod_n=pend.get("dmod"),
-                                              mod_idx=pend.get("mod_idx", (0, 1)), modality=mod_flat, any_img=any_img, mod_r=kw.get("mod"), dmod_r=kw.get("dmod"),
-                                              gate_idx=kw.get("gate_idx"), modality_r=kw.get("modality"))
-            else:
-                out = K.norm_residual_bwd(pend["dy"], pend["x"], pend["rstd"], pend["mean"], pend["w"], nt, L, dx, pend["dw"], branch, accumulate=pend["accumulate"],
-                                          w_b=kw.get("w_b"), rstd_b=kw.get("rstd"), mean_b=kw.get("mean"), dw_b=kw.get("dw_b"), p_drop=kw.get("p_drop", 0.0),
-                                          seed=kw.get("seed", 0), dbias=kw.get("dbias"))
-            pend["done"]()
+    def _norm_backward(self, bp, pn):
+        """A pre-norm backward on its own: nothing below it to pair with, or (adaLN) a shape the fused pass does not cover."""
+        S, ada = bp.S, pn.mod is not None
+        K.norm_bwd(pn.dy, pn.x, pn.rstd, pn.mean, pn.w, bp.nt, S.L, bp.dx, pn.dw, accumulate=pn.accumulate, mod=pn.mod, dmod=pn.dmod, mod_idx=pn.mod_idx,
+                   modality=S.modality if ada else None, any_img=S.any_img if ada else None)
+        self._finish_block(bp, pn.finish, pn.dmod)
+
+    def _norm_branch_bwd(self, bp, pn, branch, **kw):
+        """Norm backward (`pn`, or None), then the backward of the residual branch below it on the dx it has just updated -> the branch's gradient: one fused pass
+        where a kernel covers the pair, the two kernels otherwise.  `kw`: the branch's keywords of K.residual_bwd, and dbias (+= column sums of the result)."""
+        S, dx, nt = bp.S, bp.dx, bp.nt
+        if pn is not None and pn.mod is not None and not bp.tc_fused:
+            self._norm_backward(bp, pn)
+            pn = None
+        if pn is None:
+            dbias = kw.pop("dbias", None)
+            out = K.residual_bwd(dx, branch, S.L, **kw)
+            if dbias is not None:
+                K.colsum(out, dbias)
             return out
+        common = dict(accumulate=pn.accumulate, w_b=kw.get("w_b"), rstd_b=kw.get("rstd"), mean_b=kw.get("mean"), dw_b=kw.get("dw_b"), p_drop=kw.get("p_drop", 0.0),
+                      seed=kw.get("seed", 0), dbias=kw.get("dbias"))
+        if pn.mod is not None or kw.get("gate_idx") is not None:   # adaLN-Zero: modulated norm and / or gated branch, still one pass per row
+            out = K.norm_residual_bwd_ada(pn.dy, pn.x, pn.rstd, pn.mean, pn.w, nt, S.L, dx, pn.dw, branch, **common, mod_n=pn.mod, dmod_n=pn.dmod, mod_idx=pn.mod_idx,
+                                          modality=S.modality, any_img=S.any_img, mod_r=kw.get("mod"), dmod_r=kw.get("dmod"), gate_idx=kw.get("gate_idx"),
+                                          modality_r=kw.get("modality"))
+        else:
+            out = K.norm_residual_bwd(pn.dy, pn.x, pn.rstd, pn.mean, pn.w, nt, S.L, dx, pn.dw, branch, **common)
+        self._finish_block(bp, pn.finish, pn.dmod)
+        return out
 
-        for i in reversed(range(self.n_blocks)):
-            blk, R = self.blocks[i], S["blocks"][i]
-            if R.get("ckpt"):   # activation checkpointing: rebuild this block's activations from its saved input, right before they are consumed
-                with torch.no_grad():
-                    R = S["block_fwd"](i, R["x_in"], None, last_rows=R["rows_c"], recompute=True)[2]
-            at = blk.attention
-            mod = R.get("mod")
-            dmod = torch.zeros((Bp, 6 * d), dtype=F32, device=dev) if tc else None
-            f1, f2 = lin[f"{i}.fc1"], lin[f"{i}.fc2"]
-            # MLP branch
-            if tc:   # (pend: the modulated norm1 of block i + 1 when the fused adaLN pass is in use)
-                du2 = branch_bwd(pend, R["u2"], w_b=blk.post_ff_norm.weight.detach() if sw else None, rstd=R["rstd_m"], mean=R["mean_m"], norm_type=nt,
-                                 mod=mod, dmod=dmod, gate_idx=5, modality=mod_flat, dw_b=G[id(blk.post_ff_norm.weight)] if sw else None,
-                                 p_drop=p_drop, seed=seed0 + 4 * i + 2)
-                pend = None
-            else:
-                # (the mlp.2 bias gradient = column sums of du2 comes out of the same pass)
-                du2 = branch_bwd(pend, R["u2"], w_b=blk.post_ff_norm.weight.detach() if sw else None, rstd=R["rstd_m"], mean=R["mean_m"], norm_type=nt,
-                                 dw_b=G[id(blk.post_ff_norm.weight)] if sw else None, p_drop=p_drop, seed=seed0 + 4 * i + 2, dbias=G[id(f2.bias)])
-                pend = None
-            # dgrad through mlp.2 with the GELU' multiply and the mlp.0 bias gradient (column sums of du1) fused into the epilogue
-            du1 = K.gemm_nt(du2, f2.w16t, N=4 * d, epilogue=K.EPI_DGELU, aux=R["u1"], bias=G[id(f1.bias)])
-            lo, lq = lin[f"{i}.out"], lin[f"{i}.qkv"]
-            # few-tile regime (every weight of the block is at most half a round of tiles: UniDisc-S): the four weight gradients wait for the end of the block's
-            # backward and share ONE split-K launch + ONE reduce (K.gemm_tn_multi) instead of three split-K launches + four reduce passes
-            multi = None
-            if (self.multi_wgrads and du2.is_cuda and not tc and R.get("rows_c") is None and M % 64 == 0 and lo.bias is None and lq.bias is None
-                    and all(K.gemm_tn_wants_splitk(l_.out, l_.inp) and l_.out % 256 == 0 and l_.inp % 256 == 0 for l_ in (f1, f2, lo, lq))):
-                multi = [(du2, R["g"], f2), (du1, R["h2"], f1)]
-            if multi is None:
-                self._wgrad(du2, R["g"], f2, G, bias_done=not tc)
-            dh2 = f1.dgrad(du1, du1.shape[0], S["dgrad_form"].get(f"{i}.fc1"))
-            if multi is None:
-                self._wgrad(du1, R["h2"], f1, G, bias_done=True)
-            del du1, du2
-            # norm2 backward + attention branch
-            if tc_fused:
-                p2 = dict(dy=dh2, x=R["x_mid"], rstd=R["rstd2"], mean=R["mean2"], w=blk.norm2.weight.detach(), dw=G[id(blk.norm2.weight)], accumulate=True,
-                          done=lambda: None, mod=mod, dmod=dmod, mod_idx=(3, 4))
-                if sw:
-                    da = branch_bwd(p2, R["a_out"], w_b=blk.pre_residual_norm.weight.detach(), rstd=R["rstd_a"], mean=R["mean_a"], norm_type=nt,
-                                    dw_b=G[id(blk.pre_residual_norm.weight)])
-                else:
-                    da = branch_bwd(p2, R["a_out"], mod=mod, dmod=dmod, gate_idx=2, p_drop=p_drop, seed=seed0 + 4 * i + 1)
-            elif tc:
-                K.norm_bwd(dh2, R["x_mid"], R["rstd2"], R["mean2"], blk.norm2.weight.detach(), nt, L, dx, G[id(blk.norm2.weight)], accumulate=True,
-                           mod=mod, dmod=dmod, mod_idx=(3, 4), modality=mod_flat, any_img=any_img)
-                if sw:
-                    da = K.residual_bwd(dx, R["a_out"], L, w_b=blk.pre_residual_norm.weight.detach(), rstd=R["rstd_a"], mean=R["mean_a"], norm_type=nt,
-                                        dw_b=G[id(blk.pre_residual_norm.weight)])
-                else:
-                    da = K.residual_bwd(dx, R["a_out"], L, mod=mod, dmod=dmod, gate_idx=2, p_drop=p_drop, seed=seed0 + 4 * i + 1)
-            else:
-                p2 = dict(dy=dh2, x=R["x_mid"], rstd=R["rstd2"], mean=R["mean2"], w=blk.norm2.weight.detach(), dw=G[id(blk.norm2.weight)], accumulate=True,
-                          done=lambda: None)
-                if sw:
-                    da = branch_bwd(p2, R["a_out"], w_b=blk.pre_residual_norm.weight.detach(), rstd=R["rstd_a"], mean=R["mean_a"], norm_type=nt,
-                                    dw_b=G[id(blk.pre_residual_norm.weight)])
-                else:
-                    da = branch_bwd(p2, R["a_out"], p_drop=p_drop, seed=seed0 + 4 * i + 1)
-            pair_out = None
-            do = lo.dgrad(da, da.shape[0], S["dgrad_form"].get(f"{i}.out"))
-            if R.get("rows_c") is not None:
-                # back to all rows: the rows left out have a zero gradient in both the attention output and the residual stream
-                self._wgrad(da, R["o_c"], lo, G)
-                rows_c = R["rows_c"]
-                do = torch.zeros((M, d), dtype=do.dtype, device=dev).index_copy_(0, rows_c, do)
-                dx = torch.zeros((M, d), dtype=F32, device=dev).index_copy_(0, rows_c, dx)
-            else:
-                # The out-proj weight gradient (2048 x 2048: 64 tiles) waits for the qkv one (6144 x 2048: 192 tiles of 256 rows) where the two fill the chip
-                # exactly once TOGETHER (K.gemm_tn_pair): one launch instead of 256 tiles of 192 rows + a split-K launch + its reduce pass; few tiles over a long
-                # contraction (UniDisc-S: 27 + 9) share ONE split-K launch
-                if multi is not None:
-                    multi.append((da, R["o"], lo))
-                elif (self.pair_wgrads and da.is_cuda and lo.bias is None and lq.bias is None and lo.inp == lq.inp
-                        and K.gemm_tn_pair_ok(lq.out, lo.out, lq.inp, M)
-                        and ((lq.out // 256 + lo.out // 256) * (lq.inp // 256) % 256 == 0 or (lq.out // 256 + lo.out // 256) * (lq.inp // 256) <= 128)):
-                    pair_out = (da, R["o"])
-                else:
-                    self._wgrad(da, R["o"], lo, G)
-            dqkr = torch.empty((M, 2 * d), dtype=BF16, device=dev)
-            dqkv = torch.empty((M, 3 * d), dtype=BF16, device=dev)
-            K.attention_bwd(R["qkr"], R["qkv"], R["o"], do, R["lse"], dqkr, dqkv, B, L, H, D, S["sid"], S["doc_ranges"], q_prescaled=True, **self._attn_mask_kw,
-                            **S["attn_drop_kw"](i))
-            qn = self.qk_norm
-            K.qknorm_rope_bwd(dqkr, R["qkv"], dqkv, S["cos"], S["sin"], L, D, gq=at.q_norm.weight.detach() if qn else None,
-                              gk=at.k_norm.weight.detach() if qn else None, stats=R["qstats"], dgq=G[id(at.q_norm.weight)] if qn else None,
-                              dbq=G[id(at.q_norm.bias)] if qn else None, dgk=G[id(at.k_norm.weight)] if qn else None,
-                              dbk=G[id(at.k_norm.bias)] if qn else None, q_scale=self.attn_q_scale)
-            dh1 = lq.dgrad(dqkv, dqkv.shape[0], S["dgrad_form"].get(f"{i}.qkv"))
-            if multi is not None:
-                multi.append((dqkv, R["h1"], lq))
-                if not K.gemm_tn_multi([(dy_, x_, G[id(l_.weight)]) for dy_, x_, l_ in multi]):
-                    for dy_, x_, l_ in multi:    # (shapes outside the shared launch: the plain calls)
-                        self._wgrad(dy_, x_, l_, G, bias_done=True)
-                multi = None
-            elif pair_out is not None:
-                K.gemm_tn_pair(dqkv, R["h1"], G[id(lq.weight)], pair_out[0], pair_out[1], G[id(lo.weight)])
-                pair_out = None
-            else:
-                self._wgrad(dqkv, R["h1"], lq, G)
-            if tc_fused:   # norm1 (modulated) pairs with the gated MLP branch of block i - 1; this block's adaLN_modulation backward needs the shift / scale
-                def done_tc(i=i, blk=blk, dmod=dmod):   # gradients of that pass, so it waits for it
-                    self._ada_backward(dmod, lin[f"{i}.ada"], S["c"], dc, G)
-                    S["blocks"][i] = None
-                    self._notify(flat, list(blk.parameters()))
-                pend = dict(dy=dh1, x=R["x_in"], rstd=R["rstd1"], mean=R["mean1"], w=blk.norm1.weight.detach(), dw=G[id(blk.norm1.weight)], accumulate=True,
-                            done=done_tc, mod=mod, dmod=dmod, mod_idx=(0, 1))
-            elif tc:
-                K.norm_bwd(dh1, R["x_in"], R["rstd1"], R["mean1"], blk.norm1.weight.detach(), nt, L, dx, G[id(blk.norm1.weight)], accumulate=True,
-                           mod=mod, dmod=dmod, mod_idx=(0, 1), modality=mod_flat, any_img=any_img)
-                self._ada_backward(dmod, lin[f"{i}.ada"], S["c"], dc, G)
-                S["blocks"][i] = None  # free this block's activations
-                self._notify(flat, list(blk.parameters()))
-            else:   # norm1 pairs with the MLP branch of block i - 1: keep what it needs alive, report this block's range after that pass
-                def done(i=i, blk=blk):
-                    S["blocks"][i] = None
-                    self._notify(flat, list(blk.parameters()))
-                pend = dict(dy=dh1, x=R["x_in"], rstd=R["rstd1"], mean=R["mean1"], w=blk.norm1.weight.detach(), dw=G[id(blk.norm1.weight)], accumulate=True, done=done)
-        if pend is not None:   # block 0's norm1 (or the final norm of a model without blocks): nothing below it to pair with
-            K.norm_bwd(pend["dy"], pend["x"], pend["rstd"], pend["mean"], pend["w"], nt, L, dx, pend["dw"], accumulate=pend["accumulate"], mod=pend.get("mod"),
-                       dmod=pend.get("dmod"), mod_idx=pend.get("mod_idx", (0, 1)), modality=mod_flat if pend.get("mod") is not None else None,
-                       any_img=any_img if pend.get("mod") is not None else None)
-            pend["done"]()
+    def _block_backward(self, bp, i):
+        S, G, lin, blk, nt, tc, sw = bp.S, bp.G, self._lins, self.blocks[i], bp.nt, self.time_conditioning, self.sandwich_normalization
+        B, L, p_drop, seed0, R = S.B, S.L, S.p_drop, S.seed0, S.blocks[i]
+        M, d, H, D, dev = B * L, self.hidden_size, self.n_heads, self.head_dim, S.ids.device
+        if R.ckpt:   # activation checkpointing: rebuild this block's activations from its saved input, right before they are consumed
+            with torch.no_grad():
+                R = self._block_forward(S, i, R.x_in, None, last_rows=R.rows_c, recompute=True)[2]
+        at, mod = blk.attention, R.mod
+        dmod = torch.zeros((S.Bp, 6 * d), dtype=F32, device=dev) if tc else None
+        f1, f2 = lin[f"{i}.fc1"], lin[f"{i}.fc2"]
+        # MLP branch, fused with the pending norm above it: the final norm or norm1 of block i + 1 (with adaLN: where the fused pass is in use).  Without adaLN the
+        # mlp.2 bias gradient = column sums of du2 comes out of the same pass
+        kw = dict(mod=mod, dmod=dmod, gate_idx=5, modality=S.modality) if tc else dict(dbias=G[id(f2.bias)])
+        kw.update(w_b=blk.post_ff_norm.weight.detach() if sw else None, rstd=R.rstd_m, mean=R.mean_m, norm_type=nt, dw_b=G[id(blk.post_ff_norm.weight)] if sw else None,
+                  p_drop=p_drop, seed=seed0 + 4 * i + 2)
+        pend, bp.pend = bp.pend, None
+        du2 = self._norm_branch_bwd(bp, pend, R.u2, **kw)
+        # dgrad through mlp.2 with the GELU' multiply and the mlp.0 bias gradient (column sums of du1) fused into the epilogue
+        du1 = K.gemm_nt(du2, f2.w16t, N=4 * d, epilogue=K.EPI_DGELU, aux=R.u1, bias=G[id(f1.bias)])
+        lo, lq = lin[f"{i}.out"], lin[f"{i}.qkv"]
+        # few-tile regime (every weight of the block is at most half a round of tiles: UniDisc-S): the four weight gradients wait for the end of the block's
+        # backward and share ONE split-K launch + ONE reduce (K.gemm_tn_multi) instead of three split-K launches + four reduce passes
+        multi = pair_out = None
+        if (self.multi_wgrads and du2.is_cuda and not tc and R.rows_c is None and M % 64 == 0 and lo.bias is None and lq.bias is None
+                and all(K.gemm_tn_wants_splitk(l_.out, l_.inp) and l_.out % 256 == 0 and l_.inp % 256 == 0 for l_ in (f1, f2, lo, lq))):
+            multi = [(du2, R.g, f2), (du1, R.h2, f1)]
+        if multi is None:
+            self._wgrad(du2, R.g, f2, G, bias_done=not tc)
+        dh2 = f1.dgrad(du1, du1.shape[0], S.dgrad_form.get(f"{i}.fc1"))
+        if multi is None:
+            self._wgrad(du1, R.h2, f1, G, bias_done=True)
+        del du1, du2
+        # norm2 backward + attention branch
+        p2 = _PendingNorm(dy=dh2, x=R.x_mid, rstd=R.rstd2, mean=R.mean2, w=blk.norm2.weight.detach(), dw=G[id(blk.norm2.weight)], accumulate=True,
+                          mod=mod, dmod=dmod, mod_idx=(3, 4))
+        if sw:
+            da = self._norm_branch_bwd(bp, p2, R.a_out, w_b=blk.pre_residual_norm.weight.detach(), rstd=R.rstd_a, mean=R.mean_a, norm_type=nt,
+                                       dw_b=G[id(blk.pre_residual_norm.weight)])
+        elif tc:
+            da = self._norm_branch_bwd(bp, p2, R.a_out, mod=mod, dmod=dmod, gate_idx=2, p_drop=p_drop, seed=seed0 + 4 * i + 1)
+        else:
+            da = self._norm_branch_bwd(bp, p2, R.a_out, p_drop=p_drop, seed=seed0 + 4 * i + 1)
+        do = lo.dgrad(da, da.shape[0], S.dgrad_form.get(f"{i}.out"))
+        # The out-proj weight gradient (2048 x 2048: 64 tiles) waits for the qkv one (6144 x 2048: 192 tiles of 256 rows) where the two fill the chip
+        # exactly once TOGETHER (K.gemm_tn_pair): one launch instead of 256 tiles of 192 rows + a split-K launch + its reduce pass; few tiles over a long
+        # contraction (UniDisc-S: 27 + 9) share ONE split-K launch
+        if R.rows_c is not None:   # back to all rows: the rows left out have a zero gradient in both the attention output and the residual stream
+            self._wgrad(da, R.o_c, lo, G)
+            do = torch.zeros((M, d), dtype=do.dtype, device=dev).index_copy_(0, R.rows_c, do)
+            bp.dx = torch.zeros((M, d), dtype=F32, device=dev).index_copy_(0, R.rows_c, bp.dx)
+        elif multi is not None:
+            multi.append((da, R.o, lo))
+        elif (self.pair_wgrads and da.is_cuda and lo.bias is None and lq.bias is None and lo.inp == lq.inp
+                and K.gemm_tn_pair_ok(lq.out, lo.out, lq.inp, M)
+                and ((lq.out // 256 + lo.out // 256) * (lq.inp // 256) % 256 == 0 or (lq.out // 256 + lo.out // 256) * (lq.inp // 256) <= 128)):
+            pair_out = (da, R.o)
+        else:
+            self._wgrad(da, R.o, lo, G)
+        dqkr, dqkv = torch.empty((M, 2 * d), dtype=BF16, device=dev), torch.empty((M, 3 * d), dtype=BF16, device=dev)
+        K.attention_bwd(R.qkr, R.qkv, R.o, do, R.lse, dqkr, dqkv, B, L, H, D, S.sid, S.doc_ranges, q_prescaled=True, **self._attn_mask_kw, **S.attn_drop_kw(i))
+        qn = self.qk_norm
+        K.qknorm_rope_bwd(dqkr, R.qkv, dqkv, S.cos, S.sin, L, D, gq=at.q_norm.weight.detach() if qn else None, gk=at.k_norm.weight.detach() if qn else None,
+                          stats=R.qstats, dgq=G[id(at.q_norm.weight)] if qn else None, dbq=G[id(at.q_norm.bias)] if qn else None,
+                          dgk=G[id(at.k_norm.weight)] if qn else None, dbk=G[id(at.k_norm.bias)] if qn else None, q_scale=self.attn_q_scale)
+        dh1 = lq.dgrad(dqkv, dqkv.shape[0], S.dgrad_form.get(f"{i}.qkv"))
+        if multi is not None:
+            multi.append((dqkv, R.h1, lq))
+            if not K.gemm_tn_multi([(dy_, x_, G[id(l_.weight)]) for dy_, x_, l_ in multi]):
+                for dy_, x_, l_ in multi:    # (shapes outside the shared launch: the plain calls)
+                    self._wgrad(dy_, x_, l_, G, bias_done=True)
+        elif pair_out is not None:
+            K.gemm_tn_pair(dqkv, R.h1, G[id(lq.weight)], pair_out[0], pair_out[1], G[id(lo.weight)])
+        else:
+            self._wgrad(dqkv, R.h1, lq, G)
+        # norm1 pairs with the MLP branch of block i - 1 (with adaLN: where the fused pass covers the shape); this block is finished after that pass
+        pn = _PendingNorm(dy=dh1, x=R.x_in, rstd=R.rstd1, mean=R.mean1, w=blk.norm1.weight.detach(), dw=G[id(blk.norm1.weight)], accumulate=True,
+                          mod=mod, dmod=dmod, mod_idx=(0, 1), finish=i)
+        if tc and not bp.tc_fused:
+            self._norm_backward(bp, pn)
+        else:
+            bp.pend = pn
 
-        # ---- embeddings
-        if S.get("cnt_j") is not None:
-            n_cnt = self.img_count_embedding.shape[0]
-            if dx.is_cuda and dx.dtype == F32:   # sums formed in LDS per run of equal indices (an index_add_ here is 19 M contended atomics: 225 us)
-                K.rowgroup_sum(dx, S["cnt_j"], G[id(self.img_count_embedding)])
-            else:
-                gext = torch.zeros((n_cnt + 1, dx.shape[1]), dtype=dx.dtype, device=dx.device).index_add_(0, S["cnt_j"], dx)   # (row n_cnt collects the positions without an image index)
-                G[id(self.img_count_embedding)].add_(gext[:n_cnt])
-        K.embedding_bwd(S["ids"], dx, G[id(self.vocab_embed.embedding)], self.mask_index,
-                        modality=S["emb_mod"] if self.modality_embed is not None else None,
-                        dEm=G[id(self.modality_embed.embedding)] if self.modality_embed is not None else None)
-        tail = list(self.vocab_embed.parameters()) + (list(self.modality_embed.parameters()) if self.modality_embed is not None else [])
-        if getattr(self, "img_count_embedding", None) is not None:
-            tail.append(self.img_count_embedding)
-        if tc:  # c = silu(W2 silu(W0 te + b0) + b2)
-            dc16 = torch.empty((Bp, self.cond_dim), dtype=BF16, device=dev)
-            self._ada_collect(dc)
-            K.cast_f32_bf16(dc, dc16)
-            dl2 = K.silu_bwd(S["l2"], dc16)
-            ds1 = K.gemm_nt(dl2, lin["sig2"].w16t, N=lin["sig2"].inp)
-            self._wgrad(dl2, S["s1"], lin["sig2"], G)
-            dl1 = K.silu_bwd(S["l1"], ds1)
-            self._wgrad(dl1, S["te"], lin["sig0"], G)
-            tail += list(self.sigma_map.parameters())
-        self._notify(flat, tail)
-        if self.grad_sync_finish is not None:
-            self.grad_sync_finish()
-        # for the fused optimizer's one-pass global norm; a weak reference: the buffer lives exactly as long as the p.grad views do
-        self._last_grad_flat_ref, self._last_grad_numel = weakref.ref(flat), sum(p.numel() for p in params)
-        return [G[id(p)] for p in params]
+    def _sigma_map_backward(self, bp):
+        """c = silu(W2 silu(W0 te + b0) + b2)"""
+        S, G, lin = bp.S, bp.G, self._lins
+        dc16 = torch.empty((S.Bp, self.cond_dim), dtype=BF16, device=bp.dc.device)
+        if bp.ada_buf is not None and bp.ada_off:   # dc += the partial input-gradient tiles this pass's adaLN_modulation backwards left behind
+            bp.dc += bp.ada_buf[:bp.ada_off].sum(0)
+        K.cast_f32_bf16(bp.dc, dc16)
+        dl2 = K.silu_bwd(S.l2, dc16)
+        ds1 = K.gemm_nt(dl2, lin["sig2"].w16t, N=lin["sig2"].inp)
+        self._wgrad(dl2, S.s1, lin["sig2"], G)
+        dl1 = K.silu_bwd(S.l1, ds1)
+        self._wgrad(dl1, S.te, lin["sig0"], G)
 
-    def _ada_backward(self, dmod, lin: _Lin, c, dc, G):
+    def _ada_backward(self, bp, dmod, lin: _Lin):
         """adaLN_modulation backward: dmod fp32 [Bp, n*d] (atomically accumulated) -> dW, db, dc += dmod W."""
-        buf = getattr(self, "_ada_buf", None)
-        if buf is not None and lin.w16 is not None:
+        G, c = bp.G, bp.S.c
+        if bp.ada_buf is not None and lin.w16 is not None:
             # one launch (round 5): the input gradient as a GEMM is M = Bp rows, ONE output tile, K = 6 d - a single workgroup walking 12 288 k took ~140 us per block
             tiles = K.small_batch_linear_bwd_tiles(lin.out)
-            parts = buf[self._ada_off:self._ada_off + tiles]
-            self._ada_off += tiles
+            parts = bp.ada_buf[bp.ada_off:bp.ada_off + tiles]
+            bp.ada_off += tiles
             K.small_batch_linear_bwd(dmod, c, lin.w16, G[id(lin.weight)], G[id(lin.bias)] if lin.bias is not None else None, dx_parts=parts)
             return
         dmod16 = torch.empty(dmod.shape, dtype=BF16, device=dmod.device)
         K.cast_f32_bf16(dmod, dmod16)
         self._wgrad(dmod16, c, lin, G)
-        K.gemm_nt(dmod16, lin.w16t, out=dc, N=lin.inp, beta=1.0)
-
-
-    def _ada_collect(self, dc):
-        """dc += the partial input-gradient tiles this pass's adaLN_modulation backwards left behind"""
-        buf, off = getattr(self, "_ada_buf", None), getattr(self, "_ada_off", 0)
-        self._ada_buf, self._ada_off = None, 0
-        if buf is not None and off:
-            dc += buf[:off].sum(0)
-        return dc
+        K.gemm_nt(dmod16, lin.w16t, out=bp.dc, N=lin.inp, beta=1.0)
 
 
 class _DitFn(torch.autograd.Function):
     """One autograd node for the whole backbone (+ fused SUBS cross-entropy in "logp" mode)."""
 
     @staticmethod
-    def forward(ctx, module: DIT, mode: str, inputs: dict, *params):
-        need = bool(inputs.get("save", False))  # grad mode is off inside Function.forward, so the caller decides
-        out, S = module._engine_forward(inputs, mode, save=need)
-        ctx.module, ctx.mode, ctx.S = module, mode, S if need else None
+    def forward(ctx, module: DIT, mode: str, inputs: _EngineInputs, *params):
+        out, S = module._engine_forward(inputs, mode, save=bool(inputs.save))   # (grad mode is off inside Function.forward, so the caller decided)
+        ctx.module, ctx.mode, ctx.S = module, mode, S if inputs.save else None
         return out
 
     @staticmethod
