@@ -253,6 +253,15 @@ int udm_attention_fwd_kv_split(const void* q, const void* k, const void* v, void
                                int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t q_batch, int64_t k_batch, int64_t v_batch,
                                int64_t o_batch, float* ws, int64_t ws_elems, int64_t splits, int64_t flags, hipStream_t stream);
 int udm_attention_kv_split_plan(int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t D, int64_t splits, int64_t* splits_out, int64_t* ws_elems_out);
+/* The causal form of udm_attention_fwd_kv (chunked prefill over a K / V cache; the reference's DIT.forward(start_pos=...), models/dit.py:1324-1338, :776-780):
+ * o[b, i, h, :] = softmax over the keys j <= i + (Lk - Lq) of (q[b, i, h] . k[b, j, h]) v[b, j, h], 0 <= i < Lq - the queries are the LAST Lq of the Lk
+ * positions.  Arguments, addressing, the optional lse and the guarantees are those of udm_attention_fwd_kv (k and v are only read; no key row >= Lk and no
+ * query / output row >= Lq is addressed); flags: UDM_ATTN_Q_PRESCALED only; Lk < Lq is an argument error on top of the others.  A 128-query block walks
+ * the 64-key tiles up to its last query's frontier only (attn_kv_causal_walk_end, csrc/attention_plan.h).  Key 0 is visible to every query: no row is dead,
+ * every lse is finite.  A query that sees every key (i = Lq - 1; all of them at Lq = 1) gets the bits udm_attention_fwd_kv gives it.  No split form. */
+int udm_attention_fwd_kv_causal(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t D,
+                                int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t q_batch, int64_t k_batch, int64_t v_batch,
+                                int64_t o_batch, int64_t flags, hipStream_t stream);
 
 /* ---- embeddings: EmbeddingLayer models/dit.py:1036-1043 (+modality embedding :1402-1411) ------------- */
 /* ids outside [0, V): the forward CLAMPS them (a negative id reads row 0, an id >= V row V - 1); the backward DROPS them from dE and still counts their rows

@@ -54,6 +54,7 @@ PROTOTYPES = {
     "udm_attention_fwd_kv": [_P, _P, _P, _P, _P] + [_I64] * 14 + [_P],
     "udm_attention_fwd_kv_split": [_P, _P, _P, _P, _P] + [_I64] * 13 + [_P, _I64, _I64, _I64, _P],
     "udm_attention_kv_split_plan": [_I64] * 6 + [_P, _P],
+    "udm_attention_fwd_kv_causal": [_P, _P, _P, _P, _P] + [_I64] * 14 + [_P],
     "udm_attention_fwd": [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P],
     "udm_attention_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P],
     "udm_attention_fwd_dropout": [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _F, _U64, _P],

@@ -1,7 +1,8 @@
 // Rectangular flash attention forward (inference only): Lq queries against Lk keys / values that live in another buffer - a per-layer K / V cache.
 //   o[b, i, h, :] = softmax_j(q[b, i, h] . k[b, j, h]) v[b, j, h],  0 <= i < Lq, 0 <= j < Lk
 // The consumer: the text steps of `eval.attention_caching` with eval.attention_caching_read_cache (text queries against [fresh text keys ; cached image
-// keys], the reference's stated intent at models/dit.py:790-792).  Bidirectional only: a causal form (chunked prefill) has no caller yet and is not built.
+// keys], the reference's stated intent at models/dit.py:790-792).  udm_attention_fwd_kv and its split form are bidirectional; the causal form is an entry of
+// its own, udm_attention_fwd_kv_causal (below).
 //
 // The body is the 8-wave forward of attention.hip (attn_fwd_kernel) without sample ids and dropout: 128 queries per workgroup (4 waves x 32), 64-key tiles,
 // S^T = K Q^T so that a lane owns one query column and the softmax state is lane-local, K / V tiles by LDS-DMA into two XOR-swizzled stages each, the lazy
@@ -11,6 +12,10 @@
 // rows another one writes).  Key rows >= Lk are never addressed (an overhanging tile re-reads row Lk - 1 and masks it), query rows >= Lq neither.
 // udm_attention_fwd_kv_split is the same body with the keys split over S workgroups per (query block, b, h) and a combine launch: the read steps of the
 // conditioning K / V cache (`eval.conditioning_cache`) run at batch 1 or 2, where the unsplit grid leaves most CUs idle.
+// udm_attention_fwd_kv_causal is the same body under the rectangular causal mask: query i sees the keys j <= i + (Lk - Lq), the queries being the LAST Lq
+// positions (Lk >= Lq).  The consumer: the chunked cached forward of the AR baseline (DIT._forward_chunk: n tokens at cache slots [p, p + n) against the keys
+// [0, p + n)).  A workgroup walks key tiles only up to the frontier of its last live query (attn_kv_causal_walk_end, attention_plan.h), and only a tile that
+// crosses the frontier of one of a wave's 32 queries takes the per-element test.  Key 0 is visible to every query, so no row is ever dead.  No split form.
 #include "attention_common.h"
 #include <type_traits>
 
@@ -32,7 +37,8 @@ struct AttnKvArgs {
 
 // SPLIT (udm_attention_fwd_kv_split): the workgroup walks the key tiles of ONE of S contiguous ranges and leaves its softmax state - the reference exponent m c,
 // the row sum l and the unnormalised O - in fp32 in `ws` instead of dividing and storing O; attn_kv_combine_kernel folds the S partials of a row.
-template <int D, bool SPLIT>
+// CAUSAL (udm_attention_fwd_kv_causal): the walk ends at the block's frontier and the tiles that cross a wave's frontier are masked per element.
+template <int D, bool SPLIT, bool CAUSAL = false>
 __device__ __forceinline__ void attn_fwd_kv_body(const AttnKvArgs& a, float* ws, int S) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // K0 | K1 | V0 | V1   (one array: keeps LDS-DMA waits exact)
   constexpr int TB = BKV * D * 2;
@@ -74,6 +80,10 @@ __device__ __forceinline__ void attn_fwd_kv_body(const AttnKvArgs& a, float* ws,
   plank.init(a.k_stride, wave, lane);
   planv.init(a.v_stride, wave, lane);
   int t_begin = 0, t_end = (a.Lk + BKV - 1) / BKV;
+  // causal: the last key query qi sees, and the first key some query of this wave does NOT see (wave-uniform: tiles that end before it need no test)
+  const int off = a.Lk - a.Lq, k_last = qi + off;
+  const int wave_front = tile_x * BQ + wave * 32 + off + 1;
+  if constexpr (CAUSAL) t_end = (int)attn_kv_causal_walk_end(a.Lq, a.Lk, tile_x);   // (the staging below is bounded by a.Lk and t_end, whichever tile the walk ends at)
   if constexpr (SPLIT) {   // attn_kv_split_range (attention_plan.h): S <= tiles, so no range is empty
     const int base = t_end / S, rem = t_end % S;
     t_begin = split * base + min(split, rem);
@@ -118,7 +128,27 @@ __device__ __forceinline__ void attn_fwd_kv_body(const AttnKvArgs& a, float* ws,
         for (int f = 0; f < 2; ++f) sT[f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kq[ks % 3][f], qf[ks], sT[f], 0, 0, 0);
       }
     }
-    if (kv0 + BKV > a.Lk) {   // the ragged last tile (before the running maximum: a masked score contributes exp2(-inf) = 0 exactly)
+    // Causal: mvote is the tile maximum BEFORE the causal mask (after the ragged one): the wave votes on it (below), so it takes the rescale branch exactly
+    // where the bidirectional kernel does, and a query that sees every key - the last one - goes through the same arithmetic bit for bit.  What a lane moves
+    // its exponent TO is the maximum of the keys it sees.
+    float mvote = -INFINITY;
+    if constexpr (CAUSAL) {
+      // ONE wave-uniform branch per tile, as in the bidirectional body: the tile overhangs Lk, or crosses the frontier of one of this wave's queries.
+      // Element (f, r) is key kv0 + 4 hi + a compile-time constant, so each test is that constant against one per-lane value of the tile.
+      if (kv0 + BKV > min(wave_front, a.Lk)) {
+        const int rel_lk = a.Lk - 1 - kv0 - 4 * hi, rel = min(k_last, a.Lk - 1) - kv0 - 4 * hi;
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int kc = f * 32 + (r & 3) + 8 * (r >> 2);
+            const float s_lk = kc > rel_lk ? -INFINITY : sT[f][r];   // the ragged mask: what the bidirectional kernel's maximum is taken over
+            mvote = fmaxf(mvote, s_lk);
+            sT[f][r] = kc > rel ? -INFINITY : s_lk;
+          }
+        mvote = fmaxf(mvote, __shfl_xor(mvote, 32, 64));
+      }
+    } else if (kv0 + BKV > a.Lk) {   // the ragged last tile (before the running maximum: a masked score contributes exp2(-inf) = 0 exactly)
 #pragma unroll
       for (int f = 0; f < 2; ++f)
 #pragma unroll
@@ -134,8 +164,9 @@ __device__ __forceinline__ void attn_fwd_kv_body(const AttnKvArgs& a, float* ws,
 #pragma unroll
       for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, sT[f][r]);
     mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
+    if constexpr (CAUSAL) mvote = fmaxf(mvote, mloc);   // (a tile without a test: the maximum itself; with one: the unmasked maximum is the larger)
     // Lazy rescale (attn_fwd_kernel): m is the REFERENCE exponent of this query, moved only when some query of the wave saw a score more than 2^8 above it.
-    const bool move = q_ok && (mloc * c > m * c + 8.0f);   // (lanes of query rows past Lq never vote)
+    const bool move = q_ok && ((CAUSAL ? mvote : mloc) * c > m * c + 8.0f);   // (lanes of query rows past Lq never vote)
     if (__builtin_amdgcn_ballot_w64(move) != 0) {
       const float m_new = fmaxf(m, mloc);
       const float alpha = __builtin_amdgcn_exp2f((m - ((m_new == -INFINITY) ? 0.f : m_new)) * c);
@@ -216,6 +247,8 @@ template <int D>
 __global__ __launch_bounds__(256, ATTN_KV_WGS(D)) void attn_fwd_kv_kernel(AttnKvArgs a) { attn_fwd_kv_body<D, false>(a, nullptr, 1); }
 template <int D>
 __global__ __launch_bounds__(256, ATTN_KV_WGS(D)) void attn_fwd_kv_split_kernel(AttnKvArgs a, float* ws, int S) { attn_fwd_kv_body<D, true>(a, ws, S); }
+template <int D>
+__global__ __launch_bounds__(256, ATTN_KV_WGS(D)) void attn_fwd_kv_causal_kernel(AttnKvArgs a) { attn_fwd_kv_body<D, false, true>(a, nullptr, 1); }
 
 // The S partials of a query row, folded in the fixed order s = 0 .. S - 1 (no atomics: the same bits on every launch): M = max_s m_s,
 // O = sum_s 2^(m_s - M) O_s / sum_s 2^(m_s - M) l_s, one rounding to bf16; lse2 = M + log2 of that denominator.  One thread per (row, four columns).
@@ -263,6 +296,13 @@ void launch_kv(const AttnKvPlan& plan, const AttnKvArgs& a, hipStream_t s) {
   if (!once) { (void)hipFuncSetAttribute((const void*)attn_fwd_kv_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes); once = true; }
   hipLaunchKernelGGL((attn_fwd_kv_kernel<D>), dim3(plan.grid), dim3(256), plan.lds_bytes, s, a);
 }
+
+template <int D>
+void launch_kv_causal(const AttnKvPlan& plan, const AttnKvArgs& a, hipStream_t s) {
+  static bool once = false;
+  if (!once) { (void)hipFuncSetAttribute((const void*)attn_fwd_kv_causal_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes); once = true; }
+  hipLaunchKernelGGL((attn_fwd_kv_causal_kernel<D>), dim3(plan.grid), dim3(256), plan.lds_bytes, s, a);
+}
 }  // namespace
 
 namespace {
@@ -271,14 +311,17 @@ int kv_device_cus() {
   return n;
 }
 
-// both entry points: the argument checks, then the unsplit launch (split_form = false, or a split count that came down to 1) or the split pair
-int kv_entry(const char* name, bool split_form, const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t D,
+// all three entry points: the argument checks, then the unsplit launch (split_form = false, or a split count that came down to 1), the split pair, or the
+// causal kernel (causal_form; never with split_form)
+int kv_entry(const char* name, bool split_form, bool causal_form, const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t D,
              int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t q_batch, int64_t k_batch, int64_t v_batch, int64_t o_batch, float* ws,
              int64_t ws_elems, int64_t splits, int64_t flags, hipStream_t stream) {
   UDM_CHECK_ARG(q && k && v && o, "%s: null pointer", name);
-  UDM_CHECK_ARG((flags & ~(int64_t)UDM_ATTN_Q_PRESCALED) == 0, "%s: unknown flags %ld (UDM_ATTN_Q_PRESCALED only: there is no causal form)", name, (long)flags);
+  UDM_CHECK_ARG((flags & ~(int64_t)UDM_ATTN_Q_PRESCALED) == 0, "%s: unknown flags %ld (UDM_ATTN_Q_PRESCALED only: the causal form is udm_attention_fwd_kv_causal)", name,
+                (long)flags);
   UDM_CHECK_ARG(B > 0 && H > 0, "%s: empty problem", name);
   UDM_CHECK_ARG(Lq >= 1 && Lk >= 1, "%s: Lq = %ld, Lk = %ld (both >= 1)", name, (long)Lq, (long)Lk);
+  UDM_CHECK_ARG(!causal_form || Lk >= Lq, "%s: Lk = %ld < Lq = %ld (the queries are the last Lq of the Lk positions)", name, (long)Lk, (long)Lq);
   UDM_CHECK_ARG(D == 32 || D == 64 || D == 128 || D == 256, "%s: head_dim %ld unsupported (32, 64, 128, 256)", name, (long)D);
   UDM_CHECK_ARG(q_stride % 8 == 0 && k_stride % 8 == 0 && v_stride % 8 == 0 && o_stride % 8 == 0, "%s: row strides must be multiples of 8 elements", name);
   UDM_CHECK_ARG(q_batch % 8 == 0 && k_batch % 8 == 0 && v_batch % 8 == 0 && o_batch % 8 == 0, "%s: batch strides must be multiples of 8 elements", name);
@@ -316,6 +359,16 @@ int kv_entry(const char* name, bool split_form, const void* q, const void* k, co
     UDM_CHECK_LAUNCH(name);
     return 0;
   }
+  if (causal_form) {
+    switch (plan.D) {
+      case 256: launch_kv_causal<256>(plan, a, stream); break;
+      case 128: launch_kv_causal<128>(plan, a, stream); break;
+      case 64: launch_kv_causal<64>(plan, a, stream); break;
+      default: launch_kv_causal<32>(plan, a, stream); break;
+    }
+    UDM_CHECK_LAUNCH(name);
+    return 0;
+  }
   switch (plan.D) {
     case 256: launch_kv<256>(plan, a, stream); break;
     case 128: launch_kv<128>(plan, a, stream); break;
@@ -330,15 +383,22 @@ int kv_entry(const char* name, bool split_form, const void* q, const void* k, co
 extern "C" int udm_attention_fwd_kv(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t D, int64_t q_stride,
                                     int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t q_batch, int64_t k_batch, int64_t v_batch, int64_t o_batch, int64_t flags,
                                     hipStream_t stream) {
-  return kv_entry("udm_attention_fwd_kv", false, q, k, v, o, lse, B, H, Lq, Lk, D, q_stride, k_stride, v_stride, o_stride, q_batch, k_batch, v_batch, o_batch, nullptr, 0, 1,
+  return kv_entry("udm_attention_fwd_kv", false, false, q, k, v, o, lse, B, H, Lq, Lk, D, q_stride, k_stride, v_stride, o_stride, q_batch, k_batch, v_batch, o_batch, nullptr, 0, 1,
                   flags, stream);
 }
 
 extern "C" int udm_attention_fwd_kv_split(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t D,
                                           int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t q_batch, int64_t k_batch, int64_t v_batch,
                                           int64_t o_batch, float* ws, int64_t ws_elems, int64_t splits, int64_t flags, hipStream_t stream) {
-  return kv_entry("udm_attention_fwd_kv_split", true, q, k, v, o, lse, B, H, Lq, Lk, D, q_stride, k_stride, v_stride, o_stride, q_batch, k_batch, v_batch, o_batch, ws,
+  return kv_entry("udm_attention_fwd_kv_split", true, false, q, k, v, o, lse, B, H, Lq, Lk, D, q_stride, k_stride, v_stride, o_stride, q_batch, k_batch, v_batch, o_batch, ws,
                   ws_elems, splits, flags, stream);
+}
+
+extern "C" int udm_attention_fwd_kv_causal(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t D,
+                                           int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t q_batch, int64_t k_batch, int64_t v_batch,
+                                           int64_t o_batch, int64_t flags, hipStream_t stream) {
+  return kv_entry("udm_attention_fwd_kv_causal", false, true, q, k, v, o, lse, B, H, Lq, Lk, D, q_stride, k_stride, v_stride, o_stride, q_batch, k_batch, v_batch, o_batch,
+                  nullptr, 0, 1, flags, stream);
 }
 
 extern "C" int udm_attention_kv_split_plan(int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t D, int64_t splits, int64_t* splits_out, int64_t* ws_elems_out) {

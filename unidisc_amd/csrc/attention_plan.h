@@ -150,6 +150,16 @@ inline AttnKvPlan attn_plan_fwd_kv(const AttnKvProblem& p) {
   return plan;
 }
 
+// ---- the causal form (attention_kv.hip, udm_attention_fwd_kv_causal): query i sees the keys j <= i + (Lk - Lq), the queries being the LAST Lq positions
+// (Lk >= Lq; chunked prefill over a K / V cache).  The plan is attn_plan_fwd_kv's; what differs is where a workgroup's walk ends: the 128-query block
+// `q_tile` walks the 64-key tiles [0, end) with end = ceil((min(128 (q_tile + 1), Lq) + Lk - Lq) / 64) - the tiles that hold a key visible to its LAST live query.
+// Every visible key of the block lies in a walked tile and the last walked tile holds one (tests/test_attention_kv_causal_plan.py, against brute force).
+// constexpr: the kernel calls it too.
+constexpr long attn_kv_causal_walk_end(long Lq, long Lk, long q_tile) {
+  const long q_end = 128 * (q_tile + 1) < Lq ? 128 * (q_tile + 1) : Lq;
+  return (q_end + (Lk - Lq) + 63) / 64;
+}
+
 // ---- the key-split form (attention_kv.hip, udm_attention_fwd_kv_split): the same body, S workgroups per (128-query block, b, h), each over a contiguous range
 // of 64-key tiles; fp32 partials (m, l, unnormalised O) per query row in a workspace, a second launch combines them in the fixed order s = 0 .. S - 1.
 // The consumer is the conditioning K / V cache at batch 1 or 2 (DESIGN.md "Conditioning K/V cache"): 256 queries against 1280 keys are 32 workgroups unsplit.

@@ -1026,6 +1026,39 @@ class Diffusion:
             n0 += int(run.cumprod(0).sum())
         return min(n0, L - 1)
 
+    # eval.ar_chunk_min_tokens when the key is unset: the smallest chunk (tokens of one _forward_chunk call) worth leaving the decode path for.  Measured
+    # (scripts/bench_ar_chunked.py part (a), RESULTS.md "Chunked cached forward"; n = 2, 4, 8, ... at p = 256): one chunk forward costs about three decode
+    # steps at 1.4 B with 8 rows (n = 2: 1.46 x the two steps, n = 4: 0.74 x) and about one everywhere else measured (n = 2: 0.78 - 0.96 x), so 4 is the
+    # smallest measured n that wins at both row counts of both models.  n = 3 was not measured.
+    AR_CHUNK_MIN_TOKENS = 4
+
+    @staticmethod
+    def _ar_given_columns(x0_unmask):
+        """given[c - 1]: column c >= 1 is given in every row - the one host read of eval.ar_chunk_given, before the token loop"""
+        return x0_unmask[:, 1:].all(0).cpu().tolist()
+
+    @staticmethod
+    def _ar_given_runs(given, n0, L, min_tokens):
+        """eval.ar_chunk_given: where the token loop of _ar_sampler leaves the decode path.  given[c - 1]: column c (1 <= c < L) is given in EVERY row
+        (x0_unmask[:, 1:].all(0), on the host); n0: the prefilled prefix (_ar_fixed_prefix).  -> {i: r}: at step i >= n0 the columns i + 1 .. i + r are a
+        maximal such run behind the prefix, so the r + 1 tokens of positions i .. i + r go through one _forward_chunk at start_pos = i, and choose(i + r)
+        follows.  Position L - 1 is never fed (the cache holds L - 1 slots), so a run that reaches the last column is cut at L - 2.  Runs with
+        r + 1 < min_tokens stay on the decode path; a run that touches the prefix is the prefix's (n0 already counts it)."""
+        given = [bool(g) for g in given]
+        assert len(given) == L - 1
+        runs, c = {}, n0 + 1            # (column n0 is not given in every row, or n0 = L - 1 and nothing is left)
+        while c < L:
+            if not given[c - 1]:
+                c += 1
+                continue
+            a = c
+            while c < L and given[c - 1]:
+                c += 1
+            i, r = a - 1, min(c - 1, L - 2) - (a - 1)      # the run is columns a .. c - 1
+            if r >= 1 and r + 1 >= min_tokens:
+                runs[i] = r
+        return runs
+
     @staticmethod
     def _ar_nucleus(z, top_p, temperature, generator=None):
         """`nucleus_sampling` (model_eval.py:2691-2734), not the p / T quirk of nucleus_sampling_batch: softmax(z / T), sort, keep cumsum <= top_p plus the top
@@ -1041,7 +1074,10 @@ class Diffusion:
         """Next-token sampling of the AR baseline, KV-cached: x[:, 0] = BOS, x0 / x0_unmask conditioning, the fixed prefix prefilled in one causal forward,
         then one decode step per token; token = argmax(next + Gumbel) (noise [B, L-1, V] replays a recorded draw, otherwise Philox Gumbel from `seed`), or
         the reference's nucleus_sampling with eval.top_p.  CFG (eval.cfg with x0, eval.force_cfg_value) runs [x ; where(x0_unmask, [MASK], x)] as one
-        batch on one cache.  Returns (x [B, L], nfe) - nfe counts the argmax steps (0 with top_p, the reference's quirk)."""
+        batch on one cache.  eval.ar_chunk_given (extension): a run of columns behind the prefix that is given in every row is fed through ONE chunk
+        forward over the cache (DIT._forward_chunk) instead of one decode step per token (_ar_given_runs; runs shorter than eval.ar_chunk_min_tokens and
+        columns given in some rows only stay on the decode path).  Returns (x [B, L], nfe) - nfe counts the argmax steps (0 with top_p, the reference's
+        quirk), chunked or not."""
         self._ar_require_gpu()
         assert B > 0
         assert (x0 is None) == (x0_unmask is None)
@@ -1087,6 +1123,11 @@ class Diffusion:
         logits = kv.logits
 
         fused_top_p = top_p is not None and self._fused_nucleus(logits)
+        chunk_given = bool(cfg_get(ev, "ar_chunk_given", False))
+        if chunk_given and top_p is not None and not fused_top_p:
+            bb.reset_kv_cache(set_to_none=True)
+            raise NotImplementedError("unidisc_amd.Diffusion._ar_sampler: eval.ar_chunk_given with the tensor top-p path - its torch.Generator stream is "
+                                      "sequential, so skipped steps would move every later draw; eval.fused_nucleus and the Gumbel paths key their draws by step")
 
         def choose(i):   # token of position i + 1 from kv.logits (the next-token logits of position i); writes x and kv.ids
             if fused_top_p:   # eval.fused_nucleus: nucleus_sampling (softmax(z / T) against top_p) in one launch, no tensor operators
@@ -1119,11 +1160,27 @@ class Diffusion:
             mod0 = modality[:, :n0]
             if guided:
                 mod0 = torch.cat([mod0, mod0], 0)
+        # eval.ar_chunk_given (extension key, default false): runs of columns given in every row go through one chunk forward over the cache instead of one
+        # decode step per token.  The segmentation is fixed here, from the one host read _ar_fixed_prefix makes too; unset, `runs` is empty.
+        runs = {}
+        if chunk_given and x0_unmask is not None:
+            min_tokens = int(cfg_get(ev, "ar_chunk_min_tokens", None) or self.AR_CHUNK_MIN_TOKENS)
+            runs = self._ar_given_runs(self._ar_given_columns(x0_unmask), n0, L, max(min_tokens, 2))
         bb._prefill(ids0, mod0, last_only=True)
         choose(n0 - 1)
-        for i in range(n0, n_pred):
-            bb._decode_step(i)
-            choose(i)
+        i = n0
+        while i < n_pred:
+            r = runs.get(i, 0)
+            if r:   # positions i .. i + r are final in every row (x[:, i] was just chosen, the rest is given): their logits are never drawn from but the last's
+                ids = x[:, i:i + r + 1]
+                if guided:
+                    ids = torch.cat([ids, torch.where(x0_unmask, self.mask_index, x)[:, i:i + r + 1]], 0)
+                bb._forward_chunk(ids, None, i, last_only=True)      # (modality columns i .. i + r: the cache's full-length map)
+                i += r
+            else:
+                bb._decode_step(i)
+            choose(i)   # (the Philox draws are keyed by the step: the steps a chunk skipped move no other draw)
+            i += 1
         bb.reset_kv_cache(batch_size=R, seq_len=n_pred, dtype=self.dtype, device=dev, set_to_none=True)
         return x, (n_pred if top_p is None else 0)
 

@@ -226,13 +226,15 @@ class _Lin:
 @dataclass
 class _KVRead:
     """Attend to a K / V cache: K, V per block [B, Lmax, d]; slot0: where this call's rows go; Lk: the slots the queries see; split: the conditioning cache's
-    form (small batches, the keys split over workgroups where the plan says so) with its workspace `ws`."""
+    form (small batches, the keys split over workgroups where the plan says so) with its workspace `ws`; causal: the chunked cached forward of a causal
+    backbone (query i sees the slots j <= i + Lk - L: with slot0 = Lk - L its own slot and everything before it; udm_attention_fwd_kv_causal, no split form)."""
     K: list
     V: list
     slot0: int
     Lk: int
     split: bool = False
     ws: Optional[torch.Tensor] = None
+    causal: bool = False
 
 
 @dataclass
@@ -601,6 +603,30 @@ class DIT(nn.Module, _HubMixin):
         kv.pos = n
         return out if last_only else out[:B]
 
+    @torch.no_grad()
+    def _forward_chunk(self, ids, modality, p, last_only=False):
+        """start_pos = p > 0 over n >= 1 tokens of every cached row (chunked prefill): the engine's ordinary forward on the n positions p .. p + n - 1 - rotary
+        rows and modality columns p .. p + n - 1 of the full-length tables - whose attention writes this call's post-rope k and v into cache slots [p, p + n)
+        and lets query i see the slots [0, p + i] (udm_attention_fwd_kv_causal).  The slots [0, p) must have been written (p <= self._kv.pos: the caller's
+        check).  ids / modality [B, n], rows padded with row 0 as in _prefill.  Returns logits [B, n, V], or with last_only the logits of position p + n - 1
+        in self._kv.logits [Bp, Vp]; self._kv.pos = p + n."""
+        kv = self._kv
+        B, n = ids.shape
+        Bp = kv.Bp
+        pad = lambda t: torch.cat([t, t[:1].expand(Bp - B, *t.shape[1:])], 0) if (t is not None and Bp > B) else t   # noqa: E731
+        idsp = pad(ids.to(torch.int64)).contiguous()
+        mod = modality.to(torch.int64) if modality is not None else (kv.mod_full[:B, p:p + n] if kv.mod_full is not None else None)
+        modp = pad(mod).contiguous() if mod is not None else None
+        if kv.cos is not None:
+            rope = (kv.cos[p:p + n].transpose(0, 1).contiguous(), kv.sin[p:p + n].transpose(0, 1).contiguous())
+        else:
+            rope = (self.rotary_cos_emb[p:p + n].contiguous(), self.rotary_sin_emb[p:p + n].contiguous())
+        inputs = _EngineInputs(indices=idsp, modality=modp, kv_read=_KVRead(K=kv.K, V=kv.V, slot0=p, Lk=p + n, causal=True), rope=rope,
+                               head_out=kv.logits if last_only else None)
+        out, _ = self._engine_forward(inputs, "logits", save=False)
+        kv.pos = p + n
+        return out if last_only else out[:B]
+
     def set_flex_attention_cache(self, batch_size=None, seq_len=None, device=None, dtype=None, read_cache=False):
         """read_cache (extension, eval.attention_caching_read_cache): allocate per block bf16 K / V [batch_size, seq_len, d] (2 GB at 1.4 B, B = 8) that the
         build step fills (every position's post-rope k and its v) and the text steps read: forward_masked_logits(modality_cache="build" / "read")."""
@@ -800,8 +826,10 @@ class DIT(nn.Module, _HubMixin):
 
     @torch.no_grad()
     def _forward_cached(self, indices, modality, start_pos, attention_mask, block_mask):
-        """forward(start_pos=p) on the KV cache (reset_kv_cache first): one token per row at p (decode step, logits [B, 1, V]) or n >= 1 tokens at p = 0
-        (prefill, logits [B, n, V]).  Anything else - several tokens at p > 0 (chunked prefill) - is not built."""
+        """forward(start_pos=p) on the KV cache (reset_kv_cache first), the reference's models/dit.py:1324-1338 with :776-780: n >= 1 tokens at p = 0 (prefill,
+        logits [B, n, V]), one token per row at p > 0 (the decode step, logits [B, 1, V]), or n > 1 tokens at p > 0 (a chunk: the engine's forward over the
+        cache, _forward_chunk, logits [B, n, V]).  A chunk or a step may start at any p <= the number of slots written so far (rewriting slots is allowed,
+        leaving a gap is not) and must end inside the cache.  HIP kernels only: CPU tensors are refused before anything else is looked at."""
         if self._kv is None:
             raise RuntimeError("unidisc_amd.DIT.forward(start_pos=...): no KV cache - call reset_kv_cache(batch_size, seq_len, ...) first")
         if attention_mask is not None or (block_mask is not None and block_mask is not True):
@@ -814,8 +842,14 @@ class DIT(nn.Module, _HubMixin):
             K.require_gpu(indices)
             return self._prefill(indices, modality)
         if n != 1:
-            raise NotImplementedError(f"unidisc_amd.DIT.forward: start_pos={start_pos} with {n} tokens (multi-token decode / chunked prefill) is not built - "
-                                      "start_pos=0 prefills, start_pos=p > 0 takes one token per row")
+            if not indices.is_cuda:   # (first: nothing else of the cache is read for a call that cannot run)
+                raise NotImplementedError(f"unidisc_amd.DIT.forward: start_pos={start_pos} with {n} tokens runs on HIP kernels; there is no CPU path")
+            if start_pos < 0 or start_pos + n > kv.Lmax:
+                raise ValueError(f"unidisc_amd.DIT.forward: start_pos={start_pos} with {n} tokens outside the cache [0, {kv.Lmax})")
+            if start_pos > kv.pos:
+                raise ValueError(f"unidisc_amd.DIT.forward: start_pos={start_pos} with {n} tokens, but only the slots [0, {kv.pos}) are written - "
+                                 "the chunk would attend to slots nobody filled")
+            return self._forward_chunk(indices, modality, start_pos)
         if not 0 < start_pos < kv.Lmax:
             raise ValueError(f"unidisc_amd.DIT.forward: start_pos={start_pos} outside the cache [0, {kv.Lmax})")
         K.require_gpu(indices)
@@ -1125,7 +1159,9 @@ class DIT(nn.Module, _HubMixin):
         if S.p_attn > 0.0 and sid is not None:
             raise NotImplementedError("unidisc_amd.DIT: model.attn_dropout with packed sample_ids, a ModalityMask or an attention mask - the reference's "
                                       "FlexAttention path applies no attention dropout")
-        if S.kv_read is not None and (sid is not None or S.save or S.kv_sink is not None or self.causal):
+        # (a causal backbone reads a cache only through the causal kernel: _KVRead.causal, the chunked cached forward)
+        if S.kv_read is not None and (sid is not None or S.save or S.kv_sink is not None or self.causal != bool(S.kv_read.causal) or
+                                      (S.kv_read.causal and (S.kv_read.split or self.time_conditioning))):
             raise NotImplementedError("unidisc_amd.DIT: the cache-reading forward is an inference path without masks (no sample ids, ModalityMask, attention mask)")
         return raw_sid
 
@@ -1213,7 +1249,9 @@ class DIT(nn.Module, _HubMixin):
             s0 = kvr.slot0
             kvr.K[i][:, s0:s0 + L].copy_(qkr.view(B, L, 2 * d)[:, :, d:])
             kvr.V[i][:, s0:s0 + L].copy_(qkv.view(B, L, 3 * d)[:, :, 2 * d:])
-            if kvr.split:
+            if kvr.causal:
+                o, lse = K.attention_fwd_kv_causal(qkr[:, :d], kvr.K[i], kvr.V[i], B, L, kvr.Lk, H, D, q_prescaled=True), None
+            elif kvr.split:
                 o, lse = K.attention_fwd_kv_split(qkr[:, :d], kvr.K[i], kvr.V[i], B, L, kvr.Lk, H, D, q_prescaled=True, ws=kvr.ws), None
             else:
                 o, lse = K.attention_fwd_kv(qkr[:, :d], kvr.K[i], kvr.V[i], B, L, kvr.Lk, H, D, q_prescaled=True), None

@@ -872,6 +872,21 @@ def attention_fwd_kv(q, k_cache, v_cache, B, Lq, Lk, H, D, q_prescaled=False, ou
     return (out, lse) if want_lse else out
 
 
+def attention_fwd_kv_causal(q, k_cache, v_cache, B, Lq, Lk, H, D, q_prescaled=False, out=None, want_lse=False):
+    """K.attention_fwd_kv under the rectangular causal mask (udm_attention_fwd_kv_causal): query i of a sample sees the cache slots j <= i + (Lk - Lq) - the
+    queries are the LAST Lq of the Lk positions, a chunk of Lq tokens at the slots [Lk - Lq, Lk).  Same operands and layouts; Lk >= Lq."""
+    d = H * D
+    Bc, Lmax, dc = k_cache.shape
+    if Bc < B or dc != d or Lk > Lmax or tuple(v_cache.shape) != tuple(k_cache.shape) or k_cache.stride(2) != 1 or v_cache.stride(2) != 1 or q.stride(1) != 1:
+        raise ValueError(f"attention_fwd_kv_causal: cache {tuple(k_cache.shape)} / {tuple(v_cache.shape)} does not serve B={B}, Lk={Lk}, H D={d}")
+    if out is None:
+        out = torch.empty((B * Lq, d), dtype=BF16, device=q.device)
+    lse = torch.empty((B, H, Lq), dtype=F32, device=q.device) if want_lse else None
+    _lib.call("udm_attention_fwd_kv_causal", _p(q), _p(k_cache), _p(v_cache), _p(out), _p(lse), B, H, Lq, Lk, D, q.stride(0), k_cache.stride(1), v_cache.stride(1),
+              out.stride(0), Lq * q.stride(0), k_cache.stride(0), v_cache.stride(0), Lq * out.stride(0), _attn_flags(q_prescaled, False), _s())
+    return (out, lse) if want_lse else out
+
+
 def attention_kv_split_plan(B, Lq, Lk, H, D, splits=0):
     """(S, workspace floats) a K.attention_fwd_kv_split call of this shape runs with: splits = 0 asks the plan (csrc/attention_plan.h, for the current device),
     splits >= 1 forces a count; either is lowered to the key tiles and to 32."""
