@@ -175,8 +175,16 @@ int udm_qknorm_rope_bwd(const void* dqkr, const void* qkv, void* dqkv, const flo
 /* ---- attention core: flash_attn_qkvpacked_func models/dit.py:843 / SDPA :826-829 / FlexAttention doc mask :784-812
  * bidirectional softmax(QKᵀ/√D)V; element (b,l,h,:) of a tensor lives at base + (b*L+l)*stride + h*D.
  * Head dim D = 32 / 64 / 128 / 256 (256: the 8-wave kernels at one workgroup per CU; the backward runs dK and dV as two launches).
- * sample_ids [B,L] (or NULL): attend iff ids equal and != -1 (model_utils.py:740-771).  lse/delta fp32 [B,H,L].
- * doc_ranges int32 [B, ceil(L/64), 8] (or NULL), from udm_attention_doc_ranges on the same sample_ids: per 64-row tile {lo, hi, idmin, idmax, exact, 0, 0, 0}
+ * sample_ids int64 [B,L] (or NULL): attend iff ids equal and >= 0 - every id < 0 is padding (model_utils.py:740-771).  lse/delta fp32 [B,H,L].
+ * The slot carries MASK CODES, of which a raw sample id is the plain case:  bits 0-31 = the sample id (signed: the sign-extended low 32 bits), bits 32-39 = the
+ * KEY classes the position belongs to, bits 40-47 = the key classes it may see as a QUERY, bits 48-63 = 0.  Query i sees key j iff
+ *     id_i == id_j  and  id_i >= 0  and  (query_mask_i & key_class_j) != 0,
+ * where a zero key-class field and a zero query-mask field each read as 0xff, "all": raw ids in [0, 2^31) are the plain document mask.  Modality attention
+ * dropout uses key class 1 = text, 2 = image; a key-padding mask gives padded keys class 4, which no query mask contains.  A query that sees no key gets O = 0,
+ * lse = +inf and dQ = 0; a key no query sees gets dK = dV = 0.
+ * doc_ranges int32 [B, ceil(L/64), 8] (or NULL), from udm_attention_doc_ranges on the same sample_ids - raw ids or codes with class bits, the ranges are computed
+ * on the id field and are valid for both; a 64-row tile that holds any position with a bit above bit 31 set is reported like a tile with padding (idmin = -1), so
+ * it only ever gains the tile skipping, never the skipped element test: per 64-row tile {lo, hi, idmin, idmax, exact, 0, 0, 0}
  * - the [lo, hi) span of positions that can share a sample id with the tile, so the kernels walk only those tiles; the tile's id interval (idmin = -1
  * when it holds padding), so that tile pairs inside one document skip the per-element id test (FlexAttention's BlockMask does both: empty / full /
  * partial blocks, model_utils.py:716-771); exact = the tile's one document occupies exactly [lo, hi) (such key blocks take the wave-specialised dK/dV

@@ -42,12 +42,38 @@ def score_scales(D, prescaled):
     return (1.0, LN2) if prescaled else (LOG2E / math.sqrt(D), 1.0 / math.sqrt(D))
 
 
-def visible(B, Lq, Lk, sample_ids=None, causal=False):
-    """bool [B, 1, Lq, Lk] (True = query i sees key j), or None when every pair is visible.  Causal: j <= i + (Lk - Lq) (the queries are the LAST Lq positions)."""
+def decode_codes(sample_ids):
+    """mask codes (csrc/attention_common.h) -> (id, key class, query mask): the id is the sign-extended low 32 bits, bits 32-39 the key class, bits 40-47 the
+    query mask; a zero class or mask field reads as 0xff ("all").  Raw sample ids decode to (id, 0xff, 0xff)."""
+    code = torch.as_tensor(sample_ids).to(torch.int64)
+    ids = ((code & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000
+    kcls, qmask = (code >> 32) & 0xFF, (code >> 40) & 0xFF
+    return ids, torch.where(kcls == 0, 0xFF, kcls), torch.where(qmask == 0, 0xFF, qmask)
+
+
+PREDICATE_MUTANTS = ("ignore_class_bits", "swap_mask_and_class", "class4_visible", "padding_is_minus_one_only")
+
+
+def pair_ok(sample_ids, mutant=None):
+    """bool [B, L, L]: attn_pair_ok of every (query i, key j) - ids equal and >= 0 and (qmask_i & kclass_j) != 0 - or one of PREDICATE_MUTANTS, a wrong predicate"""
+    ids, kcls, qmask = decode_codes(sample_ids)
+    live = ids[:, :, None] != -1 if mutant == "padding_is_minus_one_only" else ids[:, :, None] >= 0
+    same = (ids[:, :, None] == ids[:, None, :]) & live
+    if mutant == "ignore_class_bits":
+        return same
+    if mutant == "swap_mask_and_class":          # the key's mask against the query's class
+        return same & ((qmask[:, None, :] & kcls[:, :, None]) != 0)
+    if mutant == "class4_visible":               # a class outside the known text / image bits reads as "every class" on the key side
+        kcls = torch.where((kcls & 3) == 0, 0xFF, kcls)
+    return same & ((qmask[:, :, None] & kcls[:, None, :]) != 0)
+
+
+def visible(B, Lq, Lk, sample_ids=None, causal=False, mutant=None):
+    """bool [B, 1, Lq, Lk] (True = query i sees key j), or None when every pair is visible.  `sample_ids` are mask codes, judged as attn_pair_ok does (pair_ok;
+    padding is id < 0); `mutant` is for the tests that show a wrong predicate is noticed.  Causal: j <= i + (Lk - Lq) (the queries are the LAST Lq positions)."""
     ok = None
     if sample_ids is not None:
-        sid = torch.as_tensor(sample_ids)
-        ok = ((sid[:, :, None] == sid[:, None, :]) & (sid[:, :, None] != -1))[:, None]
+        ok = pair_ok(sample_ids, mutant)[:, None]
     if causal:
         tri = (torch.arange(Lk)[None, :] <= torch.arange(Lq)[:, None] + (Lk - Lq))[None, None]
         ok = tri.expand(B, 1, Lq, Lk) if ok is None else ok & tri
@@ -150,11 +176,11 @@ def _scores32(q, k, c2, ok):
     return s if ok is None else s.masked_fill(~ok, float("-inf"))
 
 
-def emulate_fwd_oneshot(q, k, v, *, prescaled, sample_ids=None, causal=False, keep=None, p=0.0):
+def emulate_fwd_oneshot(q, k, v, *, prescaled, sample_ids=None, causal=False, keep=None, p=0.0, mutant=None):
     """FA2 rounding points in one shot: fp32 scores and lse, P -> bf16, fp32 accumulate, O -> bf16.  Returns (O bf16-valued fp32, lse2 fp32)."""
     B, H, L, D = q.shape
     c2, _ = score_scales(D, prescaled)
-    s = _scores32(q, k, c2, visible(B, L, k.shape[2], sample_ids, causal))
+    s = _scores32(q, k, c2, visible(B, L, k.shape[2], sample_ids, causal, mutant))
     m = s.max(-1, keepdim=True).values
     dead = torch.isinf(m)
     l = torch.exp2(s - torch.where(dead, torch.zeros_like(m), m)).sum(-1, keepdim=True)
@@ -167,13 +193,13 @@ def emulate_fwd_oneshot(q, k, v, *, prescaled, sample_ids=None, causal=False, ke
     return _bf((_bf(P) @ v.float()) * ks), lse.squeeze(-1)
 
 
-def emulate_fwd_tiled(q, k, v, *, prescaled, sample_ids=None, causal=False, keep=None, p=0.0, tile=64, lazy=8.0):
+def emulate_fwd_tiled(q, k, v, *, prescaled, sample_ids=None, causal=False, keep=None, p=0.0, tile=64, lazy=8.0, mutant=None):
     """Online softmax over 64-key tiles with the kernels' lazy reference exponent: a row's exponent m moves (and its l, acc are rescaled) only when a score of
     the tile exceeds it by more than 2^8; p = 2^(s - m) may exceed 1 by 2^8.  P -> bf16 per tile, fp32 accumulate, O = bf16(acc / l)."""
     B, H, L, D = q.shape
     Lk = k.shape[2]
     c2, _ = score_scales(D, prescaled)
-    s_all = _scores32(q, k, c2, visible(B, L, Lk, sample_ids, causal))
+    s_all = _scores32(q, k, c2, visible(B, L, Lk, sample_ids, causal, mutant))
     vf = v.float()
     m = torch.full((B, H, L, 1), float("-inf"))
     l = torch.zeros(B, H, L, 1)
@@ -197,12 +223,12 @@ def emulate_fwd_tiled(q, k, v, *, prescaled, sample_ids=None, causal=False, keep
     return _bf(acc * inv), lse.squeeze(-1)
 
 
-def emulate_bwd(q, k, v, o, do, lse, *, prescaled, sample_ids=None, causal=False, keep=None, p=0.0):
+def emulate_bwd(q, k, v, o, do, lse, *, prescaled, sample_ids=None, causal=False, keep=None, p=0.0, mutant=None):
     """The backward every flash attention runs, from the forward's bf16 O and fp32 lse2: P = 2^(s - lse) and dS rounded to bf16 in front of their matrix products,
     delta from the rounded O, fp32 accumulate, bf16 outputs.  Returns dq, dk, dv (bf16-valued fp32)."""
     B, H, L, D = q.shape
     c2, cb = score_scales(D, prescaled)
-    s = _scores32(q, k, c2, visible(B, L, k.shape[2], sample_ids, causal))
+    s = _scores32(q, k, c2, visible(B, L, k.shape[2], sample_ids, causal, mutant))
     lse = lse.unsqueeze(-1)
     dead = torch.isinf(lse)
     P = torch.where(dead, torch.zeros_like(s), torch.exp2(s - torch.where(dead, torch.zeros_like(lse), lse)))
@@ -314,3 +340,41 @@ def doc_layouts(B, L):
     pad[0] = -1
     pad[B - 1, L // 2:L // 2 + 70] = -1
     return dict(contiguous=sid, padding=pad)
+
+
+# ------------------------------------------------------------------------------------------------ mask codes (class bits above the sample id)
+def key_mask_codes(base, key_mask):
+    """The engine's key-padding arithmetic (DIT._attention_masks, restated; tests/test_attention_mask_codes_ref64.py holds it to the product): on top of `base`
+    codes (or zeros) a masked key gets key class 4, which no query mask contains; a key without a class becomes class 1, a query without a mask sees classes 1 | 2;
+    the id field keeps its 32 bits (an id of -1 stays padding)."""
+    base, km = torch.as_tensor(base).to(torch.int64), torch.as_tensor(key_mask).bool()
+    kbits, qbits = (base >> 32) & 0xFF, (base >> 40) & 0xFF
+    kbits = torch.where(km, torch.where(kbits == 0, 1, kbits), 4)
+    qbits = torch.where(qbits == 0, 3, qbits)
+    return ((base & 0xFFFFFFFF) | (kbits << 32) | (qbits << 40)).contiguous()
+
+
+def key_mask_rows(L):
+    """bool [4, L] (True = the key is attended): a few keys inside a tile; the whole first key tile; a stretch across two tile seams; every key"""
+    assert L >= 200
+    km = torch.ones(4, L, dtype=torch.bool)
+    km[0, 5:9] = False
+    km[1, 0:64] = False
+    km[2, 130:200] = False
+    km[3, :] = False
+    return km
+
+
+def code_layouts(B, L, Lt):
+    """named [B, L] int64 mask-code layouts (B = 4): `modality` - the four (txt_drop, img_drop) combinations of the product's modality_mask_codes, text below Lt;
+    `keypad` - sample 0 under key_mask_rows; `modality_keypad` - that key mask on the modality codes; `docs_keypad` - on the packed ids of
+    doc_layouts(B, L)["contiguous"] (three cuts, one sample with trailing -1 padding); `docs_keypad_neg` - the same with the padding's id -2, which only the
+    sign test of the predicate (id >= 0) reads as padding"""
+    from unidisc_amd.kernels import modality_mask_codes
+
+    assert B == 4
+    modality = modality_mask_codes(torch.tensor([False, True, False, True]), torch.tensor([False, False, True, True]), Lt, L)
+    km = key_mask_rows(L)
+    docs = doc_layouts(B, L)["contiguous"]
+    return dict(modality=modality, keypad=key_mask_codes(torch.zeros(B, L, dtype=torch.int64), km), modality_keypad=key_mask_codes(modality, km),
+                docs_keypad=key_mask_codes(docs, km), docs_keypad_neg=key_mask_codes(torch.where(docs < 0, -2, docs), km))

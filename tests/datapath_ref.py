@@ -1,7 +1,7 @@
 """Serial and fp64 statements of the kernels that build a training batch before the first GEMM and turn log-probabilities into the loss after the last one -
 udm_assemble_joint_tokens, udm_sample_t_noise, udm_qxt_absorbing, udm_interleaved_rope, udm_interleaved_block_lottery (csrc/tokens.hip),
 udm_attention_doc_ranges (csrc/attention.hip), udm_diffusion_loss (csrc/ce.hip) - with their input families, bounds, judges and mutants (CPU only; nothing of
-the product is imported here).
+the product is imported here, but for the mask-code inputs of doc_code_cases, which take the modality codes from kernels.modality_mask_codes, plain torch).
 
 The reference of tests/test_gpu_datapath_exact.py (GPU) and the subject of tests/test_datapath_ref.py (CPU); the split follows smallops_ref64.py.
 
@@ -52,7 +52,7 @@ LOSS_SHAPES = ((1, 1), (1, 1023), (1, 1024), (5, 205), (6, 200), (8, 4608))
 LOSS_CASES = ("weighted", "weighted_cap", "weighted_no_image", "mean", "mean_full_mask", "mean_no_modality", "all_padding", "cap_active", "cap_inactive", "cap_zero",
               "neither_modality")
 MUTANTS = ("runs_split_at_id", "cand_ge4", "k_not_k1", "n_over_row", "rank_per_row", "j_over_row", "txt_from_row_start", "qxt_le", "qxt_both_masks_both",
-           "offset_i_plus_1", "doc_hi_off_by_one", "doc_exact_ignores_foreign", "mean_counts_unattended", "cap_on_image", "coef_without_fraction")
+           "offset_i_plus_1", "doc_hi_off_by_one", "doc_exact_ignores_foreign", "doc_span_on_whole_code", "doc_class_bits_are_not_padding", "mean_counts_unattended", "cap_on_image", "coef_without_fraction")
 
 
 def _rng(seed):
@@ -180,26 +180,38 @@ def qxt_cases():
 
 
 # ------------------------------------------------------------------------------------------------ document ranges
+def code_id(code):
+    """the id field of a mask code: its low 32 bits, sign-extended"""
+    return ((int(code) & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000
+
+
 def doc_ranges_ref(sid, mutant=None):
-    """int32 [B, ceil(L / 64), 8]: per 64-row tile {lo, hi, idmin, idmax, exact, 0, 0, 0}.  [idmin', idmax'] = the interval of the tile's ids >= 0; [lo, hi) spans
-    the row's positions whose id lies inside it; idmin = -1 when the tile holds padding; ids >= 2^30 are never reported (idmin = -1, idmax = -2); exact = one
-    document, no padding, and every position of [lo, hi) holds it.  A tile without any id >= 0: {0, 0, -1, -2, 0}.  Rows past L are not padding."""
+    """int32 [B, ceil(L / 64), 8]: per 64-row tile {lo, hi, idmin, idmax, exact, 0, 0, 0}.  `sid` holds mask codes (csrc/attention_common.h); the id of a position
+    is the sign-extended low 32 bits of its code, id < 0 is padding.  [idmin', idmax'] = the interval of the tile's ids >= 0; [lo, hi) spans the row's positions
+    whose ID lies inside it; idmin = -1 when the tile holds padding OR any position with a bit above bit 31 set (class bits); ids >= 2^30 are never reported
+    (idmin = -1, idmax = -2); exact = one document, no padding, no class bits, and every position of [lo, hi) holds it without class bits.  A tile without any
+    id >= 0: {0, 0, -1, -2, 0}.  Rows past L are not padding.  For raw ids in [-2^31, 2^31) this is the definition on the whole value."""
     B, L = sid.shape
     nT = (L + 63) // 64
     out = np.zeros((B, nT, 8), np.int32)
+    whole = mutant == "doc_span_on_whole_code"
+    ident = (lambda c: c) if whole else code_id
     for b in range(B):
+        row = [int(v) for v in sid[b]]
         for t in range(nT):
-            tile = [int(v) for v in sid[b, t * 64:min(t * 64 + 64, L)]]
-            ids = [v for v in tile if v >= 0]
+            tile = row[t * 64:min(t * 64 + 64, L)]
+            ids = [ident(c) for c in tile if ident(c) >= 0]
             if not ids:
                 out[b, t, :5] = 0, 0, -1, -2, 0
                 continue
-            mn, mx, pad = min(ids), max(ids), len(ids) < len(tile)
-            hits = [j for j in range(L) if mn <= int(sid[b, j]) <= mx]
+            high = any(c >> 32 != 0 for c in tile) and not whole and mutant != "doc_class_bits_are_not_padding"
+            mn, mx, pad = min(ids), max(ids), len(ids) < len(tile) or high
+            hits = [j for j in range(L) if mn <= ident(row[j]) <= mx]
             lo, hi = hits[0], hits[-1] + 1
             small = mx < 2 ** 30
             idmin, idmax = (mn if small and not pad else -1), (mx if small else -2)
-            full = len(hits) == hi - lo or mutant == "doc_exact_ignores_foreign"
+            clean = len(hits) if whole else sum(1 for j in hits if row[j] >> 32 == 0)
+            full = clean == hi - lo or mutant == "doc_exact_ignores_foreign"
             out[b, t, :5] = lo, hi + (1 if mutant == "doc_hi_off_by_one" else 0), idmin, idmax, int(idmin >= 0 and idmin == idmax and full)
     return out
 
@@ -222,6 +234,31 @@ def doc_cases():
             sid[2, :64], sid[2, 64:128], sid[2, 128:] = 0, -1, 0                                # an all-padding tile between two of one document
             sid[2, 10] = -1                                                                     # padding inside a tile
         out.append(dict(name=f"B{B}-L{L}", sid=sid))
+    return out + doc_code_cases()
+
+
+DOC_RAW_CASES = len(DOC_SHAPES)      # doc_cases()[:DOC_RAW_CASES] hold raw ids only
+
+
+def doc_code_cases():
+    """mask codes (class bits above the id field): the layouts of attention_ref64.code_layouts at L = 320 - the modality codes come from the product's
+    modality_mask_codes, plain torch - and one row set whose codes have an id field of -1 (0xFFFFFFFF) under positive class bits, padding under a key mask"""
+    import attention_ref64 as R
+
+    B, L = 4, 320
+    out = []
+    for Lt in (72, 128):
+        for name, codes in R.code_layouts(B, L, Lt).items():
+            if Lt == 72 or name.startswith("modality"):
+                out.append(dict(name=f"codes-{name}-Lt{Lt}", sid=codes.numpy().copy()))
+    cls = (1 << 32) | (3 << 40)
+    sid = np.zeros((3, 200), np.int64)
+    sid[0, :] = cls                                   # sample 0 with class bits everywhere ...
+    sid[0, 70:140] = 0xFFFFFFFF | (4 << 32) | (3 << 40)   # ... and padding under a masked key, across the seam of tiles 1 and 2
+    sid[1, :64], sid[1, 64:128], sid[1, 128:] = 0xFFFFFFFF | cls, 1, 1 | cls      # a tile of coded padding only, a raw tile, the same document with class bits
+    sid[2, :100], sid[2, 100:] = 0, 1                 # raw documents ...
+    sid[2, 192:] = 0xFFFFFFFF | cls                   # ... and coded padding in the ragged last tile
+    out.append(dict(name="codes-padding-under-class-bits", sid=sid))
     return out
 
 

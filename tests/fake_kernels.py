@@ -285,20 +285,25 @@ def modality_mask_codes(txt_drop, img_drop, txt_length, L):
 
 
 def attention_doc_ranges(sample_ids):
+    """on the id field of the mask codes (the sign-extended low 32 bits); a position with any bit above bit 31 counts like padding for its tile's idmin"""
     B, L = sample_ids.shape
     nT = (L + 63) // 64
     r = torch.zeros(B, nT, 8, dtype=torch.int32)
+    idf = ((sample_ids & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000
+    plain = (sample_ids >> 32) == 0
     for b in range(B):
         for t in range(nT):
-            tile = sample_ids[b, t * 64:(t + 1) * 64]
+            tile = idf[b, t * 64:(t + 1) * 64]
             ids = tile[tile >= 0]
             r[b, t, 2], r[b, t, 3] = -1, -2
             if ids.numel():
-                hit = ((sample_ids[b] >= ids.min()) & (sample_ids[b] <= ids.max())).nonzero().flatten()
+                inside = (idf[b] >= ids.min()) & (idf[b] <= ids.max())
+                hit = inside.nonzero().flatten()
                 r[b, t, 0], r[b, t, 1] = int(hit[0]), int(hit[-1]) + 1
                 small = int(ids.max()) < 1 << 30          # ids that do not fit an int32 interval are never reported (the kernel: "never uniform")
-                r[b, t, 2], r[b, t, 3] = (int(ids.min()) if small and ids.numel() == tile.numel() else -1), (int(ids.max()) if small else -2)
-                r[b, t, 4] = int(r[b, t, 2] >= 0 and r[b, t, 2] == r[b, t, 3] and hit.numel() == int(hit[-1]) + 1 - int(hit[0]))
+                whole = ids.numel() == tile.numel() and bool(plain[b, t * 64:(t + 1) * 64].all())
+                r[b, t, 2], r[b, t, 3] = (int(ids.min()) if small and whole else -1), (int(ids.max()) if small else -2)
+                r[b, t, 4] = int(r[b, t, 2] >= 0 and r[b, t, 2] == r[b, t, 3] and int((inside & plain[b]).sum()) == int(hit[-1]) + 1 - int(hit[0]))
     return r
 
 

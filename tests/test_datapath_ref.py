@@ -318,7 +318,7 @@ def _reject_loss(m):
 
 REJECT = dict(runs_split_at_id=_reject_rope, j_over_row=_reject_rope, txt_from_row_start=_reject_rope, cand_ge4=_reject_lottery, k_not_k1=_reject_lottery,
               n_over_row=_reject_lottery, rank_per_row=_reject_lottery, qxt_le=_reject_qxt, qxt_both_masks_both=_reject_qxt, offset_i_plus_1=_reject_t_noise,
-              doc_hi_off_by_one=_reject_doc, doc_exact_ignores_foreign=_reject_doc, mean_counts_unattended=_reject_loss, cap_on_image=_reject_loss,
+              doc_hi_off_by_one=_reject_doc, doc_exact_ignores_foreign=_reject_doc, doc_span_on_whole_code=_reject_doc, doc_class_bits_are_not_padding=_reject_doc, mean_counts_unattended=_reject_loss, cap_on_image=_reject_loss,
               coef_without_fraction=_reject_loss)
 
 
@@ -326,3 +326,72 @@ REJECT = dict(runs_split_at_id=_reject_rope, j_over_row=_reject_rope, txt_from_r
 def test_the_judges_reject_every_mutant(mutant):
     assert set(REJECT) == set(D.MUTANTS)
     assert REJECT[mutant](mutant), f"no family tells the mutant `{mutant}` from the statement"
+
+
+# ------------------------------------------------------------------------------------------------ document ranges under mask codes
+def _doc_ranges_legacy(sid):
+    """doc_ranges_ref as it stood before the ranges were defined on the id field: minimum, maximum and span of the WHOLE int64 value (frozen; not to be used)"""
+    B, L = sid.shape
+    nT = (L + 63) // 64
+    out = np.zeros((B, nT, 8), np.int32)
+    for b in range(B):
+        for t in range(nT):
+            tile = [int(v) for v in sid[b, t * 64:min(t * 64 + 64, L)]]
+            ids = [v for v in tile if v >= 0]
+            if not ids:
+                out[b, t, :5] = 0, 0, -1, -2, 0
+                continue
+            mn, mx, pad = min(ids), max(ids), len(ids) < len(tile)
+            hits = [j for j in range(L) if mn <= int(sid[b, j]) <= mx]
+            lo, hi = hits[0], hits[-1] + 1
+            small = mx < 2 ** 30
+            idmin, idmax = (mn if small and not pad else -1), (mx if small else -2)
+            full = len(hits) == hi - lo
+            out[b, t, :5] = lo, hi, idmin, idmax, int(idmin >= 0 and idmin == idmax and full)
+    return out
+
+
+def test_doc_ranges_of_raw_ids_are_what_they_were():
+    """raw ids in [-2^31, 2^31): the id-field definition gives the former output bit for bit on every case without class bits"""
+    raw = D.doc_cases()[:D.DOC_RAW_CASES]
+    assert len(raw) == len(D.DOC_SHAPES) and all(((c["sid"] >> 32 == 0) | (c["sid"] >> 31 == -1)).all() for c in raw)
+    for c in raw:
+        assert D.same(D.doc_ranges_ref(c["sid"]), _doc_ranges_legacy(c["sid"])) == 0, c["name"]
+
+
+def _doc_range_faults(sid, ranges):
+    """the three promises the attention kernels build on, against the brute-force predicate of attention_ref64.pair_ok: (a) a visible pair lies inside the spans
+    of both its tiles, (b) two tiles that report the same single id see each other completely (live rows), (c) exact = every position of [lo, hi) is that raw id"""
+    import attention_ref64 as R
+
+    B, L = sid.shape
+    ok = R.pair_ok(T(sid)).numpy()
+    lo, hi, idmin, idmax, exact = (np.repeat(ranges[..., i], 64, axis=1)[:, :L] for i in range(5))      # per position: its tile's entry
+    pos = np.arange(L)
+    faults = dict(a=0, b=0, c=0)
+    for b in range(B):
+        key_in_q_span = (pos[None, :] >= lo[b][:, None]) & (pos[None, :] < hi[b][:, None])               # [i, j]: j inside the span of i's tile
+        q_in_key_span = (pos[:, None] >= lo[b][None, :]) & (pos[:, None] < hi[b][None, :])               # [i, j]: i inside the span of j's tile
+        faults["a"] += int((ok[b] & ~(key_in_q_span & q_in_key_span)).sum())
+        uni = (idmin[b] == idmax[b]) & (idmin[b] >= 0)
+        faults["b"] += int((uni[:, None] & uni[None, :] & (idmin[b][:, None] == idmin[b][None, :]) & ~ok[b]).sum())
+        for t in range(ranges.shape[1]):
+            l, h, mn, mx, ex = (int(v) for v in ranges[b, t, :5])
+            if ex:
+                faults["c"] += int(not (mn == mx >= 0 and h > l and (sid[b, l:h] == mn).all()))
+    return faults
+
+
+def test_doc_ranges_are_conservative_for_mask_codes():
+    """brute force on every doc_cases() entry; and the former whole-value definition breaks (a) on the modality codes: the text tiles of the sample without any
+    drop got the span [0, Lt) although each of their queries sees every key"""
+    n_exact = n_uniform = 0
+    for c in D.doc_cases():
+        r = D.doc_ranges_ref(c["sid"])
+        assert _doc_range_faults(c["sid"], r) == dict(a=0, b=0, c=0), c["name"]
+        n_exact, n_uniform = n_exact + int(r[..., 4].sum()), n_uniform + int(((r[..., 2] == r[..., 3]) & (r[..., 2] >= 0)).sum())
+    assert n_exact > 3 and n_uniform > n_exact                      # (b) and (c) are not vacuous
+    mod = next(c for c in D.doc_cases() if c["name"] == "codes-modality-Lt128")
+    legacy = _doc_ranges_legacy(mod["sid"])
+    assert tuple(legacy[0, 0, :2]) == (0, 128) and _doc_range_faults(mod["sid"], legacy)["a"] > 0
+    assert tuple(D.doc_ranges_ref(mod["sid"])[0, 0, :3]) == (0, 320, -1)

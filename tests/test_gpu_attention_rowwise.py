@@ -95,8 +95,9 @@ def _attention_buffers(layout, B, H, L, D):
     return A, F, op
 
 
-def _run_attention(K, layout, q, k, v, do, *, prescaled, causal=False, sample_ids=None, p_drop=0.0):
-    """udm_attention_fwd / _bwd (or the _dropout entry points) on guarded views with explicit strides.  Returns (dict of CPU outputs [B, H, L, D], list of faults)."""
+def _run_attention(K, layout, q, k, v, do, *, prescaled, causal=False, sample_ids=None, p_drop=0.0, ranges="from_ids"):
+    """udm_attention_fwd / _bwd (or the _dropout entry points) on guarded views with explicit strides.  `ranges`: "from_ids" = udm_attention_doc_ranges of the
+    sample ids go with them, None = the ids alone (every tile walked, every pair tested).  Returns (dict of CPU outputs [B, H, L, D], list of faults)."""
     from unidisc_amd import _lib
     from unidisc_amd.kernels import _p, _s
 
@@ -104,10 +105,13 @@ def _run_attention(K, layout, q, k, v, do, *, prescaled, causal=False, sample_id
     A, F, op = _attention_buffers(layout, B, H, L, D)
     for n, t in (("q", q), ("k", k), ("v", v), ("do", do)):
         op[n].copy_(_flat(t).to(DEV))
-    sid = ranges = None
+    assert ranges in ("from_ids", None)
+    sid = None
     if sample_ids is not None:
         sid = sample_ids.to(DEV)
-        ranges = K.attention_doc_ranges(sid)
+        ranges = K.attention_doc_ranges(sid) if ranges == "from_ids" else None
+    else:
+        ranges = None
     flags = (K.ATTN_Q_PRESCALED if prescaled else 0) | (K.ATTN_CAUSAL if causal else 0)
     tail = (float(p_drop), SEED, _s()) if p_drop else (_s(),)
     sfx = "_dropout" if p_drop else ""

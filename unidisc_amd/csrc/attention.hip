@@ -34,11 +34,16 @@ __global__ __launch_bounds__(256) void attn_doc_ranges_kernel(const int64_t* __r
   const int nT = (L + 63) / 64;
   const int b = blockIdx.x / nT, t = blockIdx.x % nT, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t* row = sid + (long)b * L;
+  // Everything here works on the ID FIELD of a mask code (attention_common.h: the sign-extended low 32 bits; < 0 = padding).  A position with any bit above
+  // bit 31 set (class bits, or a negative raw id) marks its tile like padding does: idmin = -1, so the tile is never uniform, exact or pure and every pair
+  // with it takes the element test (attn_pair_ok), which is the only place the class bits are read.
   long mn = INT64_MAX, mx = -1;
   int pad = 0;   // rows past L do not count as padding: nothing is ever computed for them
   if (tid < 64 && t * 64 + tid < L) {
     const long v = row[t * 64 + tid];
-    if (v >= 0) { mn = v; mx = v; } else pad = 1;
+    const int id = (int)v;
+    if (id >= 0) { mn = id; mx = id; }
+    if (id < 0 || (v >> 32) != 0) pad = 1;
   }
   for (int off = 32; off; off >>= 1) {
     mn = min(mn, __shfl_xor(mn, off, 64));
@@ -53,7 +58,8 @@ __global__ __launch_bounds__(256) void attn_doc_ranges_kernel(const int64_t* __r
   if (mx >= 0)
     for (int j = tid; j < L; j += 256) {
       const long v = row[j];
-      if (v >= mn && v <= mx) { lo = min(lo, j); hi = max(hi, j + 1); ++cnt; }
+      const int id = (int)v;
+      if (id >= mn && id <= mx) { lo = min(lo, j); hi = max(hi, j + 1); cnt += (v >> 32) == 0; }   // (cnt: the span's positions WITHOUT class bits)
     }
   for (int off = 32; off; off >>= 1) {
     lo = min(lo, __shfl_xor(lo, off, 64));
@@ -71,7 +77,7 @@ __global__ __launch_bounds__(256) void attn_doc_ranges_kernel(const int64_t* __r
     r.x = lo; r.y = hi;
     r.z = (small && !s_pad) ? (int)mn : -1;
     r.w = small ? (int)mx : -2;
-    // exact: one document (no padding in the tile) whose rows are exactly the positions [lo, hi) - nothing of another id in between
+    // exact: one document (no padding in the tile) whose rows are exactly the positions [lo, hi) - nothing of another id in between, and no class bits on any of them
     const int cnt_all = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
     const int exact = (r.z >= 0 && r.z == r.w && cnt_all == hi - lo) ? 1 : 0;
     int* out = ranges + ((long)b * nT + t) * DOC_STRIDE;

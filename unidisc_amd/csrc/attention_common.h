@@ -141,6 +141,10 @@ constexpr int DOC_STRIDE = 8;   // ints per tile in doc_ranges: {lo, hi, idmin, 
 // any padding, so that idmin == idmax >= 0 means "every row of this tile belongs to the one document idmin".  The span is conservative for any id
 // layout and exact for contiguous documents.  A tile pair that is uniform on both sides with the same id needs no per-element id test; every other
 // pair keeps it, so neither skipping tiles nor skipping the test changes a result.
+// "id" is the ID FIELD of a mask code (above: attn_pair_ok), the sign-extended low 32 bits, so the ranges are valid for codes with class bits too: a visible pair
+// has equal ids >= 0, hence lies inside the spans of both its tiles.  A tile that holds any position with a bit above bit 31 set is reported like a tile with
+// padding (idmin = -1): it is never uniform, never exact, never pure, never goes to the wave-specialised dK/dV split and always takes the element test - the only
+// place the class bits are read.  exact also wants every position of [lo, hi) free of class bits.
 struct DocSpan {
   int t_begin, t_end;   // tiles of the other side to walk
   int blk_id;           // the one document all rows of this 128-row block belong to, or -1

@@ -819,7 +819,8 @@ def modality_mask_codes(txt_drop, img_drop, txt_length, L):
 def attention_doc_ranges(sample_ids):
     """int32 [B, ceil(L/64), 8] = {lo, hi, idmin, idmax, exact, 0, 0, 0} per 64-row tile: the span of positions that can share a sample id with it
     (tile skipping for packed samples), the tile's id interval (idmin = -1 if it holds padding; idmin == idmax: one document, no per-element id
-    test needed) and whether that document's rows are exactly [lo, hi) (then its key blocks take the wave-specialised dK/dV kernel)."""
+    test needed) and whether that document's rows are exactly [lo, hi) (then its key blocks take the wave-specialised dK/dV kernel).  Computed on the id field
+    of mask codes (the sign-extended low 32 bits), so valid under class bits too: a tile that holds any is reported like one with padding (idmin = -1)."""
     B, L = sample_ids.shape
     r = torch.empty((B, (L + 63) // 64, 8), dtype=torch.int32, device=sample_ids.device)
     _lib.call("udm_attention_doc_ranges", _p(sample_ids), B, L, _p(r), _s())
