@@ -450,6 +450,28 @@ int udm_ar_sample_rows(const void* logits, const void* logits_uncond, const floa
                        int64_t ldg, int64_t g_col0, uint64_t seed, int64_t step, int64_t* x, int64_t ldx, const int64_t* x0, const void* x0_unmask, int64_t pos,
                        int64_t* next_ids, int64_t R, int64_t V, int64_t Vt, int64_t mask_id, int restrict_modality, hipStream_t stream);
 
+/* ---- The decode step on a device-side position: the forms a captured graph can replay unchanged, token after token.  pos_dev points to one int64 in
+ * device memory, read by every workgroup when it runs; no launch of the step but the last (udm_counter_add) writes it.
+ * udm_attention_decode_at: udm_attention_decode with p = *pos_dev.  The grid is fixed at (B H, S_bound) with S_bound the largest number of splits any
+ *   position below Lmax takes (csrc/decode_plan.h: S is not monotone in the position, so this is not the S of Lmax) and the combine launch is always
+ *   made; each workgroup derives the split of udm_attention_decode(p) itself and leaves at once when it has no part in it.  Same arithmetic in the same
+ *   order: o, cache slot p and every partial that is read are bit-identical to udm_attention_decode(p).  *pos_dev outside [0, Lmax): nothing is stored.
+ * udm_ar_sample_rows_at / udm_ar_nucleus_rows_at: udm_ar_sample_rows / udm_ar_nucleus_rows with pos = i + 1, step = i and g_col0 (u_col0) = i V for
+ *   i = *pos_dev, bit-identical outputs.  i < 0, i + 1 >= ldx, a modality column i + 1 >= ldm or noise columns past ldg (ldu): nothing is stored.
+ * udm_decode_stage: row *pos_dev of mod_cols (int64 [L, Bp], nullable) into mod_row [Bp], and of cos / sin (fp32 [L, rope_row], nullable together; rope_row
+ *   = D/2, or Bp D/2 for per-sample tables) into cos_row / sin_row [rope_row] - the operands udm_embedding_fwd and udm_qknorm_rope_fwd then read from
+ *   fixed addresses.  *pos_dev outside [0, L): nothing is copied.
+ * udm_counter_add: *c += delta from one thread, the last launch of a step. */
+int udm_attention_decode_at(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, void* o, float* ws, int64_t ws_elems, int64_t B,
+                            int64_t H, int64_t D, int64_t Lmax, const int64_t* pos_dev, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                            int64_t o_stride, hipStream_t stream);
+int udm_ar_sample_rows_at(const void* logits, const void* logits_uncond, const float* w, int64_t ld, const int64_t* modality, int64_t ldm, const float* g,
+                          int64_t ldg, uint64_t seed, int64_t* x, int64_t ldx, const int64_t* x0, const void* x0_unmask, const int64_t* pos_dev,
+                          int64_t* next_ids, int64_t R, int64_t V, int64_t Vt, int64_t mask_id, int restrict_modality, hipStream_t stream);
+int udm_decode_stage(const int64_t* pos_dev, const int64_t* mod_cols, int64_t* mod_row, int64_t Bp, const float* cos_t, const float* sin_t, float* cos_row,
+                     float* sin_row, int64_t rope_row, int64_t L, hipStream_t stream);
+int udm_counter_add(int64_t* c, int64_t delta, hipStream_t stream);
+
 /* ---- Top-p (nucleus) sampling without a sort: `nucleus_sampling_batch` model_eval.py:2642-2685 (the maskgit_nucleus predictor) and `nucleus_sampling`
  * :2691-2734 (the AR sampler's eval.top_p), one workgroup per row, the row read once into registers (V <= 65536, larger V is an argument error).
  *   valid ids, z and the guidance mix as in udm_categorical_sample_rows; p = softmax(inv_temperature z) over the valid ids; the valid ids ordered by
@@ -469,6 +491,11 @@ int udm_ar_nucleus_rows(const void* logits, const void* logits_uncond, const flo
                         int64_t ldu, int64_t u_col0, uint64_t seed, int64_t step, float inv_temperature, float budget, int64_t* x, int64_t ldx,
                         const int64_t* x0, const void* x0_unmask, int64_t pos, int64_t* next_ids, int64_t R, int64_t V, int64_t Vt, int64_t mask_id,
                         int restrict_modality, hipStream_t stream);
+/* the device-position form (see udm_ar_sample_rows_at) */
+int udm_ar_nucleus_rows_at(const void* logits, const void* logits_uncond, const float* w, int64_t ld, const int64_t* modality, int64_t ldm, const float* u,
+                           int64_t ldu, uint64_t seed, float inv_temperature, float budget, int64_t* x, int64_t ldx, const int64_t* x0,
+                           const void* x0_unmask, const int64_t* pos_dev, int64_t* next_ids, int64_t R, int64_t V, int64_t Vt, int64_t mask_id,
+                           int restrict_modality, hipStream_t stream);
 
 /* ---- The second half of a maskgit / maskgit_nucleus / first_hitting sampler step in one launch (`_maskgit_update` model_eval.py:3046-3114,
  * `_first_hitting_update` :3005-3043, the padding behind EOS :2390-2394 and the conditioning write-back :2399), one workgroup per sample, L <= 8192 (a longer

@@ -90,8 +90,13 @@ PROTOTYPES = {
     "udm_gemm_skinny_bf16": [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _P, _P, _I64, _P],
     "udm_attention_decode": [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P],
     "udm_ar_sample_rows": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _U64, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I, _P],
+    "udm_attention_decode_at": [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P],
+    "udm_ar_sample_rows_at": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _U64, _P, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P],
+    "udm_decode_stage": [_P, _P, _P, _I64, _P, _P, _P, _P, _I64, _I64, _P],
+    "udm_counter_add": [_P, _I64, _P],
     "udm_nucleus_sample_rows": [_P, _P, _P, _I64, _P, _P, _I64, _U64, _F, _F, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P],
     "udm_ar_nucleus_rows": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _U64, _I64, _F, _F, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I, _P],
+    "udm_ar_nucleus_rows_at": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _U64, _F, _F, _P, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P],
     "udm_reveal_rows": [_P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _I64, _U64, _F, _I, _I64, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _P],
 }
 EXTRA_SYMBOLS = ["udm_last_error", "udm_abi_version"]

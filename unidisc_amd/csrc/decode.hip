@@ -13,7 +13,17 @@
 //   udm_ar_sample_rows     the token choice: argmax(z + Gumbel) over one row per block, z = logits or (1 + w) l_c - w l_u in fp32 with [MASK] and (by next
 //                          modality) the other modality's ids excluded, and the chosen id written straight into x[b, pos] (x0 write-back applied) and into
 //                          the next step's input ids - the token loop never reads the device.
+//
+// The device-position forms (a captured graph replays one step for every token; its launches cannot take the position as an argument):
+//   udm_attention_decode_at   the same kernel bodies (template parameter AT) on a fixed grid (B H, S bound): each workgroup reads p from device memory,
+//                          derives S and chunk with decode_plan.h - the rule the host form evaluates - and leaves if it has no split; the combine launch
+//                          is always made and leaves when S = 1.  Same arithmetic, same order: bit-identical to udm_attention_decode(p).
+//   udm_ar_sample_rows_at     pos = i + 1, step = i, g_col0 = i V from i = *pos_dev, read in the kernel
+//   udm_decode_stage          row p of the modality columns and of the rotary tables into fixed one-row buffers (the embedding and qk-norm + rope kernels
+//                          then run unchanged on those); udm_counter_add: position + 1, the last launch of the step
+// A position outside its range makes every workgroup return before its first access.  All of these are plain loads and stores.
 #include "common.h"
+#include "decode_plan.h"
 #include "../../include/unidisc_hip.h"
 
 namespace {
@@ -130,11 +140,25 @@ struct DecArgs {
   float* ws;
   long q_stride, k_stride, v_stride, o_stride;
   int H, Lmax, p, S, chunk;
+  const int64_t* pos_dev;   // the device-position form (AT): p, S and chunk are derived in the kernel from *pos_dev, cap = the splits ws holds
+  int cap;
 };
+
+// the device-position form: every workgroup reads the position and plans the split itself (decode_plan.h); false: nothing to do (a position outside
+// [0, Lmax), which stores nothing)
+__device__ __forceinline__ bool dec_plan_at(DecArgs& a) {
+  const long p = *a.pos_dev;
+  if (p < 0 || p >= a.Lmax) return false;
+  const DecodePlan pl = decode_plan(p + 1, (long)gridDim.x, (long)a.cap);
+  a.p = (int)p;
+  a.S = (int)pl.S;
+  a.chunk = (int)pl.chunk;
+  return true;
+}
 
 constexpr int DEC_U = 4;   // keys per lane group in flight
 
-template <int D>
+template <int D, bool AT>
 __global__ __launch_bounds__(256) void attn_decode_kernel(DecArgs a) {
   constexpr int G = D / 8;          // lanes per key (16 B each)
   constexpr int KPW = 64 / G;       // keys per wave per load round
@@ -145,6 +169,9 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(DecArgs a) {
   const int g = lane / G, c = lane % G;
   const int grp = wave * KPW + g;
   const int bh = blockIdx.x, s = blockIdx.y;
+  if (AT) {   // the grid is (B H, S bound): the splits past this position's S leave at once (block-uniform, before any barrier)
+    if (!dec_plan_at(a) || s >= a.S) return;
+  }
   const int b = bh / a.H, h = bh % a.H;
   const long d = (long)a.H * D;
   const int lo = s * a.chunk, hi = min(a.p + 1, lo + a.chunk);
@@ -238,10 +265,13 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(DecArgs a) {
   }
 }
 
-template <int D>
+template <int D, bool AT>
 __global__ __launch_bounds__(D > 128 ? D : 128) void attn_decode_combine_kernel(DecArgs a) {
   const int bh = blockIdx.x, t = threadIdx.x;
   if (t >= D) return;
+  if (AT) {   // launched always: with one split the first launch has written o itself
+    if (!dec_plan_at(a) || a.S == 1) return;
+  }
   const int b = bh / a.H, h = bh % a.H;
   const float* w = a.ws + (long)bh * a.S * (D + 2);
   float M = -INFINITY;
@@ -269,6 +299,7 @@ struct ArArgs {
   long ld, ldg, g_col0, ldx, ldm, pos, step, V, Vt, mask_id;
   uint64_t seed;
   int R, restrict_modality;
+  const int64_t* pos_dev;   // the device-position form (AT): pos = i + 1, step = i, g_col0 = i V with i = *pos_dev
 };
 
 __device__ __forceinline__ bool ar_better(float v, long i, float bv, long bi) { return v > bv || (v == bv && i < bi); }
@@ -281,9 +312,15 @@ __device__ __forceinline__ float gumbel_of(uint32_t r) {
   return -__logf(e);
 }
 
+template <bool AT>
 __global__ __launch_bounds__(512) void ar_sample_rows_kernel(ArArgs a) {
   __shared__ float sv[8];
   __shared__ long si[8];
+  if (AT) {   // (block-uniform, before any barrier) a position whose column, modality column or noise columns do not exist: nothing is stored
+    const long i = *a.pos_dev;
+    if (i < 0 || i + 1 >= a.ldx || (a.restrict_modality && i + 1 >= a.ldm) || (a.g && (i + 1) * a.V > a.ldg)) return;
+    a.pos = i + 1, a.step = i, a.g_col0 = i * a.V;
+  }
   const int b = blockIdx.x;
   const int t = threadIdx.x;
   const bf16_t* lr = a.logits + (long)b * a.ld;
@@ -386,46 +423,78 @@ extern "C" int udm_gemm_skinny_bf16(const void* A, const void* W, void* C, int64
   return 0;
 }
 
+namespace {
+
+// the shape checks both forms of the decode attention share (`p` apart); `name` prefixes the message
+int dec_check(const char* name, const void* q, const void* k_new, const void* v_new, const void* k_cache, const void* v_cache, const void* o, const float* ws,
+              int64_t B, int64_t H, int64_t D, int64_t Lmax, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride) {
+  UDM_CHECK_ARG(q && k_new && v_new && k_cache && v_cache && o, "%s: null pointer", name);
+  UDM_CHECK_ARG(D == 32 || D == 64 || D == 128 || D == 256, "%s: head dim %ld (32 / 64 / 128 / 256)", name, (long)D);
+  UDM_CHECK_ARG(B >= 1 && H >= 1 && Lmax >= 1 && Lmax < (1L << 30) && B * H < (1L << 30), "%s: bad shape B=%ld H=%ld Lmax=%ld", name, (long)B, (long)H, (long)Lmax);
+  UDM_CHECK_ARG(q_stride % 8 == 0 && k_stride % 8 == 0 && v_stride % 8 == 0 && o_stride % 8 == 0 && q_stride >= H * D && k_stride >= H * D &&
+                    v_stride >= H * D && o_stride >= H * D, "%s: bad row strides", name);
+  UDM_CHECK_ARG(al16(q) && al16(k_new) && al16(v_new) && al16(k_cache) && al16(v_cache) && al16(o) && (!ws || al16(ws)), "%s: operands must be 16-byte aligned", name);
+  return 0;
+}
+
+template <bool AT>
+void dec_launch(int64_t D, dim3 grid, const DecArgs& a, hipStream_t stream) {
+  switch (D) {
+    case 32: hipLaunchKernelGGL((attn_decode_kernel<32, AT>), grid, dim3(256), 0, stream, a); break;
+    case 64: hipLaunchKernelGGL((attn_decode_kernel<64, AT>), grid, dim3(256), 0, stream, a); break;
+    case 256: hipLaunchKernelGGL((attn_decode_kernel<256, AT>), grid, dim3(256), 0, stream, a); break;
+    default: hipLaunchKernelGGL((attn_decode_kernel<128, AT>), grid, dim3(256), 0, stream, a); break;
+  }
+}
+
+template <bool AT>
+void dec_launch_combine(int64_t D, unsigned BH, const DecArgs& a, hipStream_t stream) {
+  switch (D) {
+    case 32: hipLaunchKernelGGL((attn_decode_combine_kernel<32, AT>), dim3(BH), dim3(128), 0, stream, a); break;
+    case 64: hipLaunchKernelGGL((attn_decode_combine_kernel<64, AT>), dim3(BH), dim3(128), 0, stream, a); break;
+    case 256: hipLaunchKernelGGL((attn_decode_combine_kernel<256, AT>), dim3(BH), dim3(256), 0, stream, a); break;   // one thread per output column
+    default: hipLaunchKernelGGL((attn_decode_combine_kernel<128, AT>), dim3(BH), dim3(128), 0, stream, a); break;
+  }
+}
+
+}  // namespace
+
 extern "C" int udm_attention_decode(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, void* o, float* ws, int64_t ws_elems,
                                     int64_t B, int64_t H, int64_t D, int64_t Lmax, int64_t p, int64_t q_stride, int64_t k_stride, int64_t v_stride,
                                     int64_t o_stride, hipStream_t stream) {
-  UDM_CHECK_ARG(q && k_new && v_new && k_cache && v_cache && o, "udm_attention_decode: null pointer");
-  UDM_CHECK_ARG(D == 32 || D == 64 || D == 128 || D == 256, "udm_attention_decode: head dim %ld (32 / 64 / 128 / 256)", (long)D);
-  UDM_CHECK_ARG(B >= 1 && H >= 1 && Lmax >= 1 && p >= 0 && p < Lmax && Lmax < (1L << 30) && B * H < (1L << 30), "udm_attention_decode: bad shape B=%ld H=%ld Lmax=%ld p=%ld",
-                (long)B, (long)H, (long)Lmax, (long)p);
-  UDM_CHECK_ARG(q_stride % 8 == 0 && k_stride % 8 == 0 && v_stride % 8 == 0 && o_stride % 8 == 0 && q_stride >= H * D && k_stride >= H * D &&
-                    v_stride >= H * D && o_stride >= H * D, "udm_attention_decode: bad row strides");
-  UDM_CHECK_ARG(al16(q) && al16(k_new) && al16(v_new) && al16(k_cache) && al16(v_cache) && al16(o) && (!ws || al16(ws)),
-                "udm_attention_decode: operands must be 16-byte aligned");
-  const long n = p + 1, BH = B * H;
-  // splits: about two workgroups per CU over B H, at least 64 keys each, at most 32, bounded by ws
-  long S = (512 + BH - 1) / BH;
-  S = S < 32 ? S : 32;
-  S = S < (n + 63) / 64 ? S : (n + 63) / 64;
+  if (int rc = dec_check("udm_attention_decode", q, k_new, v_new, k_cache, v_cache, o, ws, B, H, D, Lmax, q_stride, k_stride, v_stride, o_stride)) return rc;
+  UDM_CHECK_ARG(p >= 0 && p < Lmax, "udm_attention_decode: bad shape B=%ld H=%ld Lmax=%ld p=%ld", (long)B, (long)H, (long)Lmax, (long)p);
+  const long BH = B * H;
+  // splits: about two workgroups per CU over B H, at least 64 keys each, at most 32, bounded by ws (decode_plan.h)
   const long cap = ws ? ws_elems / (BH * (D + 2)) : 1;
-  if (S > cap) S = cap;
-  if (S < 1) S = 1;
-  long chunk = ((n + S - 1) / S + 63) / 64 * 64;
-  S = (n + chunk - 1) / chunk;
+  const DecodePlan pl = decode_plan(p + 1, BH, cap);
   DecArgs a{(const bf16_t*)q, (const bf16_t*)k_new, (const bf16_t*)v_new, (bf16_t*)k_cache, (bf16_t*)v_cache, (bf16_t*)o, ws, (long)q_stride, (long)k_stride,
-            (long)v_stride, (long)o_stride, (int)H, (int)Lmax, (int)p, (int)S, (int)chunk};
-  const dim3 grid((unsigned)BH, (unsigned)S);
-  switch (D) {
-    case 32: hipLaunchKernelGGL(attn_decode_kernel<32>, grid, dim3(256), 0, stream, a); break;
-    case 64: hipLaunchKernelGGL(attn_decode_kernel<64>, grid, dim3(256), 0, stream, a); break;
-    case 256: hipLaunchKernelGGL(attn_decode_kernel<256>, grid, dim3(256), 0, stream, a); break;
-    default: hipLaunchKernelGGL(attn_decode_kernel<128>, grid, dim3(256), 0, stream, a); break;
-  }
+            (long)v_stride, (long)o_stride, (int)H, (int)Lmax, (int)p, (int)pl.S, (int)pl.chunk, nullptr, 0};
+  dec_launch<false>(D, dim3((unsigned)BH, (unsigned)pl.S), a, stream);
   UDM_CHECK_LAUNCH("udm_attention_decode");
-  if (S > 1) {
-    switch (D) {
-      case 32: hipLaunchKernelGGL(attn_decode_combine_kernel<32>, dim3((unsigned)BH), dim3(128), 0, stream, a); break;
-      case 64: hipLaunchKernelGGL(attn_decode_combine_kernel<64>, dim3((unsigned)BH), dim3(128), 0, stream, a); break;
-      case 256: hipLaunchKernelGGL(attn_decode_combine_kernel<256>, dim3((unsigned)BH), dim3(256), 0, stream, a); break;   // one thread per output column
-      default: hipLaunchKernelGGL(attn_decode_combine_kernel<128>, dim3((unsigned)BH), dim3(128), 0, stream, a); break;
-    }
+  if (pl.S > 1) {
+    dec_launch_combine<false>(D, (unsigned)BH, a, stream);
     UDM_CHECK_LAUNCH("udm_attention_decode (combine)");
   }
+  return 0;
+}
+
+extern "C" int udm_attention_decode_at(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, void* o, float* ws, int64_t ws_elems,
+                                       int64_t B, int64_t H, int64_t D, int64_t Lmax, const int64_t* pos_dev, int64_t q_stride, int64_t k_stride,
+                                       int64_t v_stride, int64_t o_stride, hipStream_t stream) {
+  if (int rc = dec_check("udm_attention_decode_at", q, k_new, v_new, k_cache, v_cache, o, ws, B, H, D, Lmax, q_stride, k_stride, v_stride, o_stride)) return rc;
+  UDM_CHECK_ARG(pos_dev && ((uintptr_t)pos_dev & 7) == 0, "udm_attention_decode_at: the position must be an aligned device int64");
+  const long BH = B * H;
+  long cap = ws ? ws_elems / (BH * (D + 2)) : 1;
+  cap = cap < 1 ? 1 : (cap > 32 ? 32 : cap);
+  // the grid holds the S of every position below Lmax (S is not monotone in the position: decode_plan.h); both launches always, the kernels decide
+  const long Sb = decode_plan_s_bound(BH, Lmax, cap);
+  DecArgs a{(const bf16_t*)q, (const bf16_t*)k_new, (const bf16_t*)v_new, (bf16_t*)k_cache, (bf16_t*)v_cache, (bf16_t*)o, ws, (long)q_stride, (long)k_stride,
+            (long)v_stride, (long)o_stride, (int)H, (int)Lmax, 0, 1, 64, pos_dev, (int)cap};
+  dec_launch<true>(D, dim3((unsigned)BH, (unsigned)Sb), a, stream);
+  UDM_CHECK_LAUNCH("udm_attention_decode_at");
+  dec_launch_combine<true>(D, (unsigned)BH, a, stream);
+  UDM_CHECK_LAUNCH("udm_attention_decode_at (combine)");
   return 0;
 }
 
@@ -443,8 +512,82 @@ extern "C" int udm_ar_sample_rows(const void* logits, const void* logits_uncond,
                     (!x0 || al16(x0)) && (!x0_unmask || al16(x0_unmask)) && (!next_ids || al16(next_ids)),
                 "udm_ar_sample_rows: operands must be 16-byte aligned");
   ArArgs a{(const bf16_t*)logits, (const bf16_t*)logits_uncond, w, modality, g, x, x0, (const uint8_t*)x0_unmask, next_ids, (long)ld, (long)ldg, (long)g_col0,
-           (long)ldx, (long)ldm, (long)pos, (long)step, (long)V, (long)Vt, (long)mask_id, seed, (int)R, restrict_modality};
-  hipLaunchKernelGGL(ar_sample_rows_kernel, dim3((unsigned)R), dim3(512), 0, stream, a);
+           (long)ldx, (long)ldm, (long)pos, (long)step, (long)V, (long)Vt, (long)mask_id, seed, (int)R, restrict_modality, nullptr};
+  hipLaunchKernelGGL(ar_sample_rows_kernel<false>, dim3((unsigned)R), dim3(512), 0, stream, a);
   UDM_CHECK_LAUNCH("udm_ar_sample_rows");
+  return 0;
+}
+
+extern "C" int udm_ar_sample_rows_at(const void* logits, const void* logits_uncond, const float* w, int64_t ld, const int64_t* modality, int64_t ldm,
+                                     const float* g, int64_t ldg, uint64_t seed, int64_t* x, int64_t ldx, const int64_t* x0, const void* x0_unmask,
+                                     const int64_t* pos_dev, int64_t* next_ids, int64_t R, int64_t V, int64_t Vt, int64_t mask_id, int restrict_modality,
+                                     hipStream_t stream) {
+  UDM_CHECK_ARG(logits && x && pos_dev && ((uintptr_t)pos_dev & 7) == 0, "udm_ar_sample_rows_at: null pointer (the position must be an aligned device int64)");
+  UDM_CHECK_ARG(R >= 1 && V >= 1 && ld >= V && ld % 8 == 0 && ldx >= 1, "udm_ar_sample_rows_at: bad shape R=%ld V=%ld ld=%ld ldx=%ld", (long)R, (long)V, (long)ld,
+                (long)ldx);
+  UDM_CHECK_ARG(!logits_uncond || w, "udm_ar_sample_rows_at: guidance needs the weight");
+  UDM_CHECK_ARG(!restrict_modality || (modality && ldm >= 1 && Vt > 0 && Vt < V), "udm_ar_sample_rows_at: the restriction needs the modality map and 0 < Vt < V");
+  UDM_CHECK_ARG(!x0_unmask || x0, "udm_ar_sample_rows_at: x0_unmask needs x0");
+  UDM_CHECK_ARG(!g || ldg >= V, "udm_ar_sample_rows_at: bad noise layout");
+  UDM_CHECK_ARG(al16(logits) && (!logits_uncond || al16(logits_uncond)) && (!w || al16(w)) && (!modality || al16(modality)) && (!g || al16(g)) && al16(x) &&
+                    (!x0 || al16(x0)) && (!x0_unmask || al16(x0_unmask)) && (!next_ids || al16(next_ids)),
+                "udm_ar_sample_rows_at: operands must be 16-byte aligned");
+  ArArgs a{(const bf16_t*)logits, (const bf16_t*)logits_uncond, w, modality, g, x, x0, (const uint8_t*)x0_unmask, next_ids, (long)ld, (long)ldg, 0L,
+           (long)ldx, (long)ldm, 0L, 0L, (long)V, (long)Vt, (long)mask_id, seed, (int)R, restrict_modality, pos_dev};
+  hipLaunchKernelGGL(ar_sample_rows_kernel<true>, dim3((unsigned)R), dim3(512), 0, stream, a);
+  UDM_CHECK_LAUNCH("udm_ar_sample_rows_at");
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ position-dependent small operands of a captured step
+namespace {
+
+struct StageArgs {
+  const int64_t* pos_dev;
+  const int64_t* mod_cols;   // [L, Bp] (nullable)
+  int64_t* mod_row;          // [Bp]
+  const float* cos;          // [L, rope_row] (nullable)
+  const float* sin;
+  float* cos_row;            // [rope_row]
+  float* sin_row;
+  long L, Bp, rope_row;
+};
+
+__global__ __launch_bounds__(256) void decode_stage_kernel(StageArgs a) {
+  const long p = *a.pos_dev;
+  if (p < 0 || p >= a.L) return;
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (a.mod_cols && t < a.Bp) a.mod_row[t] = a.mod_cols[p * a.Bp + t];
+  if (a.cos && t < a.rope_row) {
+    a.cos_row[t] = a.cos[p * a.rope_row + t];
+    a.sin_row[t] = a.sin[p * a.rope_row + t];
+  }
+}
+
+__global__ void counter_add_kernel(int64_t* c, int64_t delta) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *c += delta;
+}
+
+}  // namespace
+
+extern "C" int udm_decode_stage(const int64_t* pos_dev, const int64_t* mod_cols, int64_t* mod_row, int64_t Bp, const float* cos, const float* sin, float* cos_row,
+                                float* sin_row, int64_t rope_row, int64_t L, hipStream_t stream) {
+  UDM_CHECK_ARG(pos_dev && ((uintptr_t)pos_dev & 7) == 0, "udm_decode_stage: the position must be an aligned device int64");
+  UDM_CHECK_ARG(L >= 1 && L < (1L << 30), "udm_decode_stage: bad table length L=%ld", (long)L);
+  UDM_CHECK_ARG(!mod_cols || (mod_row && Bp >= 1 && Bp < (1L << 20)), "udm_decode_stage: the modality column needs its [Bp] buffer");
+  UDM_CHECK_ARG((cos == nullptr) == (sin == nullptr) && (!cos || (cos_row && sin_row && rope_row >= 1 && rope_row < (1L << 24))),
+                "udm_decode_stage: the rotary rows need both tables and both one-row buffers");
+  const long n = (mod_cols ? Bp : 0) > (cos ? rope_row : 0) ? (long)Bp : (cos ? (long)rope_row : 0);
+  if (n == 0) return 0;
+  StageArgs a{pos_dev, mod_cols, mod_row, cos, sin, cos_row, sin_row, (long)L, (long)Bp, (long)rope_row};
+  hipLaunchKernelGGL(decode_stage_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  UDM_CHECK_LAUNCH("udm_decode_stage");
+  return 0;
+}
+
+extern "C" int udm_counter_add(int64_t* c, int64_t delta, hipStream_t stream) {
+  UDM_CHECK_ARG(c && ((uintptr_t)c & 7) == 0, "udm_counter_add: the counter must be an aligned device int64");
+  hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, stream, c, delta);
+  UDM_CHECK_LAUNCH("udm_counter_add");
   return 0;
 }

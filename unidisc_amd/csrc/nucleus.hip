@@ -43,6 +43,7 @@ struct NucArgs {
   uint64_t seed;
   float inv_temperature, budget;
   int R, V, Vt, mask_id, restrict_modality, w_scalar;
+  const int64_t* pos_dev;      // the device-position AR entry (AT): pos = mod_col = i + 1, step = i, u_col0 = i V with i = *pos_dev
 };
 
 struct Red {
@@ -98,11 +99,16 @@ __device__ __forceinline__ float mass_ge(const float (&e)[NG][8], int k, Red& r,
 
 __device__ __forceinline__ float mix(float c, float u, float gw) { return __fsub_rn(__fmul_rn(1.0f + gw, c), __fmul_rn(gw, u)); }
 
-template <int NG, bool GUIDED>
+template <int NG, bool GUIDED, bool AT>
 __global__ __launch_bounds__(NT) void nucleus_rows_kernel(NucArgs a) {
   __shared__ Red red;
   __shared__ float bs[NW];
   __shared__ int bi[NW];
+  if (AT) {   // (block-uniform, before any barrier) a position whose column, modality column or noise columns do not exist: nothing is stored
+    const long i = *a.pos_dev;
+    if (i < 0 || i + 1 >= a.ldx || (a.restrict_modality && i + 1 >= a.ldm) || (a.u && (i + 1) * (long)a.V > a.ldu)) return;
+    a.pos = a.mod_col = i + 1, a.step = i, a.u_col0 = i * (long)a.V;
+  }
   const long row = blockIdx.x;
   const int tid = threadIdx.x;
   int rd = 0;
@@ -307,14 +313,14 @@ __global__ __launch_bounds__(NT) void nucleus_rows_kernel(NucArgs a) {
   }
 }
 
-template <bool GUIDED>
+template <bool GUIDED, bool AT = false>
 void launch_ng(const NucArgs& a, unsigned rows, hipStream_t stream) {
   const int need = ((a.V + 7) / 8 + NT - 1) / NT;   // groups of 8 ids per thread
-  if (need <= 1) hipLaunchKernelGGL((nucleus_rows_kernel<1, GUIDED>), dim3(rows), dim3(NT), 0, stream, a);
-  else if (need <= 2) hipLaunchKernelGGL((nucleus_rows_kernel<2, GUIDED>), dim3(rows), dim3(NT), 0, stream, a);
-  else if (need <= 4) hipLaunchKernelGGL((nucleus_rows_kernel<4, GUIDED>), dim3(rows), dim3(NT), 0, stream, a);
-  else if (need <= 6) hipLaunchKernelGGL((nucleus_rows_kernel<6, GUIDED>), dim3(rows), dim3(NT), 0, stream, a);
-  else hipLaunchKernelGGL((nucleus_rows_kernel<8, GUIDED>), dim3(rows), dim3(NT), 0, stream, a);
+  if (need <= 1) hipLaunchKernelGGL((nucleus_rows_kernel<1, GUIDED, AT>), dim3(rows), dim3(NT), 0, stream, a);
+  else if (need <= 2) hipLaunchKernelGGL((nucleus_rows_kernel<2, GUIDED, AT>), dim3(rows), dim3(NT), 0, stream, a);
+  else if (need <= 4) hipLaunchKernelGGL((nucleus_rows_kernel<4, GUIDED, AT>), dim3(rows), dim3(NT), 0, stream, a);
+  else if (need <= 6) hipLaunchKernelGGL((nucleus_rows_kernel<6, GUIDED, AT>), dim3(rows), dim3(NT), 0, stream, a);
+  else hipLaunchKernelGGL((nucleus_rows_kernel<8, GUIDED, AT>), dim3(rows), dim3(NT), 0, stream, a);
 }
 
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -368,5 +374,30 @@ extern "C" int udm_ar_nucleus_rows(const void* logits, const void* logits_uncond
   a.R = (int)R; a.V = (int)V; a.Vt = (int)Vt; a.mask_id = (int)mask_id; a.restrict_modality = restrict_modality; a.w_scalar = 1;
   if (logits_uncond) launch_ng<true>(a, (unsigned)R, stream); else launch_ng<false>(a, (unsigned)R, stream);
   UDM_CHECK_LAUNCH("udm_ar_nucleus_rows");
+  return 0;
+}
+
+extern "C" int udm_ar_nucleus_rows_at(const void* logits, const void* logits_uncond, const float* w, int64_t ld, const int64_t* modality, int64_t ldm,
+                                      const float* u, int64_t ldu, uint64_t seed, float inv_temperature, float budget, int64_t* x, int64_t ldx,
+                                      const int64_t* x0, const void* x0_unmask, const int64_t* pos_dev, int64_t* next_ids, int64_t R, int64_t V, int64_t Vt,
+                                      int64_t mask_id, int restrict_modality, hipStream_t stream) {
+  UDM_CHECK_ARG(logits && x && pos_dev && ((uintptr_t)pos_dev & 7) == 0, "udm_ar_nucleus_rows_at: null pointer (the position must be an aligned device int64)");
+  UDM_CHECK_ARG(R >= 1 && R < (1L << 20) && V >= 1 && ld >= V && ld % 8 == 0 && ldx >= 1, "udm_ar_nucleus_rows_at: bad shape R=%ld V=%ld ld=%ld ldx=%ld", (long)R,
+                (long)V, (long)ld, (long)ldx);
+  UDM_CHECK_ARG(V <= V_MAX, "udm_ar_nucleus_rows_at: V=%ld > %ld (the row is held in registers)", (long)V, (long)V_MAX);
+  UDM_CHECK_ARG(inv_temperature > 0.f && budget > 0.f, "udm_ar_nucleus_rows_at: inv_temperature and budget must be positive");
+  UDM_CHECK_ARG(!logits_uncond || w, "udm_ar_nucleus_rows_at: guidance needs the weight");
+  UDM_CHECK_ARG(!restrict_modality || (modality && ldm >= 1 && Vt > 0 && Vt < V), "udm_ar_nucleus_rows_at: the restriction needs the modality map and 0 < Vt < V");
+  UDM_CHECK_ARG(!x0_unmask || x0, "udm_ar_nucleus_rows_at: x0_unmask needs x0");
+  UDM_CHECK_ARG(!u || ldu >= V, "udm_ar_nucleus_rows_at: bad noise layout");
+  UDM_CHECK_ARG(al16(logits) && al16(logits_uncond), "udm_ar_nucleus_rows_at: logits must be 16-byte aligned");
+  NucArgs a{};
+  a.logits = (const bf16_t*)logits; a.logits_u = (const bf16_t*)logits_uncond; a.w = w; a.modality = modality; a.u = u;
+  a.x = x; a.x0 = x0; a.unmask = (const uint8_t*)x0_unmask; a.next_ids = next_ids;
+  a.ld = ld; a.ldm = ldm; a.ldu = ldu; a.ldx = ldx; a.pos_dev = pos_dev;
+  a.seed = seed; a.inv_temperature = inv_temperature; a.budget = budget;
+  a.R = (int)R; a.V = (int)V; a.Vt = (int)Vt; a.mask_id = (int)mask_id; a.restrict_modality = restrict_modality; a.w_scalar = 1;
+  if (logits_uncond) launch_ng<true, true>(a, (unsigned)R, stream); else launch_ng<false, true>(a, (unsigned)R, stream);
+  UDM_CHECK_LAUNCH("udm_ar_nucleus_rows_at");
   return 0;
 }

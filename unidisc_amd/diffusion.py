@@ -1060,6 +1060,17 @@ class Diffusion:
         return runs
 
     @staticmethod
+    def _ar_decode_positions(runs, n0, n_pred):
+        """the positions of the token loop that take a decode step (the others are inside a chunk of `runs`, _ar_given_runs)"""
+        out, i = [], n0
+        while i < n_pred:
+            r = runs.get(i, 0)
+            if not r:
+                out.append(i)
+            i += r + 1
+        return out
+
+    @staticmethod
     def _ar_nucleus(z, top_p, temperature, generator=None):
         """`nucleus_sampling` (model_eval.py:2691-2734), not the p / T quirk of nucleus_sampling_batch: softmax(z / T), sort, keep cumsum <= top_p plus the top
         id, renormalise, multinomial.  z fp32 [R, V] with excluded ids at -inf (softmax is shift-invariant: raw logits give the log-probs' distribution)."""
@@ -1077,7 +1088,9 @@ class Diffusion:
         batch on one cache.  eval.ar_chunk_given (extension): a run of columns behind the prefix that is given in every row is fed through ONE chunk
         forward over the cache (DIT._forward_chunk) instead of one decode step per token (_ar_given_runs; runs shorter than eval.ar_chunk_min_tokens and
         columns given in some rows only stay on the decode path).  Returns (x [B, L], nfe) - nfe counts the argmax steps (0 with top_p, the reference's
-        quirk), chunked or not."""
+        quirk), chunked or not.  eval.ar_decode_graph (extension): the decode step, the token choice and the advance of a device-side position are
+        captured once into a graph (DIT.capture_decode_step) and every decode position is one replay; chunks stay eager.  self.ar_decode_stats counts
+        what the token loop did."""
         self._ar_require_gpu()
         assert B > 0
         assert (x0 is None) == (x0_unmask is None)
@@ -1092,6 +1105,13 @@ class Diffusion:
                 raise NotImplementedError(f"unidisc_amd.Diffusion._ar_sampler: eval.{key} with AR guidance is not built")
         top_p = cfg_get(ev, "top_p", None)
         temperature = float(cfg_get(ev, "temperature", 1.0) or 1.0)
+        # eval.ar_decode_graph (extension key, default false): a replayed step can only hold launches that read the position from device memory, which
+        # the tensor top-p path (a sort, a multinomial draw from a torch.Generator, a host-indexed column write) is not
+        decode_graph = bool(cfg_get(ev, "ar_decode_graph", False))
+        if decode_graph and top_p is not None and not (bool(cfg_get(ev, "fused_nucleus", False)) and self.vocab_size <= K.NUCLEUS_V_MAX):
+            raise NotImplementedError("unidisc_amd.Diffusion._ar_sampler: eval.ar_decode_graph with the tensor top-p path (eval.top_p without "
+                                      f"eval.fused_nucleus, or a vocabulary above {K.NUCLEUS_V_MAX}) - only the fused token-choice kernels read the position "
+                                      "from device memory; set eval.fused_nucleus or unset eval.ar_decode_graph")
         bos = self._ar_bos_id(bos_token_id)
         L = int(cfg_get(m, "length"))
         n_pred = L - 1
@@ -1151,6 +1171,14 @@ class Diffusion:
             if guided:
                 kv.ids[B:2 * B] = torch.where(x0_unmask[:, i + 1], torch.full_like(col, self.mask_index), col)
 
+        def choose_at():   # choose(i) with i read from kv.pos_dev by the kernel: the token choice of the captured step
+            kw = dict(modality=modality, restrict=restrict, seed=base_seed, x0=x0, x0_unmask=x0_unmask, next_ids=kv.ids,
+                      logits_u=logits[B:] if guided else None, w=w if guided else None, rows=B)
+            if fused_top_p:
+                K.ar_nucleus_rows_at(logits, x, kv.pos_dev, V, Vt, self.mask_index, inv_temperature=1.0 / temperature, budget=float(top_p), **kw)
+            else:
+                K.ar_sample_rows_at(logits, x, kv.pos_dev, V, Vt, self.mask_index, g=noise, **kw)
+
         n0 = self._ar_fixed_prefix(x0_unmask, L)
         ids0 = x[:, :n0]
         if guided:
@@ -1168,6 +1196,13 @@ class Diffusion:
             runs = self._ar_given_runs(self._ar_given_columns(x0_unmask), n0, L, max(min_tokens, 2))
         bb._prefill(ids0, mod0, last_only=True)
         choose(n0 - 1)
+        stats = self.ar_decode_stats = dict(captures=0, replays=0, eager_steps=0, chunks=0)
+        graph = None
+        if decode_graph and self._ar_decode_positions(runs, n0, n_pred):
+            # one capture per call, on this call's cache and state tensors (nothing of it outlives the call); its eager warm-up run is undone
+            bb.set_decode_position(n0)
+            graph = bb.capture_decode_step(choose_at)
+            stats["captures"] = 1
         i = n0
         while i < n_pred:
             r = runs.get(i, 0)
@@ -1177,10 +1212,20 @@ class Diffusion:
                     ids = torch.cat([ids, torch.where(x0_unmask, self.mask_index, x)[:, i:i + r + 1]], 0)
                 bb._forward_chunk(ids, None, i, last_only=True)      # (modality columns i .. i + r: the cache's full-length map)
                 i += r
+                stats["chunks"] += 1
+            elif graph is not None:   # the decode step at the device's position, the token choice and position + 1: one graph launch
+                graph.replay()
+                stats["replays"] += 1
+                i += 1
+                continue
             else:
                 bb._decode_step(i)
+                stats["eager_steps"] += 1
             choose(i)   # (the Philox draws are keyed by the step: the steps a chunk skipped move no other draw)
             i += 1
+            if r and graph is not None:
+                bb.set_decode_position(i)   # a device-side fill: the replays go on behind the chunk
+        graph = None   # (holds the cache's addresses: dropped before the cache)
         bb.reset_kv_cache(batch_size=R, seq_len=n_pred, dtype=self.dtype, device=dev, set_to_none=True)
         return x, (n_pred if top_p is None else 0)
 

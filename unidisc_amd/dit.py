@@ -309,6 +309,41 @@ class _Backward(_Record):
 # ------------------------------------------------------------------------------------------------
 # the module
 # ------------------------------------------------------------------------------------------------
+class _DecodeGraph:
+    """One captured decode step of a DIT on its KV cache (DIT.capture_decode_step).  Holds the addresses of the cache's buffers: it is valid until the
+    next reset_kv_cache and must be dropped before it."""
+
+    def __init__(self, dit, tail):
+        kv = dit._kv
+        self._dit, self._kv = weakref.ref(dit), kv
+
+        def step():
+            dit._decode_step_at()
+            if tail is not None:
+                tail()
+            K.counter_add(kv.pos_dev, 1)
+
+        ids0, pos0 = kv.ids.clone(), kv.pos_dev.clone()
+        step()                                   # warm-up, undone below
+        kv.ids.copy_(ids0), kv.pos_dev.copy_(pos0)
+        torch.cuda.current_stream().synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        try:
+            with torch.cuda.graph(self.graph):
+                step()
+        except Exception as e:   # (a launch refused under capture answers through udm_last_error: the message names it)
+            self.graph = None
+            raise RuntimeError(f"unidisc_amd.DIT.capture_decode_step: the runtime rejected the capture of the decode step: {e}") from e
+
+    def replay(self):
+        """one graph launch: the decode step at the device's position, the token choice, position + 1"""
+        dit = self._dit()
+        if dit is None or dit._kv is not self._kv or self.graph is None:
+            raise RuntimeError("unidisc_amd.DIT: this captured decode step belongs to a KV cache that was reset")
+        self.graph.replay()
+        self._kv.pos += 1
+
+
 class DIT(nn.Module, _HubMixin):
     def __init__(self, config, vocab_size: int, text_vocab_size: int, mask_index: int, dtype=None, device=None, static_img_sl=None, static_txt_sl=None,
                  **kwargs):
@@ -528,6 +563,11 @@ class DIT(nn.Module, _HubMixin):
             kv.cos, kv.sin = cos.transpose(0, 1).contiguous(), sin.transpose(0, 1).contiguous()
         else:
             kv.cos = kv.sin = None
+        # the device-side position of _decode_step_at and the fixed one-row operands udm_decode_stage fills from it (what a captured step reads)
+        kv.pos_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        kv.mod_row = torch.zeros(Bp, dtype=torch.int64, device=dev) if (kv.mod_cols is not None and self.modality_embed is not None) else None
+        kv.rope_tabs = (kv.cos, kv.sin) if kv.cos is not None else (self.rotary_cos_emb.contiguous(), self.rotary_sin_emb.contiguous())
+        kv.cos_row, kv.sin_row = torch.zeros_like(kv.rope_tabs[0][:1]), torch.zeros_like(kv.rope_tabs[1][:1])
         self._kv = kv
 
     def _refresh_shadows_now(self):
@@ -549,16 +589,35 @@ class DIT(nn.Module, _HubMixin):
         """One token per cached row at position p (the ids in self._kv.ids) -> logits [Bp, Vp] bf16 (self._kv.logits).  Engine path without autograd or host
         synchronisation: norm, skinny qkv, qk-norm + rope (row p of the full-length tables), decode attention (appends k / v at slot p), skinny out-proj,
         residual + norm, skinny up + GELU, skinny down, residual (+ the next block's norm), head."""
+        kv = self._kv
+        emb_mod = kv.mod_cols[p] if (self.modality_embed is not None) else None
+        cos, sin = self._rope_rows(p)
+        self._decode_launches(emb_mod, cos, sin, p)
+        kv.pos = p + 1
+        return kv.logits
+
+    @torch.no_grad()
+    def _decode_step_at(self):
+        """_decode_step at the position held in self._kv.pos_dev (device memory, read by the kernels): the same launches on fixed operands - one gather of
+        the position's modality column and rotary rows into one-row buffers (udm_decode_stage), attention through udm_attention_decode_at.  No host
+        position, no allocation, no read of the device: the sequence a graph captures once and replays for every token (capture_decode_step).  The
+        caller keeps self._kv.pos in step (the host cannot know the device's position)."""
+        kv = self._kv
+        K.decode_stage(kv.pos_dev, mod_cols=kv.mod_cols if kv.mod_row is not None else None, mod_row=kv.mod_row, cos=kv.rope_tabs[0], sin=kv.rope_tabs[1],
+                       cos_row=kv.cos_row, sin_row=kv.sin_row)
+        self._decode_launches(kv.mod_row, kv.cos_row, kv.sin_row, None)
+        return kv.logits
+
+    def _decode_launches(self, emb_mod, cos, sin, p):
+        """the launches of a decode step behind its position-dependent operands; p None: the attention reads the position from self._kv.pos_dev"""
         kv, lin = self._kv, self._lins
         d, H, D = self.hidden_size, self.n_heads, self.head_dim
         nt = K.norm_id(self.norm_type)
         sw = self.sandwich_normalization
-        emb_mod = kv.mod_cols[p] if (self.modality_embed is not None) else None
         xa, xb = kv.x
         st = kv.stat
         K.embedding_fwd(kv.ids, self.vocab_embed.embedding.detach(), emb_mod, self.modality_embed.embedding.detach() if self.modality_embed is not None else None,
                         out=xa)
-        cos, sin = self._rope_rows(p)
         res_out = (None, st[0], st[1], kv.h, st[2], st[3])
         for i, blk in enumerate(self.blocks):
             if i == 0:
@@ -567,7 +626,10 @@ class DIT(nn.Module, _HubMixin):
             at = blk.attention
             qn_kw = dict(gq=at.q_norm.weight.detach(), bq=at.q_norm.bias.detach(), gk=at.k_norm.weight.detach(), bk=at.k_norm.bias.detach()) if self.qk_norm else {}
             qkr, _ = K.qknorm_rope_fwd(qkv, cos, sin, 1, D, q_scale=self.attn_q_scale, out=(kv.qkr, kv.qstats), **qn_kw)
-            o = K.attention_decode(qkr[:, :d], qkr[:, d:], qkv[:, 2 * d:], kv.K[i], kv.V[i], p, H, D, out=kv.o, ws=kv.aws)
+            if p is None:
+                o = K.attention_decode_at(qkr[:, :d], qkr[:, d:], qkv[:, 2 * d:], kv.K[i], kv.V[i], kv.pos_dev, H, D, out=kv.o, ws=kv.aws)
+            else:
+                o = K.attention_decode(qkr[:, :d], qkr[:, d:], qkv[:, 2 * d:], kv.K[i], kv.V[i], p, H, D, out=kv.o, ws=kv.aws)
             a_out = K.gemm_skinny(o, lin[f"{i}.out"].w16, out=kv.a_out, N=d, ws=kv.gws)
             K.residual_fwd(xa, a_out, 1, w_b=blk.pre_residual_norm.weight.detach() if sw else None, norm_type=nt, next_w=blk.norm2.weight.detach(),
                            out=(xb,) + res_out[1:])
@@ -578,8 +640,27 @@ class DIT(nn.Module, _HubMixin):
             K.residual_fwd(xb, u2, 1, w_b=blk.post_ff_norm.weight.detach() if sw else None, norm_type=nt, next_w=nxt_w, out=(xa,) + res_out[1:])
         head = lin["head"]
         K.gemm_skinny(kv.h, head.w16, out=kv.logits, N=self.vocab_size, epilogue=K.EPI_BIAS, bias=head.bias.detach(), ws=kv.gws)
-        kv.pos = p + 1
-        return kv.logits
+
+    def set_decode_position(self, p):
+        """the position the next _decode_step_at / replay works at: a device-side fill of self._kv.pos_dev, no host read (after a prefill or a chunk: p =
+        the number of cache slots written)"""
+        kv = self._kv
+        kv.pos = int(p)
+        kv.pos_dev.fill_(int(p))
+
+    def capture_decode_step(self, tail=None):
+        """Capture `_decode_step_at(); tail(); pos_dev += 1` into one graph and return it: `replay()` is then one graph launch per token, whatever the
+        position.  tail: the token choice on self._kv.logits, through the device-position forms (K.ar_sample_rows_at / K.ar_nucleus_rows_at on
+        self._kv.pos_dev), writing the next input ids into self._kv.ids.  The sequence runs once eagerly first (first launches, any lazy allocation); that
+        run is undone - self._kv.ids and the position are put back, and what else it wrote (cache slot p, the tail's outputs) the first replay writes again
+        with the same values, since every launch is deterministic in (ids, position).  The weight shadows are refreshed and any recast queued on the side
+        stream is awaited before, so the capture holds launches of one stream only: one linear chain.  A capture the runtime rejects raises RuntimeError
+        naming the launch; there is no eager fallback."""
+        kv = self._kv
+        if kv is None:
+            raise RuntimeError("unidisc_amd.DIT.capture_decode_step: no KV cache - call reset_kv_cache(batch_size, seq_len, ...) first")
+        self._refresh_shadows_now()
+        return _DecodeGraph(self, tail)
 
     @torch.no_grad()
     def _prefill(self, ids, modality=None, last_only=False):

@@ -1154,6 +1154,103 @@ def ar_sample_rows(logits, x, pos, V, Vt, mask_id, *, step=0, modality=None, res
     return x
 
 
+# ---- the decode step on a device-side position (`pos_dev`: int64 [1] on the GPU): what a captured graph replays unchanged, token after token
+def _chk_pos_dev(pos_dev, name):
+    if pos_dev.dtype != torch.int64 or pos_dev.numel() != 1:
+        raise TypeError(f"{name}: pos_dev must be one int64 on the GPU")
+
+
+def attention_decode_s_bound(BH, Lmax, cap=32):
+    """the largest number of key splits udm_attention_decode takes at any position below Lmax (csrc/decode_plan.h: decode_plan_s_bound) - grid.y of the
+    device-position form.  Not the splits of Lmax: S is not monotone in the position."""
+    return max(1, min(-(-512 // BH), 32, -(-Lmax // 64), cap))
+
+
+def attention_decode_at(q, k_new, v_new, k_cache, v_cache, pos_dev, H, D, out=None, ws=None):
+    """`attention_decode` at the position held in pos_dev, read by the kernel: a fixed grid, bit-identical results; a position outside the cache stores nothing"""
+    _chk_pos_dev(pos_dev, "attention_decode_at")
+    B, Lmax, d = k_cache.shape
+    if out is None:
+        out = torch.empty((B, d), dtype=BF16, device=q.device)
+    _lib.call("udm_attention_decode_at", _p(q), _p(k_new), _p(v_new), _p(k_cache), _p(v_cache), _p(out), _p(ws), ws.numel() if ws is not None else 0, B, H, D,
+              Lmax, _p(pos_dev), q.stride(0), k_new.stride(0), v_new.stride(0), out.stride(0), _s())
+    return out
+
+
+def ar_sample_rows_at(logits, x, pos_dev, V, Vt, mask_id, *, modality=None, restrict=False, g=None, seed=0, x0=None, x0_unmask=None, next_ids=None,
+                      logits_u=None, w=None, rows=None):
+    """`ar_sample_rows(pos=i + 1, step=i, g_col0=i * V)` with i read from pos_dev by the kernel; i + 1 outside x stores nothing"""
+    _chk(logits, BF16, "ar_sample_rows_at logits")
+    _chk_pos_dev(pos_dev, "ar_sample_rows_at")
+    R = x.shape[0] if rows is None else rows
+    if (logits_u is None) != (w is None):
+        raise ValueError("ar_sample_rows_at: guidance needs both logits_u and w")
+    if logits_u is not None and logits_u.stride(0) != logits.stride(0):
+        raise ValueError("ar_sample_rows_at: logits_u must have the row stride of logits")
+    for t, name in ((x, "x"), (x0, "x0"), (modality, "modality")):
+        if t is not None and (t.dtype != torch.int64 or t.stride(-1) != 1):
+            raise TypeError(f"ar_sample_rows_at: {name} must be int64 with contiguous rows")
+    if x0_unmask is not None and (x0_unmask.dtype != torch.bool or x0_unmask.stride(0) != x.stride(0) or x0.stride(0) != x.stride(0)):
+        raise TypeError("ar_sample_rows_at: x0 / x0_unmask must be laid out like x (bool mask)")
+    if g is not None:
+        _chk(g, F32, "ar_sample_rows_at g")
+    _lib.call("udm_ar_sample_rows_at", _p(logits), _p(logits_u), _p(w), logits.stride(0), _p(modality), modality.stride(0) if modality is not None else 0, _p(g),
+              g.stride(0) if g is not None else 0, int(seed), _p(x), x.stride(0), _p(x0), _p(x0_unmask), _p(pos_dev), _p(next_ids), R, V, Vt, mask_id,
+              1 if restrict else 0, _s())
+    return x
+
+
+def ar_nucleus_rows_at(logits, x, pos_dev, V, Vt, mask_id, *, inv_temperature, budget, modality=None, restrict=False, u=None, seed=0, x0=None, x0_unmask=None,
+                       next_ids=None, logits_u=None, w=None, rows=None):
+    """`ar_nucleus_rows(pos=i + 1, step=i, u_col0=i * V)` with i read from pos_dev by the kernel; i + 1 outside x stores nothing"""
+    _chk(logits, BF16, "ar_nucleus_rows_at logits")
+    _chk_pos_dev(pos_dev, "ar_nucleus_rows_at")
+    R = x.shape[0] if rows is None else rows
+    if (logits_u is None) != (w is None):
+        raise ValueError("ar_nucleus_rows_at: guidance needs both logits_u and w")
+    if logits_u is not None and logits_u.stride(0) != logits.stride(0):
+        raise ValueError("ar_nucleus_rows_at: logits_u must have the row stride of logits")
+    for t, name in ((x, "x"), (x0, "x0"), (modality, "modality")):
+        if t is not None and (t.dtype != torch.int64 or t.stride(-1) != 1):
+            raise TypeError(f"ar_nucleus_rows_at: {name} must be int64 with contiguous rows")
+    if x0_unmask is not None and (x0_unmask.dtype != torch.bool or x0_unmask.stride(0) != x.stride(0) or x0.stride(0) != x.stride(0)):
+        raise TypeError("ar_nucleus_rows_at: x0 / x0_unmask must be laid out like x (bool mask)")
+    if u is not None:
+        _chk(u, F32, "ar_nucleus_rows_at u")
+    _lib.call("udm_ar_nucleus_rows_at", _p(logits), _p(logits_u), _p(w), logits.stride(0), _p(modality), modality.stride(0) if modality is not None else 0, _p(u),
+              u.stride(0) if u is not None else 0, int(seed), float(inv_temperature), float(budget), _p(x), x.stride(0), _p(x0), _p(x0_unmask), _p(pos_dev),
+              _p(next_ids), R, V, Vt, mask_id, 1 if restrict else 0, _s())
+    return x
+
+
+def decode_stage(pos_dev, *, mod_cols=None, mod_row=None, cos=None, sin=None, cos_row=None, sin_row=None):
+    """row *pos_dev of mod_cols [L, Bp] into mod_row [Bp] and of the contiguous fp32 tables cos / sin [L, ...] into cos_row / sin_row [1, ...], in one launch;
+    a position outside the tables copies nothing"""
+    _chk_pos_dev(pos_dev, "decode_stage")
+    L = Bp = rope_row = 0
+    if mod_cols is not None:
+        if mod_cols.dtype != torch.int64 or mod_cols.dim() != 2 or not mod_cols.is_contiguous() or mod_row.dtype != torch.int64 or not mod_row.is_contiguous() \
+                or mod_row.numel() != mod_cols.shape[1]:
+            raise TypeError("decode_stage: mod_cols must be contiguous int64 [L, Bp] and mod_row int64 [Bp]")
+        L, Bp = mod_cols.shape
+    if cos is not None:
+        rope_row = cos[0].numel()
+        for t, n in ((cos, None), (sin, None), (cos_row, rope_row), (sin_row, rope_row)):
+            _chk_packed_f32(t, "decode_stage rotary operand", n)
+        if sin.shape != cos.shape or (L and cos.shape[0] != L):
+            raise ValueError("decode_stage: cos, sin and mod_cols must have the same number of rows")
+        L = cos.shape[0]
+    if L == 0:
+        return
+    _lib.call("udm_decode_stage", _p(pos_dev), _p(mod_cols), _p(mod_row), Bp, _p(cos), _p(sin), _p(cos_row), _p(sin_row), rope_row, L, _s())
+
+
+def counter_add(counter, delta=1):
+    """counter[0] += delta on the stream (one thread): the last launch of a captured decode step"""
+    _chk_pos_dev(counter, "counter_add")
+    _lib.call("udm_counter_add", _p(counter), int(delta), _s())
+
+
 NUCLEUS_V_MAX = 65536   # udm_nucleus_sample_rows / udm_ar_nucleus_rows hold the row in registers: a larger vocabulary is refused (the hosts keep the tensor path)
 
 
