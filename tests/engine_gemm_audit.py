@@ -441,13 +441,14 @@ def cases():
     return dict(plain=dict(_PLUMB, n_blocks=2, time_conditioning=False), plain_adaln=dict(_PLUMB, n_blocks=2, time_conditioning=True), mm=mm)
 
 
-def build(model, device):
-    """seeded weights, head and adaLN weights randomised (the reference zero-initialises them), as `_product` of tests/test_gpu_shadow_lifecycle.py"""
+def build(model, device, case=None):
+    """seeded weights, head and adaLN weights randomised (the reference zero-initialises them), as `_product` of tests/test_gpu_shadow_lifecycle.py;
+    `case`: config keys on top of `cases()[model]` (tests/engine_rowattn_audit.py: the modality masking probabilities)"""
     from product_utils import product_config
     from unidisc_amd import Diffusion
 
     torch.manual_seed(0)
-    diff = Diffusion(product_config(cases()[model]), None, device)
+    diff = Diffusion(product_config(dict(cases()[model], **(case or {}))), None, device)
     diff.backbone.train()
     diff.rng_device = "cpu"
     wg = torch.Generator().manual_seed(5)

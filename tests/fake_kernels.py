@@ -1,4 +1,5 @@
-"""CPU stand-ins for ``unidisc_amd.kernels`` used ONLY by tests/test_engine_orchestration.py.
+"""CPU stand-ins for ``unidisc_amd.kernels`` used ONLY by the engine tests that run without a GPU (tests/test_engine_orchestration.py and the host halves of the
+engine audits, tests/test_engine_gemm_audit_host.py and tests/test_engine_rowattn_audit_host.py).
 
 They let the hand-scheduled forward/backward engine in ``unidisc_amd/dit.py`` (buffer plumbing, gradient
 bookkeeping, adaLN chunk indexing, callbacks) be exercised in the GPU-less container.  They are test doubles:
@@ -130,7 +131,7 @@ def norm_bwd(dy, x, rstd, mean, w, norm_type, L, dx, dw, *, accumulate=True, mod
         dmod += mod_.grad
 
 
-def _branch(x_in, br, L, w_b, norm_type, mod, gate_idx, modality):
+def _branch(x_in, br, L, w_b, norm_type, mod, gate_idx, modality, p_drop=0.0, seed=0):
     n = br
     rstd = mean = None
     if w_b is not None:
@@ -141,19 +142,22 @@ def _branch(x_in, br, L, w_b, norm_type, mod, gate_idx, modality):
         else:
             n, rstd, mean = _norm(br, w_b, norm_type)
     out = n
+    if p_drop > 0.0:   # the kernels' mask (rowops_ref64.dropout_keep restates it), on the rows the gate applies to, in front of the gate
+        import rowops_ref64
+        keep = rowops_ref64.dropout_keep(int(seed), float(p_drop), br.shape[0], br.shape[1])
+        out = torch.where(keep, n * rowops_ref64.keep_scale(p_drop), torch.zeros_like(n))
     if mod is not None and gate_idx is not None:
         d = br.shape[1]
         g = mod[_rows_to_batch(br.shape[0], L), gate_idx * d:(gate_idx + 1) * d]
-        out = g * n
-        if modality is not None:
-            out = torch.where((modality == 1)[:, None], out, n)
+        out = g * out
+    if modality is not None:
+        out = torch.where((modality == 1)[:, None], out, n)
     return x_in + out, rstd, mean
 
 
 def residual_fwd(x_in, branch, L, *, w_b=None, norm_type=NORM_RMS, mod=None, gate_idx=None, modality=None, p_drop=0.0, seed=0, next_w=None, next_mod=None,
                  next_mod_idx=(0, 1), next_modality=None, next_any_img=None):
-    assert p_drop == 0.0, "fake kernels: dropout not emulated"
-    out, rstd, mean = _branch(x_in, branch.float(), L, w_b, norm_type, mod.float() if mod is not None else None, gate_idx, modality)
+    out, rstd, mean = _branch(x_in, branch.float(), L, w_b, norm_type, mod.float() if mod is not None else None, gate_idx, modality, p_drop, seed)
     if next_w is None:
         return out, rstd, mean
     return out, rstd, mean, norm_fwd(out, next_w, norm_type, L, mod=next_mod, mod_idx=next_mod_idx, modality=next_modality, any_img=next_any_img)
@@ -189,7 +193,7 @@ def residual_bwd(dx, branch, L, *, w_b=None, rstd=None, mean=None, norm_type=NOR
     br = branch.float().clone().requires_grad_()
     w_ = w_b.clone().requires_grad_() if w_b is not None else None
     mod_ = mod.float().clone().requires_grad_() if (mod is not None and gate_idx is not None) else None
-    out, _, _ = _branch(torch.zeros_like(dx), br, L, w_, norm_type, mod_, gate_idx, modality)
+    out, _, _ = _branch(torch.zeros_like(dx), br, L, w_, norm_type, mod_, gate_idx, modality, p_drop, seed)
     out.backward(dx)
     if w_b is not None:
         dw_b += w_.grad
@@ -228,7 +232,10 @@ def qknorm_rope_fwd(qkv, cos, sin, L, D, *, gq=None, bq=None, gk=None, bk=None, 
     out = _qk(qkv.float(), cos, sin, L, D, gq, bq, gk, bk)
     d = out.shape[1] // 2
     out = torch.cat([out[:, :d] * q_scale, out[:, d:]], 1).bfloat16()
-    stats = torch.zeros(qkv.shape[0], 4) if gq is not None else None
+    stats = None
+    if gq is not None:   # (mean, rstd) of the q and of the k columns, the statistics the backward kernel is handed
+        q, k = qkv[:, :d].float(), qkv[:, d:2 * d].float()
+        stats = torch.stack([q.mean(-1), torch.rsqrt(q.var(-1, unbiased=False) + 1e-5), k.mean(-1), torch.rsqrt(k.var(-1, unbiased=False) + 1e-5)], 1)
     return out, stats
 
 
@@ -266,7 +273,7 @@ def qknorm_rope_bwd(dqkr, qkv, dqkv, cos, sin, L, D, *, gq=None, gk=None, stats=
         dbk += gb[:, d:].sum(0)
 
 
-def _attn(q, k, v, B, L, H, D, sid):
+def _attn(q, k, v, B, L, H, D, sid, want_lse=False):
     q, k, v = (t.reshape(B, L, H, D).transpose(1, 2) for t in (q, k, v))
     s = q @ k.transpose(-1, -2) / math.sqrt(D)
     if sid is not None:   # mask codes (csrc/attention_common.h: attn_pair_ok): low 32 bits sample id, bits 32-39 key class, 40-47 query mask
@@ -276,7 +283,11 @@ def _attn(q, k, v, B, L, H, D, sid):
         allow = (ids[:, :, None] == ids[:, None, :]) & (ids[:, :, None] >= 0) & ((qm[:, :, None] & kb[:, None, :]) != 0)
         s = s.masked_fill(~allow[:, None], float("-inf"))
     p = torch.nan_to_num(torch.softmax(s, -1), nan=0.0)
-    return (p @ v).transpose(1, 2).reshape(B * L, H * D)
+    o = (p @ v).transpose(1, 2).reshape(B * L, H * D)
+    if want_lse:   # base 2, +inf on a row that sees no key: what the kernels store
+        lse = torch.logsumexp(s, -1) * 1.4426950408889634
+        return o, torch.where(torch.isinf(lse), torch.full_like(lse, float("inf")), lse)
+    return o
 
 
 def modality_mask_codes(txt_drop, img_drop, txt_length, L):
@@ -310,8 +321,8 @@ def attention_doc_ranges(sample_ids):
 def attention_fwd(qkr, qkv, B, L, H, D, sample_ids=None, doc_ranges=None, q_prescaled=False):
     d = H * D
     qs = attention_q_scale(D) if q_prescaled else 1.0
-    o = _attn(qkr[:, :d].float() / qs, qkr[:, d:].float(), qkv[:, 2 * d:].float(), B, L, H, D, sample_ids)
-    return o.bfloat16(), torch.zeros(B, H, L)
+    o, lse = _attn(qkr[:, :d].float() / qs, qkr[:, d:].float(), qkv[:, 2 * d:].float(), B, L, H, D, sample_ids, want_lse=True)
+    return o.bfloat16(), lse.float()
 
 
 @torch.enable_grad()
