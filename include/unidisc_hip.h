@@ -425,8 +425,10 @@ int udm_adamw_step_shadow_ema(float* p, const float* g, float* m, float* v, int6
                               int64_t ldt, float* ema, float ema_decay, hipStream_t stream);
 
 /* ---- KV-cached AR decoding: `_ar_sampler` model_eval.py:2736-2822 with model.use_kv_cache (cache models/dit.py:588-607, 776-780, 1462-1473).
- * udm_gemm_skinny_bf16: C[M, N] = A[M, K] W[N, K]^T for 1 <= M <= 64 (a decode step's rows against the bf16 weight shadows): each weight byte is read once,
+ * udm_gemm_skinny_bf16: C[M, N] = A[M, K] W[N, K]^T for 1 <= M <= 128 (a decode step's rows against the bf16 weight shadows): each weight byte is read once,
  *   by one workgroup; K is also split over workgroups (fp32 partial slabs in ws, a second launch sums them) where the column tiles alone leave CUs idle.
+ *   M > 64 runs the rows [0, 64) and [64, M) as two row groups of one launch on the same weight fragments: with the same number of slices (ws_elems >=
+ *   the slices M * N of the call) each group equals, bit for bit, a call on its rows alone.  M > 128 returns 2 (the message names the bound).
  *   K % 32 == 0, lda / ldw multiples of 8; epilogue UDM_EPI_NONE, UDM_EPI_BIAS or UDM_EPI_BIAS_GELU (C = gelu_tanh(bf16(A W^T + bias)), no saved derivative);
  *   out_f32: C is fp32.  ws (nullable: never split): fp32, slices * M * N elements are used, slices <= 32.
  * udm_attention_decode: one new token per sequence, every row at position p.  Writes the new key row (k_new: after qk-norm + rope, as udm_qknorm_rope_fwd

@@ -1,11 +1,13 @@
 // KV-cached next-token decoding of the AR baseline (`_ar_sampler`, model_eval.py:2736-2822, cache models/dit.py:588-607, 776-780, 1462-1473): the three
 // kernels a decode step needs that the training path has no form for.
 //
-//   udm_gemm_skinny_bf16   out[M, N] = A[M, K] W[N, K]^T for M <= 64 (the B rows of a decode step): weight streaming.  Every weight byte is read from HBM
+//   udm_gemm_skinny_bf16   out[M, N] = A[M, K] W[N, K]^T for M <= 128 (the B rows of a decode step): weight streaming.  Every weight byte is read from HBM
 //                          by exactly one workgroup.  A wave owns 32 output columns over a K range and loads its operands straight to VGPRs (16 B per lane,
 //                          four 32-deep k-steps in flight) for 16x16x32 MFMAs; the four waves of a workgroup split the workgroup's K range and sum through
 //                          LDS.  Where the column tiles alone leave CUs idle (N = d out-projection, K = 4 d down-projection) K is also split over
-//                          workgroups: fp32 partial slabs in `ws` and a second launch that sums them and applies the epilogue.
+//                          workgroups: fp32 partial slabs in `ws` and a second launch that sums them and applies the epilogue (the split: skinny_plan.h).
+//                          M <= 64 is one group of up to four 16-row tiles (skinny_gemm_kernel); 65 <= M <= 128 is two such groups, rows [0, 64) and
+//                          [64, M), in one workgroup on the same weight fragments (skinny_gemm2_kernel), each group bit-identical to a call on its rows.
 //   udm_attention_decode   one query row per (b, h) against the per-layer cache, all rows at the same position p (flash-decoding): the keys are split
 //                          over workgroups so that B H x splits covers the chip; each split keeps fp32 (m, l, acc) and a second launch combines them.  The
 //                          new key / value row is read from its producer for key p and written to cache slot p by the split that owns p - no other
@@ -24,6 +26,7 @@
 // A position outside its range makes every workgroup return before its first access.  All of these are plain loads and stores.
 #include "common.h"
 #include "decode_plan.h"
+#include "skinny_plan.h"
 #include "../../include/unidisc_hip.h"
 
 namespace {
@@ -114,6 +117,111 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(SkArgs a) {
     const int ln = e & 63, r = (e >> 6) & 3, t = e >> 8;
     const int nb = t % SK_NB, mt = t / SK_NB;
     const int m = mt * 16 + (ln >> 4) * 4 + r, n = n0 + nb * 16 + (ln & 15);
+    if (m >= a.M || n >= a.N) continue;
+    if (a.S == 1) sk_store(a, m, n, sk_epilogue(v, n, a));
+    else a.ws[((long)s * a.M + m) * a.N + n] = v;
+  }
+}
+
+// 65 <= M <= 128: two row groups in one workgroup.  Group 0 is the rows [0, 64) (four 16-row tiles), group 1 the rows [64, M) (MT1 = 1..4 tiles).  Grid, wave
+// layout and K walk are skinny_gemm_kernel's; per k-group a wave loads its W fragments once (non-temporal) and feeds them to both groups' MFMAs, so every
+// weight byte is still read from HBM by one workgroup, once.  The A fragments are loaded per group, into the same registers.  Per output element the order of
+// the sum is skinny_gemm_kernel's on that element's group: k-steps ascending in a wave, w0 + w1 + w2 + w3 through LDS, the K slabs ascending in
+// skinny_reduce_kernel - rows [0, 64) and [64, M) equal, bit for bit, two launches of skinny_gemm_kernel<4> and <MT1> on those rows with the same K split.
+// Budget per lane (planned before coding, MT1 = 4): accumulators of both groups (4 + 4) x 2 x 4 = 64, W fragments SK_U x 2 x 4 = 32, one group's A
+// fragments SK_U x 4 x 4 = 64, 10 row pointers 20: 180 of the 256 registers that leave two waves per SIMD; amdgpu_waves_per_eu(2) holds the compiler
+// to that.  LDS: the cross-wave sum runs per group over the `red` layout of skinny_gemm_kernel<4>, 4 x 2048 floats = 32 KB, as there.
+template <int MT1>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void skinny_gemm2_kernel(SkArgs a) {
+  constexpr int MT0 = 4;
+  __shared__ float red[4 * MT0 * SK_NB * 4 * 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n0 = blockIdx.x * 32;
+  const int s = blockIdx.y;
+  const int kbeg = s * a.kslice;
+  const int kend = min(a.K, kbeg + a.kslice);
+  const int kl = 8 * (lane >> 4);
+  // (rows past M / N clamped to a valid row, as in skinny_gemm_kernel; group 1 clamps to M - 1, the last row of its own range)
+  const bf16_t* wrow[SK_NB];
+#pragma unroll
+  for (int nb = 0; nb < SK_NB; ++nb) wrow[nb] = a.W + (long)min(n0 + nb * 16 + (lane & 15), a.N - 1) * a.ldw + kl;
+  const bf16_t* arow0[MT0];
+#pragma unroll
+  for (int mt = 0; mt < MT0; ++mt) arow0[mt] = a.A + (long)(mt * 16 + (lane & 15)) * a.lda + kl;
+  const bf16_t* arow1[MT1];
+#pragma unroll
+  for (int mt = 0; mt < MT1; ++mt) arow1[mt] = a.A + (long)min(64 + mt * 16 + (lane & 15), a.M - 1) * a.lda + kl;
+
+  f32x4_t acc0[MT0][SK_NB], acc1[MT1][SK_NB];
+#pragma unroll
+  for (int nb = 0; nb < SK_NB; ++nb) {
+#pragma unroll
+    for (int mt = 0; mt < MT0; ++mt) acc0[mt][nb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int mt = 0; mt < MT1; ++mt) acc1[mt][nb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  }
+
+  for (int k0 = kbeg + wave * 32 * SK_U; k0 < kend; k0 += 4 * 32 * SK_U) {
+    u32x4_t wf[SK_U][SK_NB], af0[SK_U][MT0], af1[SK_U][MT1];
+#pragma unroll
+    for (int u = 0; u < SK_U; ++u) {
+      const int k = k0 + 32 * u;
+      const bool ok = k < kend;
+#pragma unroll
+      for (int nb = 0; nb < SK_NB; ++nb) wf[u][nb] = ok ? __builtin_nontemporal_load((const u32x4_t*)(wrow[nb] + k)) : u32x4_t{0, 0, 0, 0};
+#pragma unroll
+      for (int mt = 0; mt < MT0; ++mt) af0[u][mt] = ok ? *(const u32x4_t*)(arow0[mt] + k) : u32x4_t{0, 0, 0, 0};
+    }
+#pragma unroll
+    for (int u = 0; u < SK_U; ++u)
+#pragma unroll
+      for (int mt = 0; mt < MT0; ++mt)
+#pragma unroll
+        for (int nb = 0; nb < SK_NB; ++nb) acc0[mt][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(af0[u][mt]), as_frag(wf[u][nb]), acc0[mt][nb], 0, 0, 0);
+#pragma unroll
+    for (int u = 0; u < SK_U; ++u) {
+      const bool ok = k0 + 32 * u < kend;
+#pragma unroll
+      for (int mt = 0; mt < MT1; ++mt) af1[u][mt] = ok ? *(const u32x4_t*)(arow1[mt] + k0 + 32 * u) : u32x4_t{0, 0, 0, 0};
+    }
+#pragma unroll
+    for (int u = 0; u < SK_U; ++u)
+#pragma unroll
+      for (int mt = 0; mt < MT1; ++mt)
+#pragma unroll
+        for (int nb = 0; nb < SK_NB; ++nb) acc1[mt][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(af1[u][mt]), as_frag(wf[u][nb]), acc1[mt][nb], 0, 0, 0);
+  }
+  // the cross-wave sum of skinny_gemm_kernel, once per group: element e = ((mt * NB + nb) * 4 + r) * 64 + lane, row = the group's first row + ...
+  constexpr int E0 = MT0 * SK_NB * 4 * 64, E1 = MT1 * SK_NB * 4 * 64;
+#pragma unroll
+  for (int mt = 0; mt < MT0; ++mt)
+#pragma unroll
+    for (int nb = 0; nb < SK_NB; ++nb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wave * E0 + ((mt * SK_NB + nb) * 4 + r) * 64 + lane] = acc0[mt][nb][r];
+  __syncthreads();
+  for (int e = threadIdx.x; e < E0; e += 256) {
+    const float v = red[e] + red[E0 + e] + red[2 * E0 + e] + red[3 * E0 + e];
+    const int ln = e & 63, r = (e >> 6) & 3, t = e >> 8;
+    const int nb = t % SK_NB, mt = t / SK_NB;
+    const int m = mt * 16 + (ln >> 4) * 4 + r, n = n0 + nb * 16 + (ln & 15);
+    if (n >= a.N) continue;   // (m < 64 < M)
+    if (a.S == 1) sk_store(a, m, n, sk_epilogue(v, n, a));
+    else a.ws[((long)s * a.M + m) * a.N + n] = v;
+  }
+  __syncthreads();   // group 0 has been read out of `red`
+#pragma unroll
+  for (int mt = 0; mt < MT1; ++mt)
+#pragma unroll
+    for (int nb = 0; nb < SK_NB; ++nb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wave * E1 + ((mt * SK_NB + nb) * 4 + r) * 64 + lane] = acc1[mt][nb][r];
+  __syncthreads();
+  for (int e = threadIdx.x; e < E1; e += 256) {
+    const float v = red[e] + red[E1 + e] + red[2 * E1 + e] + red[3 * E1 + e];
+    const int ln = e & 63, r = (e >> 6) & 3, t = e >> 8;
+    const int nb = t % SK_NB, mt = t / SK_NB;
+    const int m = 64 + mt * 16 + (ln >> 4) * 4 + r, n = n0 + nb * 16 + (ln & 15);
     if (m >= a.M || n >= a.N) continue;
     if (a.S == 1) sk_store(a, m, n, sk_epilogue(v, n, a));
     else a.ws[((long)s * a.M + m) * a.N + n] = v;
@@ -386,34 +494,32 @@ inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 extern "C" int udm_gemm_skinny_bf16(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc, int out_f32,
                                     int epilogue, const float* bias, float* ws, int64_t ws_elems, hipStream_t stream) {
   UDM_CHECK_ARG(A && W && C, "udm_gemm_skinny_bf16: null pointer");
-  UDM_CHECK_ARG(M >= 1 && M <= 64 && N >= 1 && K >= 32 && K % 32 == 0, "udm_gemm_skinny_bf16: bad shape M=%ld N=%ld K=%ld (1 <= M <= 64, K %% 32 == 0)",
+  UDM_CHECK_ARG(M >= 1 && M <= 128 && N >= 1 && K >= 32 && K % 32 == 0, "udm_gemm_skinny_bf16: bad shape M=%ld N=%ld K=%ld (1 <= M <= 128, K %% 32 == 0)",
                 (long)M, (long)N, (long)K);
   UDM_CHECK_ARG(lda >= K && ldw >= K && ldc >= N && lda % 8 == 0 && ldw % 8 == 0, "udm_gemm_skinny_bf16: bad leading dimensions");
   UDM_CHECK_ARG(al16(A) && al16(W) && al16(C) && (!ws || al16(ws)) && (!bias || al16(bias)), "udm_gemm_skinny_bf16: operands must be 16-byte aligned");
   UDM_CHECK_ARG(epilogue == UDM_EPI_NONE || epilogue == UDM_EPI_BIAS || epilogue == UDM_EPI_BIAS_GELU, "udm_gemm_skinny_bf16: epilogue %d not supported", epilogue);
   UDM_CHECK_ARG(epilogue == UDM_EPI_NONE || bias, "udm_gemm_skinny_bf16: the epilogue needs a bias");
   UDM_CHECK_ARG(N < (1L << 30) && K < (1L << 30), "udm_gemm_skinny_bf16: shape too large");
-  const int nblk = (int)((N + 31) / 32);
-  // K split over workgroups until about two workgroups per CU stream (each slice >= 128 deep, the partial slabs must fit ws)
-  int S = 1;
-  if (ws && nblk < 512) {
-    S = (512 + nblk / 2) / nblk;
-    S = min(S, (int)(K / 128));
-    S = min(S, 32);
-    const int64_t cap = ws_elems / (M * N);
-    if (S > cap) S = (int)cap;
-    if (S < 1) S = 1;
-  }
-  int kslice = (int)(((K + S - 1) / S + 31) / 32 * 32);
-  S = (int)((K + kslice - 1) / kslice);
-  SkArgs a{(const bf16_t*)A, (const bf16_t*)W, C, ws, bias, (long)lda, (long)ldw, (long)ldc, (int)M, (int)N, (int)K, kslice, S, out_f32, epilogue};
-  const dim3 grid(nblk, S);
-  const int MT = (int)((M + 15) / 16);
-  switch (MT) {
-    case 1: hipLaunchKernelGGL(skinny_gemm_kernel<1>, grid, dim3(256), 0, stream, a); break;
-    case 2: hipLaunchKernelGGL(skinny_gemm_kernel<2>, grid, dim3(256), 0, stream, a); break;
-    case 3: hipLaunchKernelGGL(skinny_gemm_kernel<3>, grid, dim3(256), 0, stream, a); break;
-    default: hipLaunchKernelGGL(skinny_gemm_kernel<4>, grid, dim3(256), 0, stream, a); break;
+  // K split over workgroups until about two workgroups per CU stream (each slice >= 128 deep, the partial slabs must fit ws): skinny_plan.h
+  const SkinnyPlan pl = skinny_plan(M, N, K, ws != nullptr, ws_elems);
+  const int S = (int)pl.S;
+  SkArgs a{(const bf16_t*)A, (const bf16_t*)W, C, ws, bias, (long)lda, (long)ldw, (long)ldc, (int)M, (int)N, (int)K, (int)pl.kslice, S, out_f32, epilogue};
+  const dim3 grid((unsigned)pl.nblk, (unsigned)S);
+  if (M <= 64) {
+    switch ((int)((M + 15) / 16)) {
+      case 1: hipLaunchKernelGGL(skinny_gemm_kernel<1>, grid, dim3(256), 0, stream, a); break;
+      case 2: hipLaunchKernelGGL(skinny_gemm_kernel<2>, grid, dim3(256), 0, stream, a); break;
+      case 3: hipLaunchKernelGGL(skinny_gemm_kernel<3>, grid, dim3(256), 0, stream, a); break;
+      default: hipLaunchKernelGGL(skinny_gemm_kernel<4>, grid, dim3(256), 0, stream, a); break;
+    }
+  } else {   // rows [0, 64) and [64, M) in one workgroup, the weights loaded once for both
+    switch ((int)((M - 64 + 15) / 16)) {
+      case 1: hipLaunchKernelGGL(skinny_gemm2_kernel<1>, grid, dim3(256), 0, stream, a); break;
+      case 2: hipLaunchKernelGGL(skinny_gemm2_kernel<2>, grid, dim3(256), 0, stream, a); break;
+      case 3: hipLaunchKernelGGL(skinny_gemm2_kernel<3>, grid, dim3(256), 0, stream, a); break;
+      default: hipLaunchKernelGGL(skinny_gemm2_kernel<4>, grid, dim3(256), 0, stream, a); break;
+    }
   }
   UDM_CHECK_LAUNCH("udm_gemm_skinny_bf16");
   if (S > 1) {

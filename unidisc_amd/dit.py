@@ -520,7 +520,7 @@ class DIT(nn.Module, _HubMixin):
         B, Lmax = int(batch_size), int(seq_len)
         Bp = _ceil(B, 8)
         if Bp > K.SKINNY_MAX_ROWS:
-            raise NotImplementedError(f"unidisc_amd.DIT.reset_kv_cache: {B} rows (padded {Bp}); the decode step serves at most {K.SKINNY_MAX_ROWS}")
+            raise NotImplementedError(f"unidisc_amd.DIT.reset_kv_cache: {B} rows (padded {Bp}); the decode step serves at most {K.SKINNY_MAX_ROWS} rows")
         if not 1 <= Lmax <= self.total_length:
             raise ValueError(f"unidisc_amd.DIT.reset_kv_cache: seq_len {Lmax} outside [1, model.length = {self.total_length}]")
         self._kv = None

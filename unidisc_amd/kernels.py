@@ -1088,12 +1088,14 @@ def silu_bwd(x, dy, out=None):
 
 
 # ------------------------------------------------------------------------------------------------ KV-cached AR decoding (csrc/decode.hip)
-SKINNY_MAX_ROWS = 64
+SKINNY_MAX_ROWS = 128
 
 
 def gemm_skinny(a, w, out=None, *, N=None, epilogue=EPI_NONE, bias=None, out_dtype=BF16, ws=None):
-    """out[M, N] = a[M, K] @ w[N, K]^T (+ bias, + GELU) for M <= 64 rows: the weight-streaming GEMM of a decode step.  `w` is a bf16 weight shadow
-    (its padded rows past N are never read); ws: fp32 scratch for the K split (None: the per-device scratch, grown to what this shape's split needs)."""
+    """out[M, N] = a[M, K] @ w[N, K]^T (+ bias, + GELU) for M <= SKINNY_MAX_ROWS = 128 rows: the weight-streaming GEMM of a decode step.  `w` is a bf16
+    weight shadow (its padded rows past N are never read); ws: fp32 scratch for the K split (None: the per-device scratch, grown to what this shape's split
+    needs).  Above 64 rows the rows [0, 64) and [64, M) are two row groups of one launch on the same weight fragments: with the same K split (a workspace
+    of at least skinny_ws_elems(M, N, K)) each group equals, bit for bit, a call on its rows alone."""
     _chk(a, BF16, "gemm_skinny a"), _chk(w, BF16, "gemm_skinny w")
     M, K = a.shape
     N = w.shape[0] if N is None else N
@@ -1108,8 +1110,9 @@ def gemm_skinny(a, w, out=None, *, N=None, epilogue=EPI_NONE, bias=None, out_dty
 
 
 def skinny_ws_elems(M, N, K):
-    """fp32 elements udm_gemm_skinny_bf16 uses for its K split of this shape (its split plan: about two workgroups of 32 columns per CU, slices of at least 128
-    deep, at most 32), 0 when it does not split."""
+    """fp32 elements udm_gemm_skinny_bf16 uses for its K split of this shape (its split plan, csrc/skinny_plan.h: about two workgroups of 32 columns per CU,
+    slices of at least 128 deep, at most 32), 0 when it does not split.  The number of slices depends on (N, K) alone; M only scales the slabs, so a
+    workspace of this size leaves an M-row call the split of any call of fewer rows."""
     nblk = -(-N // 32)
     if nblk >= 512:
         return 0
